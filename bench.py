@@ -17,8 +17,10 @@ One "step" = one pass of the hot path over one synthetic video stream per GPU.  
 Weights: seeded random init at the true shapes, bf16 (no checkpoints exist offline).  With N > 1 every rank runs its own
 streams (weak scaling) and the per-frame scores are all-gathered over RCCL inside the timed region.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP events on the launch stream) and `cpu_baseline`
-(the oracle on the host cores, bounded sample).
+Prints ONE JSON line (rank 0): `value` frames/s and `ms_per_step` of the `--steps` timed steps.  A plain run does nothing else; with `--full` the line
+also carries `roofline` (dominant kernel, HIP events on the launch stream), `cpu_baseline` (the oracle on the host cores, bounded sample), the in-run
+parity check and the secondary legs (`multi_stream`, `host_frames`).  `--dump-outputs DIR` writes what the last timed step returned (per-frame
+scores, response token ids, final KV lengths) as DIR/<name>.npy; inputs are seeded, so two builds can be compared output for output.
 """
 import argparse, json, math, os, random, socket, subprocess, sys, time
 
@@ -211,6 +213,9 @@ def parse(argv=None):
     p.add_argument('--frames-on-host', action='store_true', help='the uint8 frames start in PINNED HOST memory and cross to the GPU inside the timed region (per tower batch, on the tower stream) -- the end-to-end form of the path (the reference: pixel_values.to(cuda), test/inference.py:203); without the flag the frames are resident in HBM (the headline, per the bench contract) and the host-frames rate is reported next to it under "host_frames"')
     p.add_argument('--host-frames-steps', type=int, default=3, help='steps of the secondary host-frames leg (0 = skip)')
     p.add_argument('--layers', type=int, default=None, help='debug: override LLM layer count (INVALID as a measurement)')
+    p.add_argument('--full', action='store_true', help='also run everything beyond the headline figure: the roofline (profiled passes and sampled kernels in the timed region), GPU idle share, '
+                   'step-to-step and native-gather checks, the oracle parity check, the CPU baseline and the multi-stream / host-frames legs.  Off: set up, warm up, time, print')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64)')
     a = p.parse_args(argv)
     c = CONFIGS[a.config]
     if a.frames is None: a.frames = c['frames']
@@ -455,14 +460,21 @@ def bench_native336(args):
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0
     assert out.shape == (args.frames, 37, Cw) and bool(torch.isfinite(out.float()).all())
-    prof(True); enc(frames); torch.cuda.synchronize(device); prof(False)
-    ms, cnt, by, fl = (C.c_double * n)(), (C.c_int64 * n)(), (C.c_double * n)(), (C.c_double * n)()
-    _lib.check(L_.mmd_prof_read(enc._ctx, ms, cnt, by, fl), enc._ctx)
-    i = _lib.K_NAMES.index('gemm_tile')
-    ach = fl[i] / max(1, cnt[i]) / (ms[i] / max(1, cnt[i]) * 1e-3) / 1e12
-    roof = dict(bound='mfma', kernel='gemm_tile', achieved=round(ach, 2), peak=MFMA_BF16_PEAK_TF, unit='TFLOP/s', frac=round(ach / MFMA_BF16_PEAK_TF, 4), traffic=None,
-                avg_launch_us=round(ms[i] / max(1, cnt[i]) * 1e3, 2), launches_timed=int(cnt[i]), per_class_ms_untimed_pass={k: round(ms[j], 1) for j, k in enumerate(_lib.K_NAMES)},
-                source='one more pass of the same workload, every launch bracketed with HIP events (untimed)')
+    if args.dump_outputs:
+        # [T, 37, C] frame tokens; past the size limit, a fixed seeded sample of whole frames (their indices stored next to them)
+        keep = min(args.frames, DUMP_LIMIT_BYTES // (37 * Cw * 4 + 8))
+        idx = sorted(random.Random(0).sample(range(args.frames), keep)) if keep < args.frames else list(range(args.frames))
+        dump_outputs(args.dump_outputs, {'frame_tokens': out[idx].float().cpu().numpy(), 'frame_index': torch.tensor(idx, dtype=torch.float64).numpy()})
+    roof = None
+    if args.full:
+        prof(True); enc(frames); torch.cuda.synchronize(device); prof(False)
+        ms, cnt, by, fl = (C.c_double * n)(), (C.c_int64 * n)(), (C.c_double * n)(), (C.c_double * n)()
+        _lib.check(L_.mmd_prof_read(enc._ctx, ms, cnt, by, fl), enc._ctx)
+        i = _lib.K_NAMES.index('gemm_tile')
+        ach = fl[i] / max(1, cnt[i]) / (ms[i] / max(1, cnt[i]) * 1e-3) / 1e12
+        roof = dict(bound='mfma', kernel='gemm_tile', achieved=round(ach, 2), peak=MFMA_BF16_PEAK_TF, unit='TFLOP/s', frac=round(ach / MFMA_BF16_PEAK_TF, 4), traffic=None,
+                    avg_launch_us=round(ms[i] / max(1, cnt[i]) * 1e3, 2), launches_timed=int(cnt[i]), per_class_ms_untimed_pass={k: round(ms[j], 1) for j, k in enumerate(_lib.K_NAMES)},
+                    source='one more pass of the same workload, every launch bracketed with HIP events (untimed)')
     gf = 2 * 577 * (4 * Cw * Cw + 2 * Cw * CI) * L + 2 * 576 * 588 * Cw + 4 * 577 * 577 * Cw * L          # per frame: encoder GEMMs + patch embed + attention
     line = {'metric': 'video frames/sec (vision encode only, native 336 px, CLIP-L/14-336 secondary encoder)', 'value': round(args.steps * args.frames / dt, 2), 'unit': 'frames/s',
             'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 2), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
@@ -471,6 +483,34 @@ def bench_native336(args):
                        'algorithmic_gflop_per_frame': round(gf / 1e9, 1), 'weights': 'random init N(0,0.02), true shape (24 layers)', 'note': 'a separate configuration: never mixed with the 384-px LLaVA path'},
             'roofline': roof, 'cpu_baseline': None}
     _emit(line)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 only), at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values()), {k: v.dtype for k, v in arrays.items()}
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_LIMIT_BYTES, {k: v.nbytes for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
+
+
+def stream_outputs(allsc, results):
+    """What a caller of the timed path receives from one step: the gathered per-frame scores [world, S, T, 2] (informative, relevance) and, for this rank's S streams,
+    the response token ids [S, R, L] (-1 past a response's end) and the final KV length [S]."""
+    import numpy as np
+    R = max([len(r['response_token_ids']) for r in results], default=0)
+    L = max([len(ids) for r in results for ids in r['response_token_ids']], default=0)
+    ids = np.full((len(results), R, L), -1.0, dtype=np.float64)
+    for s, r in enumerate(results):
+        for j, x in enumerate(r['response_token_ids']):
+            ids[s, j, :len(x)] = x
+    return {'scores': allsc.float().cpu().numpy(), 'response_token_ids': ids,
+            'final_kv_len': np.array([r['final_kv_len'] for r in results], dtype=np.float64)}
 
 
 _REAL_STDOUT = None
@@ -551,34 +591,34 @@ def main():
         sc, n_resp = run_stream(driver, frames, query)
         return [sc], n_resp
 
-    # untimed pass with every kernel class bracketed: finds the dominant kernel class of this schedule
-    model.prof_reset(); model.prof_enable(True)
-    one_step()
-    model.prof_enable(False)
-    prof_all = model.prof_read()
-    # the same with tower and LLM on ONE HIP stream and a wall clock around it: what fraction of the wall is no kernel of ours running (host scheduling,
-    # launch gaps, syncs).  Diagnostic for an N-rank run on a CPU-quota'd box: a rank that gets fewer cores shows a larger idle fraction, not slower kernels.
-    gpu_idle = None
-    if multi_runner is None:
-        d1 = make_driver(argparse.Namespace(**{**vars(args), 'no_overlap': True}), model, tok, threshold, forced)
-        run_stream(d1, frames, query)                           # (workspaces / arenas warm)
-        model.prof_reset(); model.prof_set_stride(1); model.prof_enable(True)
-        torch.cuda.synchronize(device); tw = time.perf_counter()
-        run_stream(d1, frames, query)
-        torch.cuda.synchronize(device); tw = time.perf_counter() - tw
+    gpu_idle, dom, second = None, None, None
+    if args.full:
+        # untimed pass with every kernel class bracketed: finds the dominant kernel class of this schedule
+        model.prof_reset(); model.prof_enable(True)
+        one_step()
         model.prof_enable(False)
-        busy = sum(v['ms'] for v in model.prof_read().values()) * 1e-3
-        gpu_idle = dict(frac=round(max(0.0, 1.0 - busy / tw), 4), wall_ms=round(tw * 1e3, 1), kernel_ms=round(busy * 1e3, 1),
-                        note='one stream, every launch bracketed with HIP events (untimed pass; the event pairs themselves add ~2 us per launch to the wall)')
-    dom = max(prof_all, key=lambda k: prof_all[k]['ms'])
-    # the tile-GEMM class (MFMA-bound: tower + LLM chunk GEMMs) and the weight-streaming class (HBM-bound: decode GEMV) are within a few per cent
-    # of each other on this workload; the roofline object stays on the MFMA class whenever it is within 20 % of the largest one (so the figure
-    # tracks one kernel family from round to round), the other class is reported under `roofline_secondary`
-    second = None
-    if dom != 'gemm_tile' and prof_all['gemm_tile']['ms'] >= 0.8 * prof_all[dom]['ms']:
-        dom, second = 'gemm_tile', dom
-    elif dom == 'gemm_tile' and prof_all['gemm_skinny']['ms'] >= 0.5 * prof_all[dom]['ms']:
-        second = 'gemm_skinny'
+        prof_all = model.prof_read()
+        # the same with tower and LLM on ONE HIP stream and a wall clock around it: what fraction of the wall is no kernel of ours running (host scheduling,
+        # launch gaps, syncs).  Diagnostic for an N-rank run on a CPU-quota'd box: a rank that gets fewer cores shows a larger idle fraction, not slower kernels.
+        if multi_runner is None:
+            d1 = make_driver(argparse.Namespace(**{**vars(args), 'no_overlap': True}), model, tok, threshold, forced)
+            run_stream(d1, frames, query)                           # (workspaces / arenas warm)
+            model.prof_reset(); model.prof_set_stride(1); model.prof_enable(True)
+            torch.cuda.synchronize(device); tw = time.perf_counter()
+            run_stream(d1, frames, query)
+            torch.cuda.synchronize(device); tw = time.perf_counter() - tw
+            model.prof_enable(False)
+            busy = sum(v['ms'] for v in model.prof_read().values()) * 1e-3
+            gpu_idle = dict(frac=round(max(0.0, 1.0 - busy / tw), 4), wall_ms=round(tw * 1e3, 1), kernel_ms=round(busy * 1e3, 1),
+                            note='one stream, every launch bracketed with HIP events (untimed pass; the event pairs themselves add ~2 us per launch to the wall)')
+        dom = max(prof_all, key=lambda k: prof_all[k]['ms'])
+        # the tile-GEMM class (MFMA-bound: tower + LLM chunk GEMMs) and the weight-streaming class (HBM-bound: decode GEMV) are within a few per cent
+        # of each other on this workload; the roofline object stays on the MFMA class whenever it is within 20 % of the largest one (so the figure
+        # tracks one kernel family from round to round), the other class is reported under `roofline_secondary`
+        if dom != 'gemm_tile' and prof_all['gemm_tile']['ms'] >= 0.8 * prof_all[dom]['ms']:
+            dom, second = 'gemm_tile', dom
+        elif dom == 'gemm_tile' and prof_all['gemm_skinny']['ms'] >= 0.5 * prof_all[dom]['ms']:
+            second = 'gemm_skinny'
 
     def sync():
         torch.cuda.synchronize(device)
@@ -601,7 +641,7 @@ def main():
     for w in range(max(1, args.warmup) if world > 1 else args.warmup):
         scs, n_resp = one_step()
         allsc, lens = gather(scs)
-    prof_on = not args.no_prof
+    prof_on = args.full and not args.no_prof                # the roofline's kernel sample: --full only
     model.prof_reset()
     model.prof_set_stride(args.prof_stride)                 # every 7th launch of the class carries the two HIP events (sampling)
     model.prof_enable([dom] + ([second] if second else []) if prof_on else False)        # only the dominant class(es) are bracketed inside the timed region
@@ -629,21 +669,28 @@ def main():
     dt = float(tmax.item())
     prof = model.prof_read()
     assert allsc.shape == (world, S, T, 2) and int(lens.min()) == T
-    if ng is not None:          # cross-check of the native transport against torch.distributed's, same scores, outside the timed region
-        a2, l2 = gather_scores(scs, t_max=T, n_max=S)
-        same = torch.equal(l2.cpu(), lens.cpu()) and torch.equal(torch.nan_to_num(a2.cpu()), torch.nan_to_num(allsc.cpu()))
-        native = 'ok' if same else 'MISMATCH vs torch.distributed'
+    if rank == 0 and args.dump_outputs:                     # the last timed step's results, before any secondary leg reuses the driver
+        results = multi_runner.last if multi_runner is not None else \
+            [dict(response_token_ids=driver.response_token_ids, final_kv_len=len(driver.past_key_values) if driver.past_key_values else 0)]
+        dump_outputs(args.dump_outputs, stream_outputs(allsc, results))
+    if ng is not None:
+        if args.full:           # cross-check of the native transport against torch.distributed's, same scores, outside the timed region
+            a2, l2 = gather_scores(scs, t_max=T, n_max=S)
+            same = torch.equal(l2.cpu(), lens.cpu()) and torch.equal(torch.nan_to_num(a2.cpu()), torch.nan_to_num(allsc.cpu()))
+            native = 'ok' if same else 'MISMATCH vs torch.distributed'
         ng.close()
-    # what was timed is checked (outside the timed region): every gathered score of every step is a finite probability, and -- same frames, same weights,
-    # fixed reduction orders, no atomics -- every timed step produced the SAME bits whatever the tower / decode overlap did
-    blocks = [b.cpu() for b in step_blocks]
-    finite = all(bool(torch.isfinite(b).all()) and bool(((b >= 0) & (b <= 1)).all()) for b in blocks)
-    identical = all(torch.equal(b, blocks[0]) for b in blocks[1:])
-    step_maxdiff = max([float((b - blocks[0]).abs().max()) for b in blocks[1:]], default=0.0)
-    if not finite:
-        raise SystemExit('bench.py: non-finite / out-of-range scores in the timed region')
-    verified = dict(scores_finite_in_0_1=finite, steps_bit_identical=identical, max_abs_step_to_step_diff=step_maxdiff, steps_compared=len(blocks),
-                    note='all per-frame scores of all timed steps; parity of this workload against the fp32 oracle: tests/test_gpu_fullsize.py')
+    verified = None
+    if args.full:
+        # what was timed is checked (outside the timed region): every gathered score of every step is a finite probability, and -- same frames, same weights,
+        # fixed reduction orders, no atomics -- every timed step produced the SAME bits whatever the tower / decode overlap did
+        blocks = [b.cpu() for b in step_blocks]
+        finite = all(bool(torch.isfinite(b).all()) and bool(((b >= 0) & (b <= 1)).all()) for b in blocks)
+        identical = all(torch.equal(b, blocks[0]) for b in blocks[1:])
+        step_maxdiff = max([float((b - blocks[0]).abs().max()) for b in blocks[1:]], default=0.0)
+        if not finite:
+            raise SystemExit('bench.py: non-finite / out-of-range scores in the timed region')
+        verified = dict(scores_finite_in_0_1=finite, steps_bit_identical=identical, max_abs_step_to_step_diff=step_maxdiff, steps_compared=len(blocks),
+                        note='all per-frame scores of all timed steps; parity of this workload against the fp32 oracle: tests/test_gpu_fullsize.py')
 
     def roof_from(p, name):
         avg_ms = p['ms'] / p['launches']
@@ -709,10 +756,10 @@ def main():
         roof2 = roof_from(prof[second], second)
         roof2['sampling_stride'] = args.prof_stride
     cpu = None
-    if rank == 0 and not (args.no_cpu_baseline or args.tiny or world > 1):
+    if args.full and rank == 0 and not (args.no_cpu_baseline or args.tiny or world > 1):
         cpu = cpu_baseline()
     multi = None
-    if args.multi_stream > 1 and multi_runner is None and args.mode == 'response':
+    if args.full and args.multi_stream > 1 and multi_runner is None and args.mode == 'response':
         # secondary measurement, outside the timed region and never the headline: S streams per GPU in shared forwards
         fps, ms_step, rounds, replay, frac = run_multi_stream(args, model, tok, frames, query, args.multi_stream, args.multi_frames_per_forward,
                                                               steps=1, warmup=1, device=device)
@@ -720,7 +767,7 @@ def main():
                      ms_per_step=round(ms_step, 1), forwards_per_step=rounds, replayed_frames=replay, time_in_forwards_frac=round(frac, 3),
                      note='mmduet_amd.multistream: one LLM forward carries frame chunks and decode rows of all streams; per-stream results as single-stream')
     host_leg = None
-    if multi_runner is None and args.phase == 'ab' and args.host_frames_steps > 0 and not args.frames_on_host:
+    if args.full and multi_runner is None and args.phase == 'ab' and args.host_frames_steps > 0 and not args.frames_on_host:
         # secondary measurement, never the headline: the same workload with the frames starting in pinned host memory; every tower batch uploads its own frames
         # on the tower's side stream inside the timed steps (mmduet_amd/inference.py input_video_stream / _issue_vit)
         run_stream(driver, frames_host, query)
@@ -736,8 +783,8 @@ def main():
                         rel_to_resident=round((world * args.host_frames_steps * args.frames / th) / (world * S * args.steps * args.frames / dt), 4),
                         scores_equal_resident=bool(torch.equal(sc_h, scs[0])) if not args.frames_on_host else None,
                         note='frames in pinned host memory, %.1f MB per stream uploaded per tower batch inside the timed steps; `value` of the line is the HBM-resident form' % (frames_host.numel() / 1e6))
-    parity = recorded_parity(args)
-    if rank == 0 and not (args.tiny or args.no_parity_check or args.phase == 'b' or args.layers):
+    parity = recorded_parity(args) if args.full else None
+    if args.full and rank == 0 and not (args.tiny or args.no_parity_check or args.phase == 'b' or args.layers):
         try:
             measured = measured_parity(args, model, tok, cfg, frames, query, forced, device)
         except Exception as e:                               # the checker never blocks the line
@@ -753,7 +800,7 @@ def main():
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16' if args.weights == 'bf16' else 'fp8_e4m3 weights x bf16 activations',
             'data': 'synthetic', 'rccl_ranks': rccl_ranks,
             'host_cpu_s_per_step': round(host_cpu_s / max(1, args.steps), 3), 'host_sync': args.host_sync, 'host_threads_cpu_s_per_step': [dict(comm=n, cpu_s=c, thread=w) for c, n, w in host_threads if c > 0.005], 'nproc_granted': effective_cpus(), 'nproc_visible': os.cpu_count(),
-            'torch_threads': torch.get_num_threads(), 'gpu_idle_frac': gpu_idle, 'gpu_idle_frac_kernel_trace': recorded_idle(),
+            'torch_threads': torch.get_num_threads(), 'gpu_idle_frac': gpu_idle, 'gpu_idle_frac_kernel_trace': recorded_idle() if args.full else None,
             'config': {'workload': ('tiny-plumbing' if args.tiny else 'llava-onevision-qwen2-7b + siglip-so400m-384') +
                        f', {args.frames}-frame 1fps {R}px stream{"s" if S > 1 else ""} ({S} per GPU), ' + CONFIGS[args.config]['text'],
                        'name': args.config, 'frames_per_forward': args.frames_per_forward, 'streams_per_gpu': S, 'responses_per_stream': int(n_resp),

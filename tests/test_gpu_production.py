@@ -1068,7 +1068,7 @@ def test_bench_launches_its_own_ranks_nccl():
     import subprocess, sys
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--tiny', '--frames', '12', '--steps', '1', '--warmup', '1', '--multi-stream', '0',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--no-cpu-baseline', '--full'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['rccl_ranks'] == 2 and line['config']['native_gather_check'] == 'ok'

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O
 out=$O/r04_host_thread_probe.txt; : > $out
 run() {
   tag="$1"; shift
-  line=$(env "$@" python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --multi-stream 0 --no-parity-check 2>/dev/null | tail -1)
+  line=$(env "$@" python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --multi-stream 0 --no-parity-check 2>/dev/null | tail -1)
   echo "$tag $(echo $line | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("frames/s", d["value"], "host_cpu_s_per_step", d["host_cpu_s_per_step"], "threads", [(t["comm"], t["cpu_s"], t["thread"]) for t in d["host_threads_cpu_s_per_step"]])')" >> $out
 }
 if [ "$1" != flags ]; then
@@ -19,7 +19,7 @@ fi
 # which part of the run keeps the second thread busy?  (appended in round 4: bench flags instead of runtime knobs)
 run2() {
   tag="$1"; shift
-  line=$(python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --multi-stream 0 --no-parity-check "$@" 2>/dev/null | tail -1)
+  line=$(python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --multi-stream 0 --no-parity-check "$@" 2>/dev/null | tail -1)
   echo "$tag $(echo $line | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("frames/s", d["value"], "host_cpu_s_per_step", d["host_cpu_s_per_step"], "threads", [(t["comm"], t["cpu_s"], t["thread"]) for t in d["host_threads_cpu_s_per_step"]])')" >> $out
 }
 if [ "$1" = flags ]; then

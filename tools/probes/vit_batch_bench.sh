@@ -3,6 +3,6 @@
 cd $GRAFT_REPO_ROOT
 for r in $(seq 1 ${2:-2}); do
  for b in $1; do
-  python3 bench.py --vit-batch $b --steps 3 --warmup 1 --multi-stream 0 --no-cpu-baseline --no-parity-check --host-frames-steps 0 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d.get('roofline') or {}; print('vit_batch $b:', d['value'], d['ms_per_step'], r.get('frac'), r.get('avg_launch_us'))"
+  python3 bench.py --full --vit-batch $b --steps 3 --warmup 1 --multi-stream 0 --no-cpu-baseline --no-parity-check --host-frames-steps 0 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d.get('roofline') or {}; print('vit_batch $b:', d['value'], d['ms_per_step'], r.get('frac'), r.get('avg_launch_us'))"
  done
 done

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 $B --steps 5 --warmup 1 --no-cpu-baseline 2> $O/${tag}_bench.err | tail -1 > $O/${tag}_bench.json
 $B --steps 5 --warmup 1 --no-cpu-baseline --weights fp8 2>> $O/${tag}_bench.err | tail -1 > $O/${tag}_bench_fp8.json
 P="python3 $R/bench.py --steps 1 --warmup 0 --no-prof --no-overlap --multi-stream 0 --no-cpu-baseline"

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 $B --steps 5 --warmup 1 > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 $B --steps 3 --warmup 1 --no-overlap --multi-stream 0 --no-cpu-baseline > $O/${tag}_bench_nooverlap.json 2>> $O/${tag}_bench.err
 $B --steps 3 --warmup 1 --responses 0 --multi-stream 0 --no-cpu-baseline > $O/${tag}_bench_noresponses.json 2>> $O/${tag}_bench.err
