@@ -7,6 +7,33 @@ from helpers import product_config
 from conftest import load_golden_weights
 
 
+def quantize_ref(W):
+    """Host-side statement of the fp8 scheme: per output channel, scale = amax / 448, q = float8_e4m3fn(W / scale) (round to nearest even)."""
+    Wf = W.float()
+    amax = Wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    q = (Wf / scale[:, None]).to(torch.float8_e4m3fn)
+    return q, scale
+
+
+# out-of-range write checks: quiet NaNs with a payload no kernel produces (a computed NaN is the canonical 0x7FC0 / 0x7FC00000)
+SENTINEL_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5}
+_INT_OF = {torch.bfloat16: torch.int16, torch.float32: torch.int32}
+
+
+def guarded(rows, cols, dtype, device, before=16, after=256):
+    """A [before + rows + after, cols] buffer filled with the sentinel; -> (buffer, the [rows, cols] view in its middle).  256 rows after Y: a
+    whole row tile of the largest kernel (ring: 256 rows) past M."""
+    buf = torch.empty(before + rows + after, cols, dtype=dtype, device=device)
+    buf.view(_INT_OF[dtype]).fill_(SENTINEL_BITS[dtype])
+    return buf, buf[before:before + rows]
+
+
+def sentinel_intact(t):
+    """True when every element of t still holds the sentinel bits"""
+    return bool((t.view(_INT_OF[t.dtype]) == SENTINEL_BITS[t.dtype]).all())
+
+
 class RawOps:
     def __init__(self, dtype, max_step_tokens=64):
         """max_step_tokens > 2048: the context gets the large (192 MB) split-K slab workspace of a model that runs several streams' merged chunks."""
@@ -28,6 +55,45 @@ class RawOps:
         check(lib().mmd_op_gemm(self.ctx, _ptr(Xd), _ptr(Wd), _ptr(bd), _ptr(Rd), _ptr(Y), M, N, K, EPI[epi], int(out_f32), variant), self.ctx, 'gemm')
         torch.cuda.synchronize()
         return Y
+
+    # ---- raw calls on caller-owned device buffers (tests/test_gpu_gemm_regimes.py): no copies, Y may sit inside a guarded buffer ----
+    def last_plan(self):
+        """(kernel GEMM_K_*, output tiles, K splits, blocks) of this context's most recent GEMM"""
+        p = (C.c_int * 4)()
+        check(lib().mmd_op_gemm_last_plan(self.ctx, p), self.ctx, 'last_plan')
+        return tuple(p)
+
+    def gemm_into(self, Y, X, W, bias=None, R=None, epi='none', out_f32=False, variant=0):
+        M, K = X.shape; N = W.shape[0]
+        self.m._bind_stream()
+        check(lib().mmd_op_gemm(self.ctx, _ptr(X), _ptr(W), _ptr(bias), _ptr(R), _ptr(Y), M, N, K, EPI[epi], int(out_f32), variant), self.ctx, 'gemm')
+        torch.cuda.synchronize()
+
+    def gemm_w8_into(self, Y, X, Wq, q8, scale, bias=None, R=None, epi='none', variant=0):
+        M, K = X.shape; N = Wq.shape[0]
+        self.m._bind_stream()
+        check(lib().mmd_op_gemm_w8(self.ctx, _ptr(X), _ptr(Wq), _ptr(q8), _ptr(scale), _ptr(bias), _ptr(R), _ptr(Y), M, N, K, EPI[epi], 0, variant), self.ctx, 'gemm_w8')
+        torch.cuda.synchronize()
+
+    def gemm_slabs_into(self, slabs, X, W, max_splits, variant=2):
+        """slabs: device fp32 with room for max_splits x [M, N]; -> number of slabs written"""
+        M, K = X.shape; N = W.shape[0]
+        n = C.c_int(0)
+        self.m._bind_stream()
+        check(lib().mmd_op_gemm_slabs(self.ctx, _ptr(X), _ptr(W), M, N, K, variant, _ptr(slabs), max_splits, C.byref(n)), self.ctx, 'gemm_slabs')
+        torch.cuda.synchronize()
+        return n.value
+
+    def quantize_fp8(self, W):
+        """mmd_op_quantize_fp8 on a copy of W [N, K]: -> (bf16(q) [N, K], q8 bytes [N, K], scale [N] fp32)"""
+        N, K = W.shape
+        Wq = W.to(device=self.dev, dtype=torch.bfloat16).contiguous().clone()
+        q8 = torch.empty(N, K, dtype=torch.uint8, device=self.dev)
+        sc = torch.empty(N, dtype=torch.float32, device=self.dev)
+        self.m._bind_stream()
+        check(lib().mmd_op_quantize_fp8(self.ctx, _ptr(Wq), N, K, _ptr(q8), _ptr(sc)), self.ctx, 'quantize')
+        torch.cuda.synchronize()
+        return Wq, q8, sc
 
     def gemm_slabs(self, X, W, variant=2, max_splits=16):
         """-> (sum of the fp32 partial slabs [M, N], number of slabs)"""

@@ -23,25 +23,11 @@ def ops():
     return RawOps(torch.bfloat16)
 
 
-def quantize_ref(W):
-    """Host-side statement of the scheme: per output channel, scale = amax / 448, q = float8_e4m3fn(W / scale) (round to nearest even)."""
-    Wf = W.float()
-    amax = Wf.abs().amax(dim=1)
-    scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
-    q = (Wf / scale[:, None]).to(torch.float8_e4m3fn)
-    return q, scale
+from rawops import quantize_ref          # noqa: E402  (shared with tests/test_gpu_gemm_regimes.py)
 
 
 def hip_quantize(ops, W):
-    from mmduet_amd._lib import lib, check
-    N, K = W.shape
-    Wq = W.to(device=ops.dev, dtype=torch.bfloat16).contiguous().clone()
-    q8 = torch.empty(N, K, dtype=torch.uint8, device=ops.dev)
-    sc = torch.empty(N, dtype=torch.float32, device=ops.dev)
-    ops.m._bind_stream()
-    check(lib().mmd_op_quantize_fp8(ops.ctx, C.c_void_p(Wq.data_ptr()), N, K, C.c_void_p(q8.data_ptr()), C.c_void_p(sc.data_ptr())), ops.ctx, 'quantize')
-    torch.cuda.synchronize()
-    return Wq, q8, sc
+    return ops.quantize_fp8(W)
 
 
 def hip_gemm_w8(ops, X, Wq, q8, sc, bias=None, R=None, epi='none', variant=0):
