@@ -1303,7 +1303,7 @@ __global__ __launch_bounds__(256, 2) void attn_rowmajor_kernel(AttnP p) {
 #define D72_MFMA_PIN 0x7F6
 // Round 6: the hazard is removed structurally -- the tail's 16-deep MFMA no longer takes the 32-deep MFMA's result as SrcC at all: it accumulates onto ZERO in registers of its own
 // and one v_add_f32 per score register folds it in where the softmax reads the scores (D72_TAIL_SEPARATE 1).  No MFMA of the kernel then reads another MFMA's result of a different
-// depth, in any instruction order; the pin and the ISA test stay as the second line.  0 = the chained form of round 5 (A/B: `make EXTRA=-DD72_TAIL_SEPARATE=0`).
+// depth, in any instruction order; the pin and the ISA test stay as the second line.  0 = the chained form of round 5 (A/B: `make EXTRA_DEFS=-DD72_TAIL_SEPARATE=0`).
 #ifndef D72_TAIL_SEPARATE
 #define D72_TAIL_SEPARATE 1
 #endif

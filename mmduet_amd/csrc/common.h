@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/mmduet.h"
+#include "gemm_plan.h"          // GemmArgs, GemmPlan and the dispatch decision (host-only: no GPU header), cdiv / round_up, MMD_F16
 
 typedef uint16_t bf16_t;   // raw bfloat16 storage
 
@@ -26,7 +27,6 @@ __device__ __forceinline__ bf16_t f2bf(float f) {            // round-to-nearest
     return __builtin_bit_cast(bf16_t, b);
 }
 // ---- fp16 storage of the vision tower (config tower_dtype = fp16: the reference runs the tower under torch.cuda.amp.autocast(), models/modeling_live.py:28) ----
-constexpr int MMD_F16 = 2;             // internal launcher dtype, never a context dtype: 2-byte IEEE half activations / weights, fp32 accumulate and statistics
 typedef _Float16 f16_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
@@ -92,64 +92,18 @@ template <typename T> __device__ __forceinline__ float silu_t(float x) {
     if constexpr (sizeof(T) == 2) return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-x * 1.4426950408889634f)); else return silu_f(x);
 }
 
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 static inline size_t dtype_size(int dt) { return dt == MMD_F32 ? 4 : 2; }
 
 // device-resident state of a graph-captured decode step (updated by the last kernel of the graph)
 struct StepState { long long n_ctx; long long cap; void* K; void* V; int n_prev; int pad; };
 
-// ---- epilogues of the GEMM family ------------------------------------------------------------------------------
-enum { EPI_NONE = 0, EPI_GELU_TANH = 1, EPI_GELU_ERF = 2, EPI_RESID = 3, EPI_SWIGLU = 4 };
-enum { GEMM_AUTO = 0, GEMM_GENERIC = 1, GEMM_SKINNY = 2, GEMM_LARGE = 3, GEMM_BIG = 4, GEMM_SLAB = 5, GEMM_RING256 = 6, GEMM_RING256_SPLIT = 7,
-       GEMM_RINGX = 16 /* + 1: 4-wave 256x128 blocks, + 2: 32x32x16 MFMA, + 4: split K */,
-       GEMM_STREAM = 8 /* gemm_stream_kernel (32 < M <= 256, slabs or SwiGLU) */ };
-
-// Decode chain of the weight-streaming GEMV (M <= 16, bf16): the residual add + RMSNorm between two GEMVs costs a launch and a cold, dependent
-// load chain of its own (5.5 us + a kernel boundary, twice per layer at decode).  Instead
-//   * the PRODUCER (o_proj / down_proj) owns an n-tile over all of K (one 16-wave block per tile, K split over the waves, LDS reduce) and folds
-//     its result into the residual stream itself: h = rnd(rnd(x W^T) + h), leaving that tile's per-row sum of h^2 in ssq[m][tile];
-//   * the CONSUMER (qkv / gate_up) never reads a normalised activation: every lane builds its X fragment as rnd(gamma * rnd(h * inv)),
-//     inv = rsqrt(sum(ssq[m][:]) / K + eps) summed in a fixed order (deterministic; same rounding points as slab_resid_rmsnorm_kernel).
-constexpr int GEMV_SSQ_STRIDE = 256;   // floats per row in ssq (n-tiles of 16 columns: N <= 4096)
-constexpr int GEMV_CHAIN_ROWS = 4;     // rows a consumer keeps in LDS; K <= 4096
-struct GemvChain {
-    const void* xn_h = nullptr; const void* xn_gamma = nullptr; const float* xn_ssq = nullptr; float xn_eps = 0.f;     // consumer side
-    void* fin_h = nullptr; float* fin_ssq = nullptr;                                                                     // producer side
-};
-struct GemmArgs {
-    const void* X; int64_t ldx;      // [M,K]
-    const void* W; int64_t ldw;      // [N,K]  (nn.Linear layout); may be null when only Wp exists
-    const void* Wp = nullptr;        // same matrix, MFMA-fragment-major (launch_pack_w); enables the weight-streaming skinny kernel
-    const void* Wp8 = nullptr;       // fp8 e4m3 copy of the (unscaled) weights, fragment-major in 64-k pairs (launch_pack_w8): the weight-streaming
-                                     // kernels (M <= 64) read this one -- half the bytes; W / Wp then hold bf16(q), bit-identical values
-    const float* wscale = nullptr;   // per-output-channel scale of a quantised matrix: Y = (X . q^T) * wscale[n] (+ bias ...)
-    const void* bias;                // [N] or null (ctx dtype)
-    const void* R; int64_t ldr;      // residual [M,N] (EPI_RESID)
-    void* Y; int64_t ldy;            // [M,N] (or [M,N/2] for SWIGLU); ctx dtype, or fp32 if out_f32
-    int M, N, K;
-    int epi; int out_f32;
-    int variant;
-    float* splitk_ws; size_t splitk_ws_bytes;   // fp32 partial slabs
-    int no_gemv = 0;                            // A/B switch: use the LDS-staged skinny kernel also for M <= 16
-    int* ring_slabs_out = nullptr;              // if set: a split-K tile GEMM (ring / 128-row) leaves its [splits][M][N] fp32 slabs in splitk_ws and reports the count here
-                                                // (0 = the GEMM ran unsplit and applied its epilogue itself); the caller consumes them with launch_slab_resid_rmsnorm
-    int* slabs_out = nullptr;                   // if set (packed skinny path only): leave [splits][M][N] fp32 slabs in splitk_ws, no
-                                                // epilogue, and return the split count here; a fused consumer kernel reduces them
-    int ring_flags = 16;                        // ring GEMM instantiation the auto dispatch uses (launch_ringx flags; 16 = 8 waves, 256 x 256, early refill)
-    int ring_max_blocks = 0;                    // > 0: cap on the persistent grid (co-residency experiments: leave CU resources to another stream)
-    const GemvChain* chain = nullptr;           // gemv16 path only (M <= 16, packed bf16 / fp8 weights); see GemvChain
-    int* plan_out = nullptr;                    // if set: int[4] = {kernel (GEMM_K_*), output tiles, K splits, blocks launched}
-    int x_pm = 0, y_pm = 0;                     // X is / Y becomes a PIECE-MAJOR activation ([M/16][K/32] pieces of 16 rows x 32 elements, gemm_ringx_kernel): ring GEMMs only -- ask gemm_ring_auto first
-    int f16 = 0;                                // operands, bias, residual and output are IEEE half (launch_gemm(MMD_F16, ...): the fp16 vision tower; ring / big kernels only)
-};
-// which kernel the dispatcher chose (mmd_op_gemm_last_plan; parity tests assert the production kernel really ran)
-enum { GEMM_K_TILE64 = 0, GEMM_K_TILE128 = 1, GEMM_K_SKINNY = 2, GEMM_K_GEMV16 = 3, GEMM_K_BIG64 = 4, GEMM_K_BIG128 = 5, GEMM_K_RING256 = 6, GEMM_K_RING128X2 = 7, GEMM_K_STREAM = 8 };
-bool gemm_can_slab(int dtype, const GemmArgs& a);
+// ---- the GEMM family (arguments, epilogues, kernel ids and the dispatch decision: gemm_plan.h) ---------------------------
+GemmPlan gemm_plan_for(int dtype, const GemmArgs& a);          // gemm_plan with the process's GemmTuning: what launch_gemm(dtype, a, ...) would launch
+bool gemm_can_slab(int dtype, const GemmArgs& a);          // would a weight-streaming kernel leave X . W^T as fp32 K slabs in splitk_ws (GemmArgs::slabs_out)?
 bool gemm_ring_auto(int dtype, const GemmArgs& a, bool plain_only = false);          // would the automatic dispatch run this GEMM on gemm_ringx_kernel (plain or split-K; plain_only: not the split-K form)?  (what a piece-major operand needs; a piece-major OUTPUT needs the plain form)
 
 // launchers (dtype = mmd_dtype).  All return hipError_t of the launch.
-hipError_t launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* kind_out);
+hipError_t launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, const GemmPlan* planned = nullptr);          // planned: gemm_plan_for(dtype, a), if the caller already asked (it is evaluated once per GEMM)
 hipError_t launch_pack_w(const void* W, int64_t ldw, int N, int K, void* out, hipStream_t st);   // bf16 only, N%16==0, K%32==0
 // fp8 e4m3 (OCP) weights, one scale per output channel: W [N,K] bf16 row-major is REPLACED by bf16(q) (q = rne_fp8(W / scale), scale = amax / 448),
 // q8_rowmajor [N,K] bytes and scale [N] fp32 are written;  launch_pack_w8 lays q8 out fragment-major for the streaming kernels (N%16==0, K%64==0)

@@ -856,76 +856,34 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_stream_kernel(GemmP p, int 
     });
 }
 
-static inline void set_plan(const GemmArgs& a, int kernel, int tiles, int splits, int blocks) {
-    if (a.plan_out) { a.plan_out[0] = kernel; a.plan_out[1] = tiles; a.plan_out[2] = splits; a.plan_out[3] = blocks; }
+// ---- launchers ---------------------------------------------------------------------------------------------------
+// Each maps a GemmPlan (gemm_plan.h: every split, tile count, grid and instantiation is decided there) to a template instantiation and launches it.
+static void launch_reduce(void (*kernel)(GemmP, int), const GemmP& p, int splits, hipStream_t st) {          // the serial slab reduce (slab 0, 1, 2, ... -- the fused consumers' order) applies the epilogue
+    long long work = (long long)p.M * ((p.N + 3) / 4);
+    hipLaunchKernelGGL(kernel, dim3(cdiv(work, 256)), dim3(256), 0, st, p, splits);
 }
-
-static void launch_gemv16(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    const int KT = a.K >> 5, ntiles = a.N >> 4;
-    int ksplit = 1;
-    if (a.slabs_out && ntiles < 512 && KT >= 256 && a.splitk_ws) {          // long K, few n-tiles (down_proj): 2-4 K slabs
-        ksplit = cdiv(768, ntiles); if (ksplit > 4) ksplit = 4;
-        while (ksplit > 1 && (size_t)ksplit * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --ksplit;
-    }
-    else if (a.slabs_out && ntiles < 512 && a.splitk_ws) {
-        // short K, few n-tiles (qkv, o at decode): one block per n-tile is latency-bound (8.0 / 6.4 us for 33 / 26 MB); two K slabs halve each wave's
-        // dependent load chain: 6.7 / 5.3 us (fp8: 6.0 / 5.2 -> 4.7 / 4.1); the slab consumers sum them for free.  MMDUET_GEMV_KSPLIT_SHORT overrides (1..4)
-        static const int ks_short = getenv("MMDUET_GEMV_KSPLIT_SHORT") ? atoi(getenv("MMDUET_GEMV_KSPLIT_SHORT")) : 2;
-        ksplit = ks_short < 1 ? 1 : (ks_short > 4 ? 4 : ks_short);
-        while (ksplit > 1 && (size_t)ksplit * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --ksplit;
-    }
-    if (a.slabs_out) *a.slabs_out = ksplit;
-    set_plan(a, GEMM_K_GEMV16, ntiles, ksplit, (a.epi == EPI_SWIGLU || (ntiles % 2 == 0 && ntiles >= 2048) ? ntiles / 2 : ntiles) * ksplit);
-    const bool two = a.epi == EPI_SWIGLU || (ntiles % 2 == 0 && ntiles >= 2048);
+static void launch_gemv16(const GemmP& p, const GemmPlan& pl, const GemvChain* chain, hipStream_t st) {
+    const int KT = p.K >> 5;
     const GemvChain none;
-    const bool chain = a.chain && (a.chain->xn_h || a.chain->fin_h);
-    const GemvChain& ch = chain ? *a.chain : none;
-    GemmP q = p; if (a.Wp8) q.W = a.Wp8;
-    if (chain && ch.fin_h) {
+    const GemvChain& ch = pl.chain != GEMV_PLAIN ? *chain : none;
+    const bool w8 = pl.w_from == GEMM_W_PACKED8, two = pl.nt == 2, chained = pl.chain != GEMV_PLAIN;
+    if (pl.chain == GEMV_PRODUCER) {
         // producer: one 16-wave block per n-tile, K split over the waves (no slabs, no second kernel)
-        q.slabs = 0;
-        if (a.slabs_out) *a.slabs_out = 0;
-        set_plan(a, GEMM_K_GEMV16, ntiles, 1, ntiles);
-        if (a.Wp8) hipLaunchKernelGGL((gemm_gemv16_kernel<1, 8, true, true, 16>), dim3(ntiles), dim3(1024), 0, st, q, KT, ch);
-        else hipLaunchKernelGGL((gemm_gemv16_kernel<1, 8, false, true, 16>), dim3(ntiles), dim3(1024), 0, st, q, KT, ch);
+        GemmP q = p; q.slabs = 0;
+        if (w8) hipLaunchKernelGGL((gemm_gemv16_kernel<1, 8, true, true, 16>), dim3(pl.gx), dim3(1024), 0, st, q, KT, ch);
+        else hipLaunchKernelGGL((gemm_gemv16_kernel<1, 8, false, true, 16>), dim3(pl.gx), dim3(1024), 0, st, q, KT, ch);
         return;
     }
-    const dim3 grid(two ? ntiles / 2 : ntiles, ksplit);
-#define GEMV16_GO(NT_, W8_, CH_) hipLaunchKernelGGL((gemm_gemv16_kernel<NT_, 8, W8_, CH_>), grid, dim3(256), 0, st, q, KT, ch)
-    if (a.Wp8) { if (two) { if (chain) GEMV16_GO(2, true, true); else GEMV16_GO(2, true, false); } else { if (chain) GEMV16_GO(1, true, true); else GEMV16_GO(1, true, false); } }
-    else       { if (two) { if (chain) GEMV16_GO(2, false, true); else GEMV16_GO(2, false, false); } else { if (chain) GEMV16_GO(1, false, true); else GEMV16_GO(1, false, false); } }
+    const dim3 grid(pl.gx, pl.splits);
+#define GEMV16_GO(NT_, W8_, CH_) hipLaunchKernelGGL((gemm_gemv16_kernel<NT_, 8, W8_, CH_>), grid, dim3(256), 0, st, p, KT, ch)
+    if (w8) { if (two) { if (chained) GEMV16_GO(2, true, true); else GEMV16_GO(2, true, false); } else { if (chained) GEMV16_GO(1, true, true); else GEMV16_GO(1, true, false); } }
+    else    { if (two) { if (chained) GEMV16_GO(2, false, true); else GEMV16_GO(2, false, false); } else { if (chained) GEMV16_GO(1, false, true); else GEMV16_GO(1, false, false); } }
 #undef GEMV16_GO
 }
 
-// gemm_stream_kernel: 32 < M <= 256, packed bf16 weights, slab output (fused consumers) or the SwiGLU epilogue.  K must be a whole number of steps.
-static bool stream_ok(int dtype, const GemmArgs& a) {
-    if (dtype != MMD_BF16 || a.f16 || !a.Wp || a.M <= 32 || a.M > 256 || (a.N % 16) != 0 || (a.ldx % 8) != 0 || ((uintptr_t)a.X % 16) != 0 || a.out_f32) return false;
-    if (a.Wp8 && a.M <= 64) return false;                                  // fp8 builds keep the 1-byte skinny kernel where it exists
-    if ((long long)a.M * a.ldx * 2 >= (1ll << 32)) return false;            // X addressed as base + 32-bit offset
-    const int ksb = a.M <= 128 ? 4 : 2;          // k-tiles per step of the instantiation that serves this M
-    if ((a.K % (ksb * 32)) != 0) return false;
-    if (a.epi == EPI_SWIGLU) return (a.N % 32) == 0 && !a.slabs_out;
-    if (a.slabs_out) return a.splitk_ws != nullptr && a.epi == EPI_NONE && (size_t)a.M * a.N * sizeof(float) <= a.splitk_ws_bytes;          // (even ONE slab must fit)
-    // epilogue in place (unfused schedule, several streams per forward): the same K split into the workspace, then the serial slab reduce applies bias / residual / activation --
-    // slab for slab what the fused consumers do, so both schedules produce the same bits
-    return a.splitk_ws != nullptr && (a.N % 4) == 0 && (a.ldy % 4) == 0 && (a.epi != EPI_RESID || (a.ldr % 4) == 0);
-}
 template <int MT, int NT, int WK, int KS, int NB, int DBG = 0, int WN = 4>
-static hipError_t launch_stream_t(const GemmP& p, const GemmArgs& a, hipStream_t st, int want_split = 0) {
+static void launch_stream_t(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
     constexpr int KSB = WK * KS;
-    const int KT = a.K >> 5, ntiles = a.N >> 4;
-    const int bx = cdiv(ntiles, WN * NT);
-    int ksplit = 1;
-    if (a.slabs_out || (a.epi != EPI_SWIGLU && a.splitk_ws)) {
-        ksplit = want_split > 0 ? want_split : cdiv(288, bx);                                            // ~ one block per CU and a bit: every CU streams
-        const int maxs = KT / (KSB * 6); if (ksplit > maxs) ksplit = maxs;  // >= 6 steps per block (the pipeline is NB - 1 steps deep)
-        if (ksplit > 16) ksplit = 16; if (ksplit < 1) ksplit = 1;
-        while (ksplit > 1 && (size_t)ksplit * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --ksplit;
-    }
-    const int ktper = (int)round_up(cdiv(KT, ksplit), KSB);
-    ksplit = cdiv(KT, ktper);
-    if (a.slabs_out) *a.slabs_out = ksplit;
-    set_plan(a, GEMM_K_STREAM, ntiles, ksplit, bx * ksplit);
     constexpr size_t ring = (size_t)NB * MT * KSB * 1024, red = (size_t)(WK - 1) * WN * MT * NT * 1024;
     constexpr size_t smem = ring > red ? ring : red;
     static bool attr_set[64] = {};
@@ -934,83 +892,36 @@ static hipError_t launch_stream_t(const GemmP& p, const GemmArgs& a, hipStream_t
         hipFuncSetAttribute((const void*)gemm_stream_kernel<MT, NT, WK, KS, NB, DBG, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         attr_set[adev] = true;
     }
-    hipLaunchKernelGGL((gemm_stream_kernel<MT, NT, WK, KS, NB, DBG, WN>), dim3(bx, ksplit), dim3(64 * WN * WK), smem, st, p, KT, ktper);
-    if (!a.slabs_out && ksplit > 1) {          // epilogue in place: the serial slab reduce (slab 0, 1, 2, ... -- the fused consumers' order)
-        long long work = (long long)a.M * ((a.N + 3) / 4);
-        hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(cdiv(work, 256)), dim3(256), 0, st, p, ksplit);
-    }
-    return hipGetLastError();
-}
-// Decomposition of a streaming GEMM over the 256 CUs.  A CU streams ~25 GB/s whatever runs on it, so the launch is as long as its busiest CU: 296 four-wave blocks
-// (gate_up at WN = 4) take two block rounds for 1.16 rounds of work -- 63 us where 237 five-pair blocks take 46 (tools/bench_gemm.py stream, profiles/r04_stream_sweep.txt).
-// Pick the column-group width WN (n-tile slots per block = waves) and the K split that minimise   rounds x (W bytes + 0.5 X bytes per block) + slab bytes / 256
-// under: whole K steps per block, >= 6 steps per block when K is split (the pipeline is NB - 1 steps deep), slabs within the workspace.
-struct StreamPlan { int wn, ksplit; };
-static StreamPlan stream_plan(const GemmArgs& a, int NT, int MT, int KSB, bool can_split) {
-    const int KT = a.K >> 5, ntiles = a.N >> 4;
-    StreamPlan best{4, 1}; double best_cost = 1e30;
-    for (int wn = 4; wn <= 8; ++wn) {
-        const int bx = cdiv(ntiles, wn * NT);
-        for (int ks = 1; ks <= (can_split ? 16 : 1); ++ks) {
-            const int ktper = (int)round_up(cdiv(KT, ks), KSB);
-            if (cdiv(KT, ktper) != ks) continue;                                            // (this split count rounds to another one)
-            if (ks > 1 && ktper < 6 * KSB) break;
-            if (ks > 1 && (size_t)ks * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) break;
-            const int rounds = cdiv((long long)bx * ks, 256);
-            const double wb = (double)wn * NT * ktper * 1024, xb = (double)MT * 16 * ktper * 64;
-            const double slab = can_split ? (double)ks * a.M * a.N * 8.0 / 256.0 : 0.0;
-            const double cost = rounds * (wb + 0.5 * xb) + slab;
-            if (cost < best_cost * 0.999) { best_cost = cost; best = StreamPlan{wn, ks}; }
-        }
-    }
-    return best;
+    hipLaunchKernelGGL((gemm_stream_kernel<MT, NT, WK, KS, NB, DBG, WN>), dim3(pl.gx, pl.splits), dim3(64 * WN * WK), smem, st, p, p.K >> 5, pl.kt_per_block);
+    if (pl.reduce) launch_reduce(splitk_reduce_kernel<bf16_t>, p, pl.splits, st);
 }
 template <int MT, int NT, int WK, int KS, int NB>
-static hipError_t launch_stream_wn(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    const StreamPlan pl = stream_plan(a, NT, MT, WK * KS, a.slabs_out != nullptr || (a.epi != EPI_SWIGLU && a.splitk_ws != nullptr));
+static void launch_stream_wn(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
     switch (pl.wn) {
-        case 5: return launch_stream_t<MT, NT, WK, KS, NB, 0, 5>(p, a, st, pl.ksplit);
-        case 6: return launch_stream_t<MT, NT, WK, KS, NB, 0, 6>(p, a, st, pl.ksplit);
-        case 7: return launch_stream_t<MT, NT, WK, KS, NB, 0, 7>(p, a, st, pl.ksplit);
-        case 8: return launch_stream_t<MT, NT, WK, KS, NB, 0, 8>(p, a, st, pl.ksplit);
-        default: return launch_stream_t<MT, NT, WK, KS, NB, 0, 4>(p, a, st, pl.ksplit);
+        case 5: return launch_stream_t<MT, NT, WK, KS, NB, 0, 5>(p, pl, st);
+        case 6: return launch_stream_t<MT, NT, WK, KS, NB, 0, 6>(p, pl, st);
+        case 7: return launch_stream_t<MT, NT, WK, KS, NB, 0, 7>(p, pl, st);
+        case 8: return launch_stream_t<MT, NT, WK, KS, NB, 0, 8>(p, pl, st);
+        default: return launch_stream_t<MT, NT, WK, KS, NB, 0, 4>(p, pl, st);
     }
 }
-static hipError_t launch_stream(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    const bool two = a.epi == EPI_SWIGLU || (a.N >> 4) >= 4096;
-    if (a.M <= 64) return two ? launch_stream_wn<4, 2, 1, 4, 3>(p, a, st) : launch_stream_wn<4, 1, 1, 4, 3>(p, a, st);
-    if (a.M <= 128) return two ? launch_stream_wn<8, 2, 1, 2, 4>(p, a, st) : launch_stream_wn<8, 1, 1, 4, 3>(p, a, st);
-    return two ? launch_stream_wn<16, 2, 1, 1, 4>(p, a, st) : launch_stream_wn<16, 1, 1, 2, 4>(p, a, st);
+static void launch_stream(const GemmP& p, const GemmPlan& pl, hipStream_t st) {          // (MT, NT) -> the steps WK x KS (plan_stream's KSB) and the ring depth NB of the instantiation
+    const bool two = pl.nt == 2;
+    if (pl.mt == 4) return two ? launch_stream_wn<4, 2, 1, 4, 3>(p, pl, st) : launch_stream_wn<4, 1, 1, 4, 3>(p, pl, st);
+    if (pl.mt == 8) return two ? launch_stream_wn<8, 2, 1, 2, 4>(p, pl, st) : launch_stream_wn<8, 1, 1, 4, 3>(p, pl, st);
+    return two ? launch_stream_wn<16, 2, 1, 1, 4>(p, pl, st) : launch_stream_wn<16, 1, 1, 2, 4>(p, pl, st);
 }
 
 template <int MT>
-static void launch_skinny_mt(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    const int KT = a.K >> 5, ntiles = a.N >> 4;
-    const int NT = (a.epi == EPI_SWIGLU || ntiles >= 4096) ? 2 : 1;
-    int nblocks = cdiv(ntiles, 4 * NT);
-    int splits = 1;
-    if (nblocks < 512 && a.epi != EPI_SWIGLU && a.splitk_ws) {
-        splits = cdiv(512, nblocks);
-        int maxs = KT / 16; if (maxs < 1) maxs = 1;              // >= 512 k per split
-        if (splits > maxs) splits = maxs;
-        if (splits > 8) splits = 8;
-        while (splits > 1 && (size_t)splits * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --splits;
-    }
-    int ktper = (int)round_up(cdiv(KT, splits), 4);
-    splits = cdiv(KT, ktper);
-    dim3 grid(nblocks, splits);
-    set_plan(a, GEMM_K_SKINNY, ntiles, splits, nblocks * splits);
-    if (a.Wp8) {
-        GemmP q = p; q.W = a.Wp8;
-        if (NT == 2) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2, true>), grid, dim3(256), 0, st, q, KT, ktper);
-        else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 1, true>), grid, dim3(256), 0, st, q, KT, ktper);
-    } else if (NT == 2) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2>), grid, dim3(256), 0, st, p, KT, ktper);
-    else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 1>), grid, dim3(256), 0, st, p, KT, ktper);
-    if (a.slabs_out) { *a.slabs_out = splits; return; }
-    if (splits > 1) {
-        long long work = (long long)a.M * ((a.N + 3) / 4);
-        hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(cdiv(work, 256)), dim3(256), 0, st, p, splits);
-    }
+static void launch_skinny_mt(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+    const int KT = p.K >> 5;
+    const dim3 grid(pl.gx, pl.splits);
+    if (pl.w_from == GEMM_W_PACKED8) {
+        if (pl.nt == 2) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2, true>), grid, dim3(256), 0, st, p, KT, pl.kt_per_block);
+        else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 1, true>), grid, dim3(256), 0, st, p, KT, pl.kt_per_block);
+    } else if (pl.nt == 2) hipLaunchKernelGGL((gemm_skinny_kernel<MT, 2>), grid, dim3(256), 0, st, p, KT, pl.kt_per_block);
+    else hipLaunchKernelGGL((gemm_skinny_kernel<MT, 1>), grid, dim3(256), 0, st, p, KT, pl.kt_per_block);
+    if (pl.reduce) launch_reduce(splitk_reduce_kernel<bf16_t>, p, pl.splits, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1167,61 +1078,33 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(GemmP p, int KT) {
     }
 }
 
-// 160-row tiles of the 64-column form (plain / residual epilogue, bf16: a chunk's qkv / o_proj): when they take fewer block rounds per CU.  A CU holds three 128 x 64 blocks
-// (48 KB of LDS each) or two 160 x 64 ones (56 KB); a CU's time ~ blocks it runs x rows per block.
-static bool big_bm160(const GemmArgs& a, int BN) {
-    if (BN != 64 || a.f16 || (a.epi != EPI_NONE && a.epi != EPI_RESID) || a.M < 512) return false;
-    const long long t128 = (long long)(a.N / 64) * cdiv(a.M, 128), t160 = (long long)(a.N / 64) * cdiv(a.M, 160);
-    if (t160 > 512) return false;                                          // (a third block per CU would have to wait for a slot)
-    return (double)cdiv(t160, 256) * 160.0 < (double)cdiv(t128, 256) * 128.0 * 0.97;
-}
 template <int BN>
-static void launch_big(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    if (big_bm160(a, BN)) {
+static void launch_big(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+    const int KT = p.K >> 5;
+    const dim3 grid(pl.gx, pl.gy, pl.splits);
+    if (pl.bm == 160) {
         if constexpr (BN == 64) {
-            const int tiles = (a.N / 64) * cdiv(a.M, 160);
-            set_plan(a, GEMM_K_BIG64, tiles, 1, tiles);
-            const dim3 grid(a.N / 64, cdiv(a.M, 160), 1);
-            if (a.epi == EPI_RESID) hipLaunchKernelGGL((gemm_big_kernel<64, EPI_RESID, false, 160>), grid, dim3(256), 0, st, p, a.K >> 5);
-            else hipLaunchKernelGGL((gemm_big_kernel<64, EPI_NONE, false, 160>), grid, dim3(256), 0, st, p, a.K >> 5);
-            return;
+            if (p.epi == EPI_RESID) hipLaunchKernelGGL((gemm_big_kernel<64, EPI_RESID, false, 160>), grid, dim3(256), 0, st, p, KT);
+            else hipLaunchKernelGGL((gemm_big_kernel<64, EPI_NONE, false, 160>), grid, dim3(256), 0, st, p, KT);
         }
+        return;
     }
-    const int tiles = (a.N / BN) * cdiv(a.M, 128);
-    int splits = 1;
-    if (tiles < 320 && a.K >= 8192 && a.epi != EPI_SWIGLU && a.splitk_ws && !a.f16) {      // long K, under one block per CU (down_proj): split K
-        splits = 3;                                                                // (measured: splitting K = 3584 GEMMs costs more than it fills)
-        if (tiles <= 64) splits = 4;
-        while (splits > 1 && (size_t)splits * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --splits;
-    } else if (tiles < 128 && a.K >= 2048 && a.epi != EPI_SWIGLU && a.splitk_ws && !a.f16) {
-        // a handful of rows (65 <= M <= ~256: a few frames per forward, several streams' decode rows): 56-72 tiles cannot pull the weights out of HBM (a CU streams ~25 GB/s);
-        // split K so that ~one block per CU streams.  round 3, 15 k context: an M = 98 step 8.5 -> see profiles/r03_decode_experiments.md
-        splits = 256 / tiles; if (splits > 4) splits = 4; if (splits < 1) splits = 1;
-        while (splits > 1 && (size_t)splits * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --splits;
-    }
-    dim3 grid(a.N / BN, cdiv(a.M, 128), splits);
-    set_plan(a, BN == 128 ? GEMM_K_BIG128 : GEMM_K_BIG64, tiles, splits, tiles * splits);
-    const int KT = a.K >> 5;
-    if (a.f16) {          // the fp16 vision tower: plain / GELU(tanh) / residual epilogues
-        switch (a.epi) {
+    if (pl.f16) {          // the fp16 vision tower: plain / GELU(tanh) / residual epilogues
+        switch (p.epi) {
             case EPI_GELU_TANH: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_GELU_TANH, true>), grid, dim3(256), 0, st, p, KT); break;
             case EPI_RESID: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_RESID, true>), grid, dim3(256), 0, st, p, KT); break;
             default: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_NONE, true>), grid, dim3(256), 0, st, p, KT); break;
         }
         return;
     }
-    switch (a.epi) {
+    switch (p.epi) {
         case EPI_GELU_TANH: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_GELU_TANH>), grid, dim3(256), 0, st, p, KT); break;
         case EPI_GELU_ERF: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_GELU_ERF>), grid, dim3(256), 0, st, p, KT); break;
         case EPI_RESID: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_RESID>), grid, dim3(256), 0, st, p, KT); break;
         case EPI_SWIGLU: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_SWIGLU>), grid, dim3(256), 0, st, p, KT); break;
         default: hipLaunchKernelGGL((gemm_big_kernel<BN, EPI_NONE>), grid, dim3(256), 0, st, p, KT); break;
     }
-    if (splits > 1) {
-        if (a.ring_slabs_out) { *a.ring_slabs_out = splits; return; }          // the caller folds the slabs itself (reduce + residual + RMSNorm in one pass)
-        long long work = (long long)a.M * ((a.N + 3) / 4);
-        hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(cdiv(work, 256)), dim3(256), 0, st, p, splits);
-    }
+    if (pl.reduce) launch_reduce(splitk_reduce_kernel<bf16_t>, p, pl.splits, st);
 }
 
 
@@ -1235,18 +1118,10 @@ static void* ring_dump_slot() {
 }
 
 template <int WN, bool M32, int NS, bool EARLY, bool F16 = false>
-static hipError_t launch_ringx_t(const GemmP& p, const GemmArgs& a, hipStream_t st, int splits, bool stagger = true) {
-    if (F16) splits = 1;
-    while (splits > 1 && (a.epi == EPI_SWIGLU || !a.splitk_ws || (size_t)splits * a.M * a.N * sizeof(float) > a.splitk_ws_bytes)) --splits;
+static hipError_t launch_ringx_t(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
     constexpr int BN = 64 * WN;
-    const int tiles = cdiv(a.N, BN) * cdiv(a.M, 256);
-    const int slots = (WN == 2 && NS == 3) ? 512 : 256;                      // resident blocks: two 4-wave blocks per CU (72 KB rings), else one
-    // ring_max_blocks: > 0 caps the persistent grid (tower share); < 0 (the overlap experiments of round 4, tools/probes/dropped/overlap_sweep.sh): NON-persistent, one tile per block, so that the
-    // dispatcher can place another stream's blocks at every tile end
-    const int cap = a.ring_max_blocks < 0 ? tiles : (a.ring_max_blocks > 0 && a.ring_max_blocks < slots ? a.ring_max_blocks : slots);
-    dim3 grid(splits > 1 || tiles <= cap ? tiles : cap, 1, splits);
-    set_plan(a, WN == 2 ? GEMM_K_RING128X2 : GEMM_K_RING256, tiles, splits, (int)grid.x * splits);
-    const int KT = a.K >> 5;
+    const dim3 grid(pl.gx, 1, pl.splits);
+    const int KT = p.K >> 5;
     const size_t smem = NS * (256 * 32 + BN * 32) * sizeof(bf16_t);          // 96 KB / 72 KB (3 slots), 128 KB / 96 KB (4)
     static bool attr_set[64] = {};          // per device (hipFuncSetAttribute applies to the current device's code object)
     int adev = 0; hipGetDevice(&adev);
@@ -1261,285 +1136,130 @@ static hipError_t launch_ringx_t(const GemmP& p, const GemmArgs& a, hipStream_t 
     GemmP q = p;
     q.dump = ring_dump_slot();
     if (!q.dump) return hipErrorOutOfMemory;
-    // start-up stagger of the second-slot blocks in ~4 us units: about half a tile (K/32 steps of ~0.75 us) -- see the kernel
-    q.kper = (!stagger || splits > 1) ? 0 : ((a.K / 32) * 10) / 100 + 1;
-    if constexpr (F16) {
-        switch (a.epi) {
-            case EPI_GELU_TANH: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_GELU_TANH, WN, M32, NS, EARLY, 0, true>), grid, block, smem, st, q, KT); break;
-            case EPI_RESID: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_RESID, WN, M32, NS, EARLY, 0, true>), grid, block, smem, st, q, KT); break;
-            case EPI_NONE: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_NONE, WN, M32, NS, EARLY, 0, true>), grid, block, smem, st, q, KT); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else
-    switch (a.epi) {
-        case EPI_GELU_TANH: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_GELU_TANH, WN, M32, NS, EARLY>), grid, block, smem, st, q, KT); break;
-        case EPI_GELU_ERF: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_GELU_ERF, WN, M32, NS, EARLY>), grid, block, smem, st, q, KT); break;
-        case EPI_RESID: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_RESID, WN, M32, NS, EARLY>), grid, block, smem, st, q, KT); break;
-        case EPI_SWIGLU: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_SWIGLU, WN, M32, NS, EARLY>), grid, block, smem, st, q, KT); break;
-        default: hipLaunchKernelGGL((gemm_ringx_kernel<EPI_NONE, WN, M32, NS, EARLY>), grid, block, smem, st, q, KT); break;
+#define RX_GO(E) hipLaunchKernelGGL((gemm_ringx_kernel<E, WN, M32, NS, EARLY, 0, F16>), grid, block, smem, st, q, KT)
+    switch (p.epi) {          // (the IEEE-half form has the plain / GELU(tanh) / residual epilogues: the plan holds no other for it)
+        case EPI_GELU_TANH: RX_GO(EPI_GELU_TANH); break;
+        case EPI_GELU_ERF: if constexpr (!F16) RX_GO(EPI_GELU_ERF); break;
+        case EPI_RESID: RX_GO(EPI_RESID); break;
+        case EPI_SWIGLU: if constexpr (!F16) RX_GO(EPI_SWIGLU); break;
+        default: RX_GO(EPI_NONE); break;
     }
-    if (splits > 1) {
-        if (a.ring_slabs_out) { *a.ring_slabs_out = splits; return hipGetLastError(); }
-        long long work = (long long)a.M * ((a.N + 3) / 4);
-        hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(cdiv(work, 256)), dim3(256), 0, st, p, splits);
-    }
+#undef RX_GO
+    if (pl.reduce) launch_reduce(splitk_reduce_kernel<bf16_t>, p, pl.splits, st);
+    return hipSuccess;
+}
+// the instantiations of gemm_ringx_kernel in the library (plan_ring, gemm_plan.h, says what they are for and rejects the flags of the others)
+static hipError_t launch_ringx(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
+    if (pl.f16) return launch_ringx_t<4, false, 3, true, true>(p, pl, st);
+    return pl.wn == 4 ? launch_ringx_t<4, false, 3, true>(p, pl, st) : launch_ringx_t<2, false, 3, true>(p, pl, st);
+}
+
+static inline void set_plan(const GemmArgs& a, const GemmPlan& pl) {
+    if (a.plan_out) { a.plan_out[0] = pl.kernel; a.plan_out[1] = pl.tiles; a.plan_out[2] = pl.splits; a.plan_out[3] = pl.blocks; }
+}
+
+#ifdef MMDUET_DEBUG_VARIANTS
+// Timing experiments of tools/bench_gemm.py (`make DEBUG_VARIANTS=1`; never in the library otherwise; most give WRONG results): variants 92-99 run gemm_ringx_kernel's DBG
+// modes, 300-339 sweep configurations of gemm_stream_kernel at M <= 64.  -> true: the variant was one of these and *err is its launch's result.
+template <int DBG, int NS = 3>
+static hipError_t launch_ringx_dbg(const GemmP& p, const GemmArgs& a, hipStream_t st) {
+    GemmPlan pl;
+    pl.kernel = GEMM_K_RING256; pl.tiles = cdiv(a.N, 256) * cdiv(a.M, 256); pl.blocks = pl.tiles <= 256 ? pl.tiles : 256;
+    set_plan(a, pl);
+    const size_t smem = NS * (256 * 32 + 256 * 32) * sizeof(bf16_t);
+    hipFuncSetAttribute((const void*)gemm_ringx_kernel<EPI_NONE, 4, false, NS, true, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL((gemm_ringx_kernel<EPI_NONE, 4, false, NS, true, DBG>), dim3(pl.blocks), dim3(512), smem, st, p, a.K >> 5);
     return hipGetLastError();
 }
-#ifdef MMDUET_DEBUG_VARIANTS
-template <int DBG>
-static hipError_t launch_ringx_dbg(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    const int tiles = cdiv(a.N, 256) * cdiv(a.M, 256);
-    dim3 grid(tiles <= 256 ? tiles : 256, 1, 1);
-    set_plan(a, GEMM_K_RING256, tiles, 1, (int)grid.x);
-    const size_t smem = 3 * (256 * 32 + 256 * 32) * sizeof(bf16_t);
-    hipFuncSetAttribute((const void*)gemm_ringx_kernel<EPI_NONE, 4, false, 3, true, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL((gemm_ringx_kernel<EPI_NONE, 4, false, 3, true, DBG>), grid, dim3(512), smem, st, p, a.K >> 5);
-    return hipGetLastError();
+static bool launch_debug_variant(GemmP p, const GemmArgs& a, hipStream_t st, hipError_t* err) {
+    const int variant = a.variant;
+    p.W = a.Wp;
+    if (variant >= 92 && variant <= 99) {
+        if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) { *err = hipErrorInvalidValue; return true; }
+        switch (variant) {
+            case 92: *err = launch_ringx_dbg<8, 4>(p, a, st); break;          // DBG 8 on the 4-slot ring
+            case 93: *err = launch_ringx_dbg<7>(p, a, st); break;
+            case 94: *err = launch_ringx_dbg<6>(p, a, st); break;
+            case 95: *err = launch_ringx_dbg<5>(p, a, st); break;
+            case 99: *err = launch_ringx_dbg<4>(p, a, st); break;
+            case 96: *err = launch_ringx_dbg<1>(p, a, st); break;
+            case 97: *err = launch_ringx_dbg<2>(p, a, st); break;
+            default: *err = launch_ringx_dbg<3>(p, a, st); break;
+        }
+        return true;
+    }
+    if (variant >= 300 && variant < 340 && a.M <= 64 && a.Wp) {
+        p.slabs = a.epi == EPI_SWIGLU ? 0 : 1;
+        GemmArgs b = a; int dummy = 0; if (a.epi != EPI_SWIGLU) { b.slabs_out = &dummy; b.epi = EPI_NONE; p.epi = EPI_NONE; }
+        const bool two = a.epi == EPI_SWIGLU;
+        GemmPlan pl;
+#define SGO(NT_, WK_, KS_, NB_, DBG_, WN_, SPLIT_) (stream_geometry(pl, b, 4, NT_, WK_ * KS_, WN_, SPLIT_), set_plan(a, pl), launch_stream_t<4, NT_, WK_, KS_, NB_, DBG_, WN_>(p, pl, st))
+#define SCFG(id, WK_, KS_, NB_, DBG_) case id: if (two) SGO(2, WK_, KS_, NB_, DBG_, 4, 0); else SGO(1, WK_, KS_, NB_, DBG_, 4, 0); break;
+        switch (variant - 300) {
+            SCFG(0, 2, 2, 4, 0) SCFG(1, 1, 4, 3, 0) SCFG(2, 4, 1, 4, 0) SCFG(3, 2, 4, 3, 0) SCFG(4, 1, 4, 4, 0) SCFG(5, 4, 2, 3, 0) SCFG(7, 2, 2, 6, 0)
+            SCFG(10, 2, 2, 4, 1) SCFG(11, 1, 4, 3, 1) SCFG(12, 2, 2, 4, 2) SCFG(13, 1, 4, 3, 2)
+            // balanced decompositions: 5 pairs per block (gate_up: 237 blocks), 7 n-tiles x 8 K chunks (down / o: 256 blocks)
+            case 20: if (two) SGO(2, 2, 2, 4, 0, 5, 0); else SGO(1, 2, 2, 4, 0, 7, 8); break;
+            case 21: if (two) SGO(2, 3, 2, 3, 0, 5, 0); else SGO(1, 2, 2, 4, 0, 7, 4); break;
+            case 22: if (two) SGO(2, 2, 2, 4, 1, 5, 0); else SGO(1, 2, 2, 4, 1, 7, 8); break;
+            case 23: if (two) SGO(2, 1, 4, 3, 0, 5, 0); else SGO(1, 1, 4, 3, 0, 7, 8); break;
+            case 24: if (two) SGO(2, 2, 2, 4, 0, 8, 0); else SGO(1, 2, 2, 4, 0, 7, 16); break;
+            default: *err = hipErrorInvalidValue; return true;
+        }
+#undef SCFG
+#undef SGO
+        *err = hipGetLastError();
+        return true;
+    }
+    return false;
 }
 #endif
-// flags: 16 = 8 waves, 256 x 256 tiles, three-slot ring, refill DMAs in the first rows of a step (every tower / projector GEMM, gate_up and split-K down of a chunk);
-//        17 = 4 waves, 256 x 128 tiles, two blocks per CU (a chunk's qkv / o_proj where 256 x 256 tiles cannot fill the chip).  The other instantiations the template was
-//        built to test (late refill, 32x32x16 MFMA, four slots) lost their A/B (header of gemm_ringx_kernel) and are no longer compiled into the library.
-static hipError_t launch_ringx(int flags, const GemmP& p, const GemmArgs& a, hipStream_t st, int splits = 1) {
-    if (a.f16) return launch_ringx_t<4, false, 3, true, true>(p, a, st, 1);          // the fp16 tower runs the shipped instantiation
-    switch (flags & 27) {
-        case 16: return launch_ringx_t<4, false, 3, true>(p, a, st, splits);
-        case 17: return launch_ringx_t<2, false, 3, true>(p, a, st, splits);
-        default: return hipErrorInvalidValue;
+
+template <typename T>
+static hipError_t launch_t(const GemmArgs& a, const GemmPlan& pl, hipStream_t st) {
+    GemmP p;
+    p.X = a.X; p.W = pl.w_from == GEMM_W_PACKED8 ? a.Wp8 : (pl.w_from == GEMM_W_PACKED ? a.Wp : a.W); p.bias = a.bias; p.R = a.R; p.Y = a.Y; p.ws = a.splitk_ws; p.wscale = a.wscale;
+    p.ldx = a.ldx; p.ldw = a.ldw; p.ldr = a.ldr; p.ldy = a.ldy;
+    p.M = a.M; p.N = a.N; p.K = a.K; p.epi = a.epi; p.out_f32 = a.out_f32; p.slabs = a.slabs_out ? 1 : 0; p.dump = nullptr; p.flags = 0; p.kper = pl.kper; p.x_pm = a.x_pm; p.y_pm = a.y_pm;
+    p.vec = (sizeof(T) == 2 && (a.ldx % 8) == 0 && (a.ldw % 8) == 0 && ((uintptr_t)a.X % 16) == 0 && ((uintptr_t)a.W % 16) == 0) ? 1 : 0;
+    if (a.ring_slabs_out) *a.ring_slabs_out = pl.ring_slabs;
+    if (pl.kernel == GEMM_PLAN_EMPTY) return hipSuccess;
+#ifdef MMDUET_DEBUG_VARIANTS
+    if (hipError_t e = hipSuccess; sizeof(T) == 2 && launch_debug_variant(p, a, st, &e)) return e;
+#endif
+    if (!pl.valid()) return hipErrorInvalidValue;
+    if (a.slabs_out && (pl.kernel == GEMM_K_GEMV16 || pl.kernel == GEMM_K_SKINNY || pl.kernel == GEMM_K_STREAM)) *a.slabs_out = pl.slabs;
+    set_plan(a, pl);
+    switch (pl.kernel) {
+        case GEMM_K_GEMV16: launch_gemv16(p, pl, a.chain, st); break;
+        case GEMM_K_STREAM: launch_stream(p, pl, st); break;
+        case GEMM_K_RING256: case GEMM_K_RING128X2: if (hipError_t e = launch_ringx(p, pl, st); e != hipSuccess) return e; break;
+        case GEMM_K_BIG128: launch_big<128>(p, pl, st); break;
+        case GEMM_K_BIG64: launch_big<64>(p, pl, st); break;
+        case GEMM_K_SKINNY: if (pl.mt == 1) launch_skinny_mt<1>(p, pl, st); else if (pl.mt == 2) launch_skinny_mt<2>(p, pl, st); else launch_skinny_mt<4>(p, pl, st); break;
+        case GEMM_K_TILE128: hipLaunchKernelGGL((gemm_tile_kernel<T, 128, 128>), dim3(pl.gx, pl.gy, 1), dim3(256), 0, st, p); break;
+        default:          // GEMM_K_TILE64
+            hipLaunchKernelGGL((gemm_tile_kernel<T, 64, 64>), dim3(pl.gx, pl.gy, pl.splits), dim3(256), 0, st, p);
+            if (pl.reduce) launch_reduce(splitk_reduce_kernel<T>, p, pl.splits, st);
     }
+    return hipGetLastError();
 }
 
-
-// the ring GEMM addresses its operands as uniform base + 32-bit byte offset
-static bool ring_size_ok(const GemmArgs& a) { return (long long)a.M * a.ldx * 2 < (1ll << 32) && (long long)a.N * a.K * 2 < (1ll << 32); }
-// enough 256^2 tiles for the persistent ring: >= 400 (1.6 block waves of the 256 CUs), or close to whole waves from 0.75 of one up (4096^2: 256 tiles = one
-// wave, 1.36 PF against 0.94 for the 128-row kernel; 300 tiles would leave the second wave at 17 % and stay with the 128-row kernel)
-static bool ring_tiles_ok(long long t) { return t >= 400 || (t >= 192 && (double)t / (double)(cdiv((int)t, 256) * 256) >= 0.9); }
-static bool big_packed_ok(int dtype, const GemmArgs& a, int BN) {
-    return dtype == MMD_BF16 && a.Wp != nullptr && a.M > 64 && (a.N % BN) == 0 && (a.K % 64) == 0 && (a.ldx % 8) == 0 &&
-           ((uintptr_t)a.X % 16) == 0 && !a.out_f32 && (a.ldy % 4) == 0 && ((uintptr_t)a.Y % 8) == 0 &&
-           (a.epi != EPI_RESID || ((a.ldr % 4) == 0 && ((uintptr_t)a.R % 8) == 0)) && (a.bias == nullptr || ((uintptr_t)a.bias % 8) == 0);
+// the process's GemmTuning: read from the environment once
+GemmPlan gemm_plan_for(int dtype, const GemmArgs& a) {
+    static const GemmTuning tune = [] { GemmTuning t; if (const char* s = getenv("MMDUET_GEMV_KSPLIT_SHORT")) t.gemv_ksplit_short = atoi(s); return t; }();
+    return gemm_plan(dtype, a, tune);
 }
-
-// packed-W skinny path usable?  bf16, M <= 64, N % 16 == 0, K % 32 == 0, 16-byte aligned rows of X
-static bool skinny_packed_ok(int dtype, const GemmArgs& a) {
-    return dtype == MMD_BF16 && a.Wp != nullptr && a.M <= 64 && (a.N % 16) == 0 && (a.K % 32) == 0 && (a.ldx % 8) == 0 &&
-           ((uintptr_t)a.X % 16) == 0 && (a.epi != EPI_SWIGLU || (a.N % 32) == 0);
-}
-
-// the two automatic ring conditions of launch_t (kept in one place: the model asks before it lays an activation out piece-major)
-static bool ring256_auto(const GemmArgs& a) {
-    return a.M >= 512 && (a.N % 32) == 0 && big_packed_ok(MMD_BF16, a, 16) && ring_size_ok(a) && ring_tiles_ok((long long)cdiv(a.M, 256) * cdiv(a.N, 256));
-}
-// K splits of the split-K ring for t256 output tiles.  Up to half a block wave of tiles: as many splits as fit one wave (down_proj of a chunk: 70 tiles x 3).  Between half a
-// wave and the plain ring's threshold (down_proj of several streams' merged chunks: M = 2548 -> 140 tiles, which left 116 CUs idle for the whole K on the plain ring and ran at
-// 0.28 of peak on the 128-row kernel) the split count comes from a small cost model: rounds of 256 blocks x K / sp steps of ~25 ns per unit of K, plus the fp32 slabs' write + read
-// at ~5 TB/s (140 tiles: 3 splits = 420 items in two rounds of K / 3 -- two thirds of the unsplit time).
-static int ring_split_choice(const GemmArgs& a) {
-    const int t256 = cdiv(a.M, 256) * cdiv(a.N, 256);
-    int sp = 256 / t256; if (sp < 1) sp = 1;
-    if (t256 > 128) {
-        double best = 1e30; int bsp = 1;
-        for (int s = 1; s <= 8; ++s) {
-            if (s > 1 && (a.K / s < 1024 || (size_t)s * a.M * a.N * sizeof(float) > a.splitk_ws_bytes)) break;
-            const double rounds = (double)cdiv(t256 * s, 256);
-            const double cost = rounds * ((double)a.K / s) * 0.025 + (s > 1 ? (double)s * a.M * a.N * 8.0 / 5e6 : 0.0);
-            if (cost < best * 0.97) { best = cost; bsp = s; }          // (a finer split has to buy 3 %)
-        }
-        return bsp;
-    }
-    while (sp > 1 && a.K / sp < 1024) --sp;
-    while (sp > 1 && (size_t)sp * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --sp;
-    return sp;
-}
-static bool ring256_split_auto(const GemmArgs& a) {
-    if (a.f16 || !(a.M >= 512 && a.K >= 8192 && big_packed_ok(MMD_BF16, a, 16) && (a.N % 32) == 0 && a.epi != EPI_SWIGLU && a.splitk_ws != nullptr && ring_size_ok(a))) return false;
-    return ring_split_choice(a) >= 2;
+bool gemm_can_slab(int dtype, const GemmArgs& a) {
+    int dummy = 0; GemmArgs b = a; b.slabs_out = &dummy; b.epi = EPI_NONE;
+    const int k = gemm_plan_for(dtype, b).kernel;
+    return k == GEMM_K_GEMV16 || k == GEMM_K_SKINNY || k == GEMM_K_STREAM;          // (64 < M <= 256: gemm_stream_kernel leaves slabs too)
 }
 bool gemm_ring_auto(int dtype, const GemmArgs& a, bool plain_only) {
-    if (dtype != MMD_BF16 && dtype != MMD_F16) return false;
-    GemmArgs b = a; b.f16 = dtype == MMD_F16;
-    if (b.variant != GEMM_AUTO || b.wscale) return false;
-    return ring256_auto(b) || (!plain_only && ring256_split_auto(b));
+    const int ring = gemm_plan_for(dtype, a).ring_auto;
+    return !a.wscale && (plain_only ? ring == RING_AUTO_PLAIN : ring != RING_AUTO_NONE);
 }
-template <typename T>
-static hipError_t launch_t(const GemmArgs& a, hipStream_t st, int* kind_out) {
-    GemmP p;
-    p.X = a.X; p.W = a.W; p.bias = a.bias; p.R = a.R; p.Y = a.Y; p.ws = a.splitk_ws; p.wscale = a.wscale;
-    p.ldx = a.ldx; p.ldw = a.ldw; p.ldr = a.ldr; p.ldy = a.ldy;
-    p.M = a.M; p.N = a.N; p.K = a.K; p.epi = a.epi; p.out_f32 = a.out_f32; p.slabs = a.slabs_out ? 1 : 0; p.dump = nullptr; p.flags = 0; p.kper = 0; p.x_pm = a.x_pm; p.y_pm = a.y_pm;
-    p.vec = (sizeof(T) == 2 && (a.ldx % 8) == 0 && (a.ldw % 8) == 0 && ((uintptr_t)a.X % 16) == 0 && ((uintptr_t)a.W % 16) == 0) ? 1 : 0;
-    if (a.ring_slabs_out) *a.ring_slabs_out = 0;
-    if (a.M <= 0 || a.N <= 0) return hipSuccess;
-    int variant = a.variant;
-    bool skinny = (variant == GEMM_SKINNY) || (variant == GEMM_AUTO && a.M <= 64);
-    bool large = (variant == GEMM_LARGE) || (variant == GEMM_AUTO && a.M >= 256 && a.N >= 128);
-    if (kind_out) *kind_out = skinny ? MMD_K_GEMM_SKINNY : MMD_K_GEMM_TILE;
-    if ((a.x_pm || a.y_pm) && (sizeof(T) != 2 || variant != GEMM_AUTO || !(ring256_auto(a) || ring256_split_auto(a)) || a.wscale ||
-                               (a.x_pm && (a.K % 32)) || (a.y_pm && ((a.epi == EPI_SWIGLU ? a.N / 2 : a.N) % 32))))
-        return hipErrorInvalidValue;          // a piece-major operand exists for the ring kernel only (the caller asks gemm_ring_auto first)
-    if (a.y_pm && !ring256_auto(a)) return hipErrorInvalidValue;          // ... and a piece-major OUTPUT for its plain form only: the split-K form leaves fp32 slabs and splitk_reduce writes Y row-major
-    if constexpr (sizeof(T) == 2) {
-        // the weight-streaming regime above the GEMV's 16 rows: per-frame steps, short chunks (gemm_stream_kernel); slab consumers or the SwiGLU epilogue
-        if ((variant == GEMM_AUTO || variant == GEMM_SKINNY || variant == GEMM_STREAM) && stream_ok(MMD_BF16, a)) {
-            p.W = a.Wp;
-            if (kind_out) *kind_out = MMD_K_GEMM_SKINNY;
-            return launch_stream(p, a, st);
-        }
-        if (variant == GEMM_STREAM) return hipErrorInvalidValue;
-#ifdef MMDUET_DEBUG_VARIANTS          // tools/bench_gemm.py stream: configuration sweep of gemm_stream_kernel at M <= 64 (`make DEBUG_VARIANTS=1`; never in the shipped library)
-        if (variant >= 300 && variant < 340 && a.M <= 64 && a.Wp) {
-            p.W = a.Wp; p.slabs = a.epi == EPI_SWIGLU ? 0 : 1;
-            GemmArgs b = a; int dummy = 0; if (a.epi != EPI_SWIGLU) { b.slabs_out = &dummy; b.epi = EPI_NONE; p.epi = EPI_NONE; }
-            const bool two = a.epi == EPI_SWIGLU;
-#define SCFG(id, WK_, KS_, NB_, DBG_) case id: return two ? launch_stream_t<4, 2, WK_, KS_, NB_, DBG_>(p, b, st) : launch_stream_t<4, 1, WK_, KS_, NB_, DBG_>(p, b, st);
-            switch (variant - 300) {
-                SCFG(0, 2, 2, 4, 0) SCFG(1, 1, 4, 3, 0) SCFG(2, 4, 1, 4, 0) SCFG(3, 2, 4, 3, 0) SCFG(4, 1, 4, 4, 0) SCFG(5, 4, 2, 3, 0) SCFG(7, 2, 2, 6, 0)
-                SCFG(10, 2, 2, 4, 1) SCFG(11, 1, 4, 3, 1) SCFG(12, 2, 2, 4, 2) SCFG(13, 1, 4, 3, 2)
-                // balanced decompositions: 5 pairs per block (gate_up: 237 blocks), 7 n-tiles x 8 K chunks (down / o: 256 blocks)
-                case 20: return two ? launch_stream_t<4, 2, 2, 2, 4, 0, 5>(p, b, st) : launch_stream_t<4, 1, 2, 2, 4, 0, 7>(p, b, st, 8);
-                case 21: return two ? launch_stream_t<4, 2, 3, 2, 3, 0, 5>(p, b, st) : launch_stream_t<4, 1, 2, 2, 4, 0, 7>(p, b, st, 4);
-                case 22: return two ? launch_stream_t<4, 2, 2, 2, 4, 1, 5>(p, b, st) : launch_stream_t<4, 1, 2, 2, 4, 1, 7>(p, b, st, 8);
-                case 23: return two ? launch_stream_t<4, 2, 1, 4, 3, 0, 5>(p, b, st) : launch_stream_t<4, 1, 1, 4, 3, 0, 7>(p, b, st, 8);
-                case 24: return two ? launch_stream_t<4, 2, 2, 2, 4, 0, 8>(p, b, st) : launch_stream_t<4, 1, 2, 2, 4, 0, 7>(p, b, st, 16);
-                default: return hipErrorInvalidValue;
-            }
-#undef SCFG
-        }
-#endif
-        // 256^2 tiles pay once there are ~1.5 block waves of them (every ViT / projector GEMM, gate_up of a >= 600-row chunk)
-        if (variant == GEMM_RING256 || (variant == GEMM_AUTO && ring256_auto(a))) {
-            if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0 || !ring_size_ok(a)) return hipErrorInvalidValue;
-            p.W = a.Wp;
-            if (kind_out) *kind_out = MMD_K_GEMM_TILE;
-            return launch_ringx(a.ring_flags, p, a, st);
-        }
-        // long K with under one block wave of 256^2 tiles (down_proj of a chunk): split K across grid.z so ~one block per CU runs a
-        // long steady state (1.05 PF at M = 1274 against 0.84 PF for the 128-row kernel's 3-way split); K = 3584 shapes lose to it
-        const bool ring_split_ok = big_packed_ok(MMD_BF16, a, 16) && (a.N % 32) == 0 && a.epi != EPI_SWIGLU && a.splitk_ws != nullptr && ring_size_ok(a);
-        if (!a.f16 && (variant == GEMM_RING256_SPLIT || (variant == GEMM_AUTO && a.M >= 512 && a.K >= 8192 && ring_split_ok))) {
-            if (variant == GEMM_RING256_SPLIT && (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0 || !ring_size_ok(a))) return hipErrorInvalidValue;
-            const int sp = ring_split_choice(a);
-            if (variant == GEMM_RING256_SPLIT || sp >= 2) {
-                p.W = a.Wp;
-                if (kind_out) *kind_out = MMD_K_GEMM_TILE;
-                return launch_ringx(16, p, a, st, sp);
-            }
-        }
-#ifdef MMDUET_DEBUG_VARIANTS          // timing experiments of tools/bench_gemm.py (most give WRONG results): `make DEBUG_VARIANTS=1`; never in the shipped library
-        if (variant == 92) {          // DBG 8 on the 4-slot ring
-            if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) return hipErrorInvalidValue; p.W = a.Wp;
-            const int tiles = cdiv(a.N, 256) * cdiv(a.M, 256);
-            const size_t smem = 4 * (256 * 32 + 256 * 32) * sizeof(bf16_t);
-            hipFuncSetAttribute((const void*)gemm_ringx_kernel<EPI_NONE, 4, false, 4, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            hipLaunchKernelGGL((gemm_ringx_kernel<EPI_NONE, 4, false, 4, true, 8>), dim3(tiles <= 256 ? tiles : 256), dim3(512), smem, st, p, a.K >> 5);
-            set_plan(a, GEMM_K_RING256, tiles, 1, tiles <= 256 ? tiles : 256);
-            return hipGetLastError();
-        }
-        if (variant == 93) { if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) return hipErrorInvalidValue; p.W = a.Wp; return launch_ringx_dbg<7>(p, a, st); }
-        if (variant == 94) { if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) return hipErrorInvalidValue; p.W = a.Wp; return launch_ringx_dbg<6>(p, a, st); }
-        if (variant == 95) { if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) return hipErrorInvalidValue; p.W = a.Wp; return launch_ringx_dbg<5>(p, a, st); }
-        if (variant == 99) { if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) return hipErrorInvalidValue; p.W = a.Wp; return launch_ringx_dbg<4>(p, a, st); }
-        if (variant >= 96 && variant <= 98) {                               // timing experiments (WRONG results): see gemm_ringx_kernel DBG
-            if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) return hipErrorInvalidValue;
-            p.W = a.Wp;
-            return variant == 96 ? launch_ringx_dbg<1>(p, a, st) : (variant == 97 ? launch_ringx_dbg<2>(p, a, st) : launch_ringx_dbg<3>(p, a, st));
-        }
-#endif
-        if (variant >= GEMM_RINGX && variant < GEMM_RINGX + 128) {          // forced ring variants (A/B and parity of every instantiation)
-            if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0 || !ring_size_ok(a)) return hipErrorInvalidValue;
-            const int flags = variant - GEMM_RINGX;
-            int sp = 1;
-            if (flags & 4) {
-                const int slots = (flags & 1) ? 512 : 256, tl = cdiv(a.M, 256) * cdiv(a.N, (flags & 1) ? 128 : 256);
-                sp = slots / tl; if (sp < 1) sp = 1;
-                while (sp > 1 && a.K / sp < 1024) --sp;
-                if (sp < 2) sp = 2;
-            }
-            p.W = a.Wp;
-            if (kind_out) *kind_out = MMD_K_GEMM_TILE;
-            return launch_ringx(flags, p, a, st, sp);
-        }
-        const bool want_big = variant == GEMM_BIG || (variant == GEMM_AUTO && a.M > 64);
-        if (want_big) {
-            int bn = 0;
-            // 128-wide tiles need ~1.5 block waves to keep two blocks per CU busy; below that 64-wide tiles (3 blocks/CU) win
-            // by 8-10 % (measured at M = 980 / 1274, K = 3584); long-K shapes keep 128 and split K instead
-            const long long t128 = (long long)cdiv(a.M, 128) * (a.N / 128);
-            if (big_packed_ok(MMD_BF16, a, 128) && (t128 >= 400 || (a.K >= 8192 && t128 >= 224))) bn = 128;
-            else if (big_packed_ok(MMD_BF16, a, 64)) bn = 64;
-            // mid-M (a chunk's qkv / o_proj): once some CU would carry three or more 128-row blocks, one 256x128 ring tile per CU (4-wave ring, flags 17) is the
-            // shorter schedule.  Per-CU cost in units of one 128x64 block at two per CU (17.5 us at K = 3584), fitted to tools/probes/midm_ring4w_sweep.py:
-            // n blocks of 128x64 cost max(1.83, n), of 128x128 max(2.29, 1.77 n), a 256x128 ring tile 2.95 (M = 1323 qkv 75 -> 51 us, M = 1911 o 63 -> 58 us)
-            if (bn && variant == GEMM_AUTO && !a.f16 && a.M >= 512 && a.K >= 1024 && (a.N % 128) == 0 && big_packed_ok(MMD_BF16, a, 16) && ring_size_ok(a)) {
-                const long long mt128 = cdiv(a.M, 128);
-                const double nb = bn == 64 ? (double)cdiv(mt128 * (a.N / 64), 256) : (double)cdiv(t128, 256);
-                const double cbig = bn == 64 ? (nb > 1.83 ? nb : 1.83) : (1.77 * nb > 2.29 ? 1.77 * nb : 2.29);
-                const double cr4 = 2.95 * (double)cdiv((long long)cdiv(a.M, 256) * (a.N / 128), 256);
-                if (cr4 < 0.8 * cbig) {          // (only where the model predicts >= 20 %: inside the model, with each layer's weights cold, the 2-8 % cases of the sweep measured -0.3 %)
-                    p.W = a.Wp;
-                    if (kind_out) *kind_out = MMD_K_GEMM_TILE;
-                    return launch_ringx(17, p, a, st);
-                }
-            }
-            if (bn) {
-                p.W = a.Wp;
-                if (kind_out) *kind_out = MMD_K_GEMM_TILE;
-                if (bn == 128) launch_big<128>(p, a, st); else launch_big<64>(p, a, st);
-                return hipGetLastError();
-            }
-            if (variant == GEMM_BIG) return hipErrorInvalidValue;
-        }
-        if (a.f16) return hipErrorInvalidValue;          // IEEE-half operands exist in the ring / big kernels only (the tower's shapes: M >= 65, N % 64 == 0, K % 64 == 0, packed weights)
-        if (skinny && skinny_packed_ok(MMD_BF16, a)) {
-            p.W = a.Wp;
-            if (a.M <= 16 && !a.no_gemv) launch_gemv16(p, a, st);
-            else if (a.chain) return hipErrorInvalidValue;          // the decode chain exists in the GEMV kernel only
-            else if (a.M <= 16) launch_skinny_mt<1>(p, a, st);
-            else if (a.M <= 32) launch_skinny_mt<2>(p, a, st);
-            else launch_skinny_mt<4>(p, a, st);
-            return hipGetLastError();
-        }
-    }
-    if (a.slabs_out) return hipErrorInvalidValue;          // slab mode exists only on the packed skinny path
-    if (a.chain) return hipErrorInvalidValue;
-    if (a.W == nullptr) return hipErrorInvalidValue;       // only the packed copy exists but the shape needs the generic path
-    int splits = 1;
-    if (skinny) {
-        int blocks = cdiv(a.N, 64) * cdiv(a.M, 64);
-        int want = cdiv(512, blocks);
-        int maxs = a.K / 256; if (maxs < 1) maxs = 1;
-        splits = want < maxs ? want : maxs;
-        if (splits > 16) splits = 16;
-        if (a.splitk_ws == nullptr) splits = 1;
-        while (splits > 1 && (size_t)splits * a.M * a.N * sizeof(float) > a.splitk_ws_bytes) --splits;
-    }
-    int kper = (int)round_up(cdiv(a.K, splits), 32);
-    splits = cdiv(a.K, kper);
-    p.kper = kper;
-    if (large) {
-        dim3 grid(cdiv(a.N, 128), cdiv(a.M, 128), 1);
-        set_plan(a, GEMM_K_TILE128, (int)(grid.x * grid.y), 1, (int)(grid.x * grid.y));
-        hipLaunchKernelGGL((gemm_tile_kernel<T, 128, 128>), grid, dim3(256), 0, st, p);
-    } else {
-        dim3 grid(cdiv(a.N, 64), cdiv(a.M, 64), splits);
-        set_plan(a, GEMM_K_TILE64, (int)(grid.x * grid.y), splits, (int)(grid.x * grid.y) * splits);
-        hipLaunchKernelGGL((gemm_tile_kernel<T, 64, 64>), grid, dim3(256), 0, st, p);
-        if (splits > 1) {
-            long long work = (long long)a.M * ((a.N + 3) / 4);
-            hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(cdiv(work, 256)), dim3(256), 0, st, p, splits);
-        }
-    }
-    return hipGetLastError();
-}
-
-bool gemm_can_slab(int dtype, const GemmArgs& a) {
-    if (skinny_packed_ok(dtype, a) && a.splitk_ws != nullptr && a.epi != EPI_SWIGLU) return true;
-    int dummy = 0; GemmArgs b = a; b.slabs_out = &dummy; b.epi = EPI_NONE;
-    return stream_ok(dtype, b);          // 64 < M <= 256: gemm_stream_kernel leaves slabs too
-}
-
-hipError_t launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* kind_out) {
-    if (dtype == MMD_F16) { GemmArgs h = a; h.f16 = 1; return launch_t<bf16_t>(h, st, kind_out); }          // 2-byte storage either way; the kernels' F16 forms read the bits as IEEE half
-    return dtype == MMD_F32 ? launch_t<float>(a, st, kind_out) : launch_t<bf16_t>(a, st, kind_out);
+hipError_t launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, const GemmPlan* planned) {
+    const GemmPlan pl = planned ? *planned : gemm_plan_for(dtype, a);
+    return dtype != MMD_F32 ? launch_t<bf16_t>(a, pl, st) : launch_t<float>(a, pl, st);          // MMD_F16: 2-byte storage either way; the kernels' F16 forms read the bits as IEEE half
 }

@@ -1,5 +1,5 @@
 // gemm_ring.h -- the ring GEMM (gemm_ringx_kernel) with the parameter block and the epilogue helpers it shares with the other tile kernels.
-// Included by gemm.hip (the dispatcher and every other GEMM kernel) and by tools/probes/ring_probe.hip (one instantiation, for register / ISA audits).
+// Included by gemm.hip (the launchers and every other GEMM kernel; when this kernel runs, in which instantiation and with how many K splits: plan_kernel / plan_ring in gemm_plan.h) and by tools/probes/ring_probe.hip (one instantiation, for register / ISA audits).
 #pragma once
 #include "common.h"
 #include <type_traits>

@@ -189,34 +189,39 @@ static void prof_drain(mmd_ctx* c) {
 }
 
 // ---- GEMM wrapper --------------------------------------------------------------------------------------------------
-static int gemm(mmd_ctx* c, const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const void* R, int64_t ldr, void* Y,
-                int64_t ldy, int M, int N, int K, int epi, int out_f32 = 0, int variant = GEMM_AUTO, const void* Wp = nullptr, bool tower = false,
-                const void* Wp8 = nullptr, const float* wscale = nullptr, const GemvChain* chain = nullptr, int* ring_slabs_out = nullptr, int pm = 0) {
-    GemmArgs a; a.chain = chain; a.ring_slabs_out = ring_slabs_out; a.x_pm = pm & 1; a.y_pm = (pm >> 1) & 1;          // pm: 1 = X is piece-major, 2 = Y becomes piece-major (gemm_pair_pm)
+// the GemmArgs of a GEMM in this context (tower: the side stream's split-K scratch and ring instantiation) -- the one place they are filled, for launches and for probes
+static GemmArgs gemm_args(mmd_ctx* c, const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K,
+                          int epi, int out_f32, int variant, const void* Wp, bool tower, const void* Wp8 = nullptr, const float* wscale = nullptr) {
+    GemmArgs a;
     a.X = X; a.ldx = ldx; a.W = W; a.ldw = ldw; a.Wp = Wp; a.bias = bias; a.R = R; a.ldr = ldr; a.Y = Y; a.ldy = ldy;
     a.M = M; a.N = N; a.K = K; a.epi = epi; a.out_f32 = out_f32; a.variant = variant; a.Wp8 = Wp8; a.wscale = wscale;
     a.splitk_ws = tower ? c->v_splitk_ws : c->splitk_ws; a.splitk_ws_bytes = tower ? c->v_splitk_bytes : c->splitk_bytes;
     a.plan_out = c->last_plan;
     if (tower && c->tower_ring_flags >= 0) { a.ring_flags = c->tower_ring_flags; a.ring_max_blocks = c->tower_ring_blocks; }
-    int kind = (variant == GEMM_SKINNY || (variant != GEMM_BIG && variant != GEMM_RING256 && variant != GEMM_RING256_SPLIT && variant < GEMM_RINGX && variant != GEMM_LARGE && variant != GEMM_GENERIC && (M <= 64 || (M <= 256 && epi == EPI_SWIGLU)))) ? MMD_K_GEMM_SKINNY : MMD_K_GEMM_TILE;          // (64 < M <= 256: gate_up runs on the streaming kernel)
+    return a;
+}
+static int gemm(mmd_ctx* c, const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const void* R, int64_t ldr, void* Y,
+                int64_t ldy, int M, int N, int K, int epi, int out_f32 = 0, int variant = GEMM_AUTO, const void* Wp = nullptr, bool tower = false,
+                const void* Wp8 = nullptr, const float* wscale = nullptr, const GemvChain* chain = nullptr, int* ring_slabs_out = nullptr, int pm = 0) {
+    GemmArgs a = gemm_args(c, X, ldx, W, ldw, bias, R, ldr, Y, ldy, M, N, K, epi, out_f32, variant, Wp, tower, Wp8, wscale);
+    a.chain = chain; a.ring_slabs_out = ring_slabs_out; a.x_pm = pm & 1; a.y_pm = (pm >> 1) & 1;          // pm: 1 = X is piece-major, 2 = Y becomes piece-major (gemm_pair_pm)
+    const int dt = c->gemm_half ? MMD_F16 : c->cfg.dtype;          // gemm_half: inside the fp16 vision tower (vit_tower sets it)
+    const GemmPlan pl = gemm_plan_for(dt, a);          // the profiler class is that of the kernel that runs
     double e = (double)es(c);
     double bytes = (double)M * K * e + (double)N * K * ((Wp8 && M <= 64) ? 1.0 : e) + (double)M * (epi == EPI_SWIGLU ? N / 2 : N) * (out_f32 ? 4.0 : e);
-    ProfScope ps(c, kind, bytes, 2.0 * M * N * K);
-    HIPCHK(c, launch_gemm(c->gemm_half ? MMD_F16 : c->cfg.dtype, a, c->stream, nullptr));          // gemm_half: inside the fp16 vision tower (vit_tower sets it)
+    ProfScope ps(c, pl.prof_class, bytes, 2.0 * M * N * K);
+    HIPCHK(c, launch_gemm(dt, a, c->stream, &pl));
     return MMD_OK;
 }
 
 // May the intermediate between a producer GEMM (X1 [M,K1] -> T [M,N1], epilogue epi1) and its ONLY consumer (T -> [M,N2]) live in the ring kernel's piece-major layout?
-// Yes when the automatic dispatch runs BOTH on gemm_ringx_kernel (same conditions the launcher itself evaluates: gemm_ring_auto).
+// Yes when the automatic dispatch runs BOTH on gemm_ringx_kernel (gemm_ring_auto asks the planner about the very arguments gemm() will launch with).
 static bool gemm_pair_pm(mmd_ctx* c, bool tower, const void* X1, int64_t ldx1, const void* W1p, const void* b1, int N1w, int K1, int epi1, void* T, int64_t ldt,
                          const void* W2p, int N2, const void* R2, int64_t ldr2, void* Y2, int64_t ldy2, int epi2, int M) {
     if (c->no_pm) return false;
     const int dt = c->gemm_half ? MMD_F16 : c->cfg.dtype;
-    GemmArgs a; memset(&a, 0, sizeof(a)); a.ring_flags = 16;
-    a.X = X1; a.ldx = ldx1; a.Wp = W1p; a.bias = b1; a.Y = T; a.ldy = ldt; a.M = M; a.N = N1w; a.K = K1; a.epi = epi1; a.variant = GEMM_AUTO;
-    a.splitk_ws = tower ? c->v_splitk_ws : c->splitk_ws; a.splitk_ws_bytes = tower ? c->v_splitk_bytes : c->splitk_bytes;
-    GemmArgs b = a;
-    b.X = T; b.ldx = ldt; b.Wp = W2p; b.bias = nullptr; b.R = R2; b.ldr = ldr2; b.Y = Y2; b.ldy = ldy2; b.N = N2; b.K = (int)ldt; b.epi = epi2;
+    const GemmArgs a = gemm_args(c, X1, ldx1, nullptr, 0, b1, nullptr, 0, T, ldt, M, N1w, K1, epi1, 0, GEMM_AUTO, W1p, tower);
+    const GemmArgs b = gemm_args(c, T, ldt, nullptr, 0, nullptr, R2, ldr2, Y2, ldy2, M, N2, (int)ldt, epi2, 0, GEMM_AUTO, W2p, tower);
     return gemm_ring_auto(dt, a, true) && gemm_ring_auto(dt, b);          // (the producer on the PLAIN ring: its split-K form writes row-major through splitk_reduce -- ADVICE r05)
 }
 
@@ -1249,17 +1254,20 @@ static int llm_step_segs(mmd_ctx* c, const StepSeg* segs, int nseg, const void* 
     // Fused schedule for the weight-streaming regime (S <= 256, packed bf16 weights): the skinny / streaming GEMMs leave fp32 split-K
     // slabs and the NEXT operator consumes them (reduce + bias + RoPE + KV append; reduce + residual + RMSNorm):
     // 9 launches per layer instead of 12, identical rounding points.
+    // the GemmArgs of a slab-mode GEMM of this step (the weight-streaming kernels leave fp32 K slabs in the split-K workspace): what slab_gemm launches and the probes below ask about
+    auto slab_args = [&](const void* X, int64_t ldx, const void* Wp, int M, int N, int K) {
+        GemmArgs a; memset(&a, 0, sizeof(a));
+        a.X = X; a.ldx = ldx; a.Wp = Wp; a.M = M; a.N = N; a.K = K; a.epi = EPI_NONE; a.variant = GEMM_SKINNY;
+        a.splitk_ws = c->splitk_ws; a.splitk_ws_bytes = c->splitk_bytes;
+        return a;
+    };
     bool fused = false;
     // (several streams in one step -- mmd_round_multi's decode rounds: every talking stream's row, a few short segments -- take the same schedule: the GEMVs and the
     //  slab consumers are row-wise, RoPE + KV append + attention read each stream's rows of the slabs at its row offset; MMDUET_NO_MULTI_FUSE=1 keeps the unfused form, A/B)
     static const bool no_multi_fuse = getenv("MMDUET_NO_MULTI_FUSE") != nullptr;
     if ((nseg == 1 || !no_multi_fuse) && dt == MMD_BF16 && S <= 256 && H <= 4096 && (H & 3) == 0 && !c->no_fuse) {          // (S > 64: gemm_stream_kernel's slabs -- gemm_can_slab says whether the shapes qualify)
-        GemmArgs probe; memset(&probe, 0, sizeof(probe));
-        probe.X = c->l_xn; probe.ldx = H; probe.Wp = c->L[0].wqkv_p; probe.M = S; probe.N = c->qkv_w; probe.K = H; probe.epi = EPI_NONE;
-        probe.splitk_ws = c->splitk_ws; probe.splitk_ws_bytes = c->splitk_bytes;
-        GemmArgs p2 = probe; p2.Wp = c->L[0].wdown_p; p2.N = H; p2.K = I; p2.ldx = I; p2.X = c->l_act;
-        GemmArgs p3 = probe; p3.Wp = c->L[0].wo_p; p3.N = H; p3.K = nh * d; p3.ldx = nh * d; p3.X = c->l_attn;
-        fused = gemm_can_slab(dt, probe) && gemm_can_slab(dt, p2) && gemm_can_slab(dt, p3);
+        fused = gemm_can_slab(dt, slab_args(c->l_xn, H, c->L[0].wqkv_p, S, c->qkv_w, H)) && gemm_can_slab(dt, slab_args(c->l_act, I, c->L[0].wdown_p, S, H, I)) &&
+                gemm_can_slab(dt, slab_args(c->l_attn, nh * d, c->L[0].wo_p, S, H, nh * d));
     }
     // Decode chain (S <= 4: every GEMM is the weight-streaming GEMV): o_proj / down_proj fold their result into the residual stream themselves
     // and leave the row sums of squares, qkv / gate_up build the normalised activation per lane (GemvChain, common.h): 7 launches per layer.
@@ -1268,12 +1276,10 @@ static int llm_step_segs(mmd_ctx* c, const StepSeg* segs, int nseg, const void* 
     ch_fin.fin_h = c->l_h; ch_fin.fin_ssq = c->chain_ssq;
     ch_xn.xn_h = c->l_h; ch_xn.xn_ssq = c->chain_ssq; ch_xn.xn_eps = g.rms_norm_eps;
     auto slab_gemm = [&](const void* X, int64_t ldx, const void* Wp, int N, int K, int* splits, const void* Wp8, const float* wscale, const GemvChain* chn = nullptr, int Mrows = 0) -> int {
-        GemmArgs a; memset(&a, 0, sizeof(a));
-        a.chain = chn;
-        a.X = X; a.ldx = ldx; a.Wp = Wp; a.Wp8 = Wp8; a.wscale = wscale; a.M = Mrows > 0 ? Mrows : S; a.N = N; a.K = K; a.epi = EPI_NONE; a.variant = GEMM_SKINNY;
-        a.splitk_ws = c->splitk_ws; a.splitk_ws_bytes = c->splitk_bytes; a.slabs_out = splits;
+        GemmArgs a = slab_args(X, ldx, Wp, Mrows > 0 ? Mrows : S, N, K);
+        a.chain = chn; a.Wp8 = Wp8; a.wscale = wscale; a.slabs_out = splits;
         ProfScope ps(c, MMD_K_GEMM_SKINNY, (double)S * K * e + (double)N * K * (Wp8 ? 1.0 : e) + (double)S * N * e, 2.0 * S * N * K);
-        HIPCHK(c, launch_gemm(dt, a, st, nullptr));
+        HIPCHK(c, launch_gemm(dt, a, st));
         return MMD_OK;
     };
     if (dyn && !fused) FAIL(c, MMD_EINVAL, "graph decode needs the fused bf16 schedule");
@@ -1321,11 +1327,7 @@ static int llm_step_segs(mmd_ctx* c, const StepSeg* segs, int nseg, const void* 
     //  last layer would stream the same weights for fewer rows and add the gather launches: nothing to win, so the gate is `!fused`, not a row count.)
     bool sparse_last = false;
     if (need_rows && n_need > 0 && n_need <= 64 && !fused && S > 64 && dt == MMD_BF16 && H <= 4096 && (H & 3) == 0 && !c->no_fuse && !c->full_last_layer && !hidden_out && !dyn) {
-        GemmArgs probe; memset(&probe, 0, sizeof(probe));
-        probe.X = c->l_q; probe.ldx = nh * d; probe.Wp = c->L[0].wo_p; probe.M = n_need; probe.N = H; probe.K = nh * d; probe.epi = EPI_NONE;
-        probe.splitk_ws = c->splitk_ws; probe.splitk_ws_bytes = c->splitk_bytes;
-        GemmArgs p2 = probe; p2.Wp = c->L[0].wdown_p; p2.K = I; p2.ldx = I; p2.X = c->l_act;
-        sparse_last = gemm_can_slab(dt, probe) && gemm_can_slab(dt, p2);
+        sparse_last = gemm_can_slab(dt, slab_args(c->l_q, nh * d, c->L[0].wo_p, n_need, H, nh * d)) && gemm_can_slab(dt, slab_args(c->l_act, I, c->L[0].wdown_p, n_need, H, I));
         if (sparse_last) {
             for (int k = 0; k < n_need; ++k) if (need_rows[k] < 0 || need_rows[k] >= S) FAIL(c, MMD_ERANGE, "needed row %d outside the step", need_rows[k]);
         }
@@ -1829,7 +1831,7 @@ extern "C" int mmd_op_gemm_slabs(mmd_ctx* c, const void* X, const void* W, int M
     g.X = X; g.ldx = K; g.Wp = Wp; g.M = M; g.N = N; g.K = K; g.epi = EPI_NONE; g.variant = variant;
     g.splitk_ws = slabs_out; g.splitk_ws_bytes = (size_t)max_splits * M * N * sizeof(float); g.slabs_out = &splits; g.plan_out = c->last_plan;
     if (!Wp || !gemm_can_slab(c->cfg.dtype, g)) { if (Wp) dev_free(c, Wp); FAIL(c, MMD_EINVAL, "gemm_slabs: no slab kernel takes M = %d, N = %d, K = %d in this context's dtype", M, N, K); }          // (a shape no slab kernel accepts would fall through to a tile kernel with Y == nullptr)
-    hipError_t e = launch_gemm(c->cfg.dtype, g, c->stream, nullptr);
+    hipError_t e = launch_gemm(c->cfg.dtype, g, c->stream);
     hipStreamSynchronize(c->stream);
     dev_free(c, Wp);
     if (e != hipSuccess) FAIL(c, MMD_EHIP, "slab GEMM launch failed: %s", hipGetErrorString(e));
@@ -1913,7 +1915,7 @@ extern "C" int mmd_op_gemm_bench(mmd_ctx* c, int M, int N, int K, int epi, int v
             GemmArgs g; memset(&g, 0, sizeof(g));
             g.X = X; g.ldx = K; g.Wp = Wp; g.Wp8 = Wp8; g.wscale = wsc; g.M = M; g.N = N; g.K = K; g.epi = EPI_NONE; g.variant = GEMM_SKINNY;
             g.splitk_ws = c->splitk_ws; g.splitk_ws_bytes = c->splitk_bytes; g.slabs_out = &slabs;
-            return launch_gemm(c->cfg.dtype, g, c->stream, nullptr) == hipSuccess ? MMD_OK : MMD_EHIP;
+            return launch_gemm(c->cfg.dtype, g, c->stream) == hipSuccess ? MMD_OK : MMD_EHIP;
         }
         return gemm(c, X, K, W, K, nullptr, epi == EPI_RESID ? R : nullptr, NO, Y, NO, M, N, K, epi, 0, variant, Wp, false, Wp8, wsc);
     };

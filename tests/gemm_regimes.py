@@ -1,6 +1,7 @@
-"""The GEMM dispatch regimes of launch_t (mmduet_amd/csrc/gemm.hip), one row per shape: which kernel and which instantiation the automatic
+"""The GEMM dispatch regimes of gemm_plan (mmduet_amd/csrc/gemm_plan.h), one row per shape: which kernel and which instantiation the automatic
 dispatch must choose, on both sides of every threshold.  Plain data (imports without a GPU): tests/test_gemm_regime_table.py checks the table
-itself, tests/test_gpu_gemm_regimes.py runs every row on the device.
+itself, tests/test_gemm_plan_host.py asks gemm_plan about every row on the host (plan and instantiation), tests/test_gpu_gemm_regimes.py runs every
+row on the device.
 
 A row is (name, mode, width, M, max_step_tokens, plan, inst):
   * mode -- 'gemm': mmd_op_gemm, epilogue in place, variant 0 (automatic);  'slabs': mmd_op_gemm_slabs, variant 2 (the fused schedule's fp32 K
@@ -13,11 +14,12 @@ A row is (name, mode, width, M, max_step_tokens, plan, inst):
     per wave for SwiGLU or >= 2048 even n-tiles), MT / NT / WN (waves per block, from stream_plan's cost model) of gemm_stream_kernel.
     blocks = (NT == 2 ? tiles / 2 : tiles) * splits (GEMV), cdiv(tiles, 4 NT) * splits (skinny), cdiv(tiles, WN NT) * splits (stream).
 
-Every plan was derived by hand from launch_t, launch_gemv16, launch_skinny_mt, stream_ok / stream_plan / launch_stream_t, launch_big / big_bm160,
-ring256_auto / ring_tiles_ok, ring_split_choice and the mid-M cost model of the 4-wave ring; the GPU test confirms each one."""
+Every plan was derived by hand from gemm_plan and what it calls: plan_kernel's branch order, plan_gemv16, plan_skinny, stream_ok / stream_plan /
+stream_geometry, plan_big / big_bm160, ring_tiles_ok, ring_split_choice / plan_ring and the mid-M cost model of the 4-wave ring; the host test and the GPU
+test confirm each one."""
 from collections import namedtuple
 
-# GEMM_K_* of csrc/common.h (the host test checks the names and values against the header)
+# GEMM_K_* of csrc/gemm_plan.h (the host test checks the names and values against the header)
 TILE64, TILE128, SKINNY, GEMV16, BIG64, BIG128, RING256, RING128X2, STREAM = range(9)
 KERNEL_NAMES = {TILE64: 'TILE64', TILE128: 'TILE128', SKINNY: 'SKINNY', GEMV16: 'GEMV16', BIG64: 'BIG64', BIG128: 'BIG128', RING256: 'RING256',
                 RING128X2: 'RING128X2', STREAM: 'STREAM'}

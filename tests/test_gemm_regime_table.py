@@ -1,6 +1,7 @@
 """The GEMM regime table (tests/gemm_regimes.py) against the header and against itself, without a GPU: every kernel id of GEMM_K_* has a row, every
 M threshold has its rows on both sides at every swept width, every named edge really switches the plan, and every row meets the shape conditions of
-the kernel and instantiation it claims (tests/test_gpu_gemm_regimes.py then checks on the device that the dispatcher agrees)."""
+the kernel and instantiation it claims (tests/test_gemm_plan_host.py then asks the dispatch decision itself, on the host, and tests/test_gpu_gemm_regimes.py checks on the
+device that every row's kernel really runs and computes the right thing)."""
 import os
 import re
 import pytest
@@ -15,9 +16,9 @@ def cdiv(a, b):
 
 
 def _header_kernel_ids():
-    src = open(os.path.join(ROOT, 'mmduet_amd', 'csrc', 'common.h')).read()
+    src = open(os.path.join(ROOT, 'mmduet_amd', 'csrc', 'gemm_plan.h')).read()
     m = re.search(r'enum\s*\{\s*(GEMM_K_[^}]*)\}', src)
-    assert m, 'GEMM_K_* enum not found in common.h'
+    assert m, 'GEMM_K_* enum not found in gemm_plan.h'
     ids = dict((k, int(v)) for k, v in re.findall(r'GEMM_K_(\w+)\s*=\s*(\d+)', m.group(1)))
     assert ids
     return ids
