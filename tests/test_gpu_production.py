@@ -17,6 +17,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 from oracle import duet_oracle as O
 from conftest import ROOT
+from parity_common import rel_err as _rel_err, ref_attention as _ref_attention_gpu, ref_attention_rows as _ref_attention_rows
 
 RESULTS = {}
 
@@ -49,10 +50,6 @@ def _plan(ops):
 
 
 RING = (6, 7)       # GEMM_K_RING256 / the 4-wave 256x128 ring
-
-
-def _rel_err(got, ref):
-    return (got.float() - ref.float()).abs().max().item() / max(1.0, ref.float().abs().max().item())
 
 
 # ---- (a) production GEMM shapes through the dispatcher ---------------------------------------------------------------------------
@@ -185,20 +182,6 @@ def test_ring_gemm_is_deterministic_and_tile_order_independent(ops):
 
 
 # ---- (b) chunk attention at the production sizes -----------------------------------------------------------------------------------
-def _ref_attention_gpu(q, K, V, nh, nkv, d, n_ctx):
-    """fp32 torch attention on the device, one kv group at a time.  q [S, nh*d]; K/V [nkv, cap, d]."""
-    S = q.shape[0]; n_tot = n_ctx + S; rep = nh // nkv
-    qh = q.float().view(S, nh, d).transpose(0, 1)
-    out = torch.empty(nh, S, d, device=q.device)
-    mask = torch.arange(n_tot, device=q.device)[None, :] > (torch.arange(S, device=q.device)[:, None] + n_ctx)
-    for h in range(nkv):
-        kk, vv = K[h, :n_tot].float(), V[h, :n_tot].float()
-        s = qh[h * rep:(h + 1) * rep] @ kk.T * d ** -0.5
-        s = s.masked_fill(mask[None], float('-inf'))
-        out[h * rep:(h + 1) * rep] = torch.softmax(s, -1) @ vv
-    return out.transpose(0, 1).reshape(S, nh * d)
-
-
 # (147 rows x 7 heads = 1029 rows per kv head: the smallest step on the 256-row phase-split kernel; 146 stays on the 128-row form; 1 / 2 / 3 key tiles per split, a partial
 #  last query block, new positions on tile boundaries, contexts deep enough for every ring slot to be refilled many times)
 @pytest.mark.parametrize('S,n_ctx', [(1274, 0), (1274, 15000), (1274, 30000), (1323, 8000), (49, 30000), (131, 15000),
@@ -468,29 +451,6 @@ def test_ring_attention_repeats_bit_identical_beside_a_copy_stream(ops, S, n_ctx
                 noise[:128 << 20].copy_(noise[128 << 20:], non_blocking=True)
         assert torch.equal(ops.attention(q, K, V, nh, nkv, d, n_ctx, True, 3), first), r
     torch.cuda.synchronize()
-
-
-def _ref_attention_rows(q, K, V, nh, nkv, d, n_ctx, rows):
-    """fp32 attention of the query rows `rows` only (row r sees keys 0 .. n_ctx + r), one kv group and 256 Ki keys at a time with a running (max, sum) --
-    the 1 M-key contexts never materialise an [S, n] score matrix.  q [S, nh*d]; K / V [nkv, cap, d] row-major."""
-    rep = nh // nkv
-    rows_t = torch.as_tensor(rows, device=q.device)
-    qh = q.float().view(q.shape[0], nh, d)[rows_t].transpose(0, 1)              # [nh, R, d]
-    out = torch.empty(nh, len(rows), d, device=q.device)
-    n_max = n_ctx + max(rows) + 1
-    for h in range(nkv):
-        qq = qh[h * rep:(h + 1) * rep] * d ** -0.5
-        m = torch.full((rep, len(rows), 1), float('-inf'), device=q.device); l = torch.zeros_like(m); acc = torch.zeros(rep, len(rows), d, device=q.device)
-        for k0 in range(0, n_max, 1 << 18):
-            k1 = min(n_max, k0 + (1 << 18))
-            s = qq @ K[h, k0:k1].float().T
-            dead = torch.arange(k0, k1, device=q.device)[None, :] > (rows_t[:, None] + n_ctx)
-            s = s.masked_fill(dead[None], float('-inf'))
-            m2 = torch.maximum(m, s.amax(-1, keepdim=True))
-            p = torch.exp(s - m2); sc = torch.exp(m - m2)
-            l = l * sc + p.sum(-1, keepdim=True); acc = acc * sc + p @ V[h, k0:k1].float(); m = m2
-        out[h * rep:(h + 1) * rep] = acc / l
-    return out.transpose(0, 1).reshape(len(rows), nh * d)
 
 
 @pytest.mark.parametrize('S,variant,form', [(49, 5, 5), (1, 3, 3), (1274, 6, 8)], ids=['frame_step', 'decode_row', 'chunk_26_frames'])

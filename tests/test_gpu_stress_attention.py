@@ -1,0 +1,204 @@
+"""Every attention form on the inputs real checkpoints produce and `randn` data does not (tests/stress_inputs.py): an attention sink, a hot key in the last
+split, a running max that rises on every key tile, scores in the thousands, three outlier channels, a row that sees one key.  These reach what the benign
+parity tests cannot: the exp2-domain online softmax with its deferred rescale (ATTN_DEFER: P may reach 2^4 before the running max moves), the
+`m_run == -INFINITY` guards, and split merges in which a split's weight exp2(m_s - M) is exactly 0.
+
+Reference: plain torch attention in float64 on the same bf16 inputs (parity_common.ref_attention).  Bound: the benign tests' own, unchanged --
+max|o - ref| <= 1.8e-2 max(1, max|ref|) for the 28 / 4 / 128 forms, assert_close(scale = 1.5) of tests/test_gpu_ops.py for the others -- plus isfinite.  V is
+N(0, 1) and the outputs O(1 .. 5), so the max-norm and the element-wise view coincide.  A host emulation of the kernels' arithmetic (64-key tiles, exp2
+domain, rescale deferred by 4, P rounded to bf16, fp32 accumulators, 4-way split merge, bf16 output) stays within 5.6e-3 (outlier_dims), 3.4e-3 (rising),
+1.9e-3 (huge) and exactly 0 (sink, last_hot): a 3x margin for a right kernel, none for one that drops a rescale, merges an underflowed split with a NaN
+weight or reads a poisoned key.
+
+The bound is keyed on the form and the dtype, never on the pattern: 1.8e-2 for forms 3, 4, 5 and 8 (the specialised bf16 kernels), assert_close(scale = 1.5)
+for forms 1, 2, 6 and 7 -- 1.8e-2 in bf16, 3e-5 in fp32.  The fp32 instantiation of variant 1 gets one more term, from the arithmetic alone and the same for every
+case: 2 ulp_fp32(max|score|) of max(1, max|ref|).  An fp32 score cannot be carried better than half an ulp at its own magnitude however it is summed, nor can the
+running max, so the exponent s - m is uncertain by an ulp; the second ulp covers the order of the d-term sum.  A softmax weight inherits that as a relative error and
+the output, a weighted mean of V rows, with it.  At max|score| = 60 (the one-hot patterns) the term is 8e-6; at ~410 (rising, d = 32) 6e-5, where the kernel measured
+3.5e-5; at ~4000 (huge, d = 128) 5e-4, where it measured 1.3e-4.
+
+Two assertions the benign data cannot make: under sink / last_hot / first_row_only every row that sees the hot key must equal that key's V row to one
+bf16 ulp (exact in the reference), and variants 3, 5 and 6 agree with each other within 8e-3 under stress too.
+
+Forms (mmd_op_attention_last_form, asserted per case): 1 one wave per row, 2 16-row MFMA, 3 decode ring / 64-row, 4 two-slot 128-row and 256-row
+phase-split, 5 attn_gqa128_w1_kernel, 6 register-staged row-major (d = 64, and d = 72 with MMDUET_VIT_ATTN_RING=0), 7 attn_d72_ring_kernel,
+8 attn_gqa128_chunk_kernel + combine.  Form 9 (several streams' decode rows in one launch) is reachable only through mmd_round_multi:
+no case here reaches it; a model-level stream on sink-structured weights is the follow-up that would.
+
+Measured errors are recorded under stress_attn_<form>_<pattern>_S.._n.. (_record of tests/test_gpu_production.py).  On an MI355X, largest max|o - ref| / max(1, max|ref|) over
+the shapes of each variant (sink, last_hot and first_row_only: exactly 0 on every form):
+    variant            rising    huge      outlier_dims
+    1 bf16 / 2         2.7e-3    2.0e-3    3.1e-3
+    1 fp32             3.5e-5    1.3e-4    1.0e-5
+    3 (forms 3, 4)     3.7e-3    3.3e-3    4.7e-3
+    4 (forms 6, 7)     5.4e-3    2.6e-3    4.1e-3
+    5                  4.5e-3    2.9e-3    3.8e-3
+    6 (form 8)         3.1e-3    3.0e-3    4.3e-3
+No kernel bug was found by these cases.
+
+Mutation check (throw-away builds, never committed, each run once on an MI355X).  (a) ATTN_DEFER raised to 400, so the deferred rescale never happens after the first tile: the 176
+benign attention cases of test_gpu_ops.py / test_gpu_production.py all still pass; 87 of the 249 cases here fail (not finite, or outside the bound) -- forms 3 and 4
+on huge 15, last_hot 13, rising 7, outlier_dims 4; the w1 kernel 18, the chunk kernel 15, the tower kernels 14 + the register-staged twin.  (b) attn_combine128_kernel's
+`Mn == -INFINITY ? 0 : Mn` guard replaced by Mn (an unconditional exp2f(m_s - M)): both suites pass, and must -- it is an equivalent mutant.  exp2f(-inf - M) is 0
+for every finite M, so an empty split merges with weight 0 either way; the guard only acts when EVERY split of a row is empty, and every row sees at least its own key.
+The same holds for the `-INFINITY` tests of attn_combine_kernel and attn_combine128_chunk_kernel: no valid launch reaches them.  (c) The guard a launch does reach,
+the in-kernel `m_run == -INFINITY ? 0 : -m_run` of attn_gqa128_kernel, attn_gqa128_w1_kernel and attn_gqa128_chunk_kernel, replaced by -m_run (a split or a tile whose
+keys are all masked for the early rows then computes exp2(-inf + inf)): 24 of the 249 cases here fail -- the chunk kernel 14 (first_row_only 4, two of each other
+pattern), forms 3 / 4 and the w1 kernel one per pattern -- and the benign data sees this one too, 15 of 176 (it needs masked tiles, not outliers)."""
+import ctypes as C
+import math, os, subprocess, sys
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+import stress_inputs as SI
+from parity_common import rel_err, ref_attention, max_abs_score
+from test_gpu_production import _record as record
+from conftest import ROOT
+
+CAUSAL_PATTERNS = ['sink', 'rising', 'last_hot', 'huge', 'outlier_dims', 'first_row_only']
+NONCAUSAL_PATTERNS = ['sink', 'rising', 'last_hot', 'huge', 'outlier_dims']
+Q7 = (28, 4, 128)
+
+
+@pytest.fixture(scope='module')
+def ctxs():
+    """one RawOps context per dtype, released with the module"""
+    c = {}
+    yield c
+    c.clear()
+    torch.cuda.empty_cache()
+
+
+def _ops(ctxs, dtype):
+    if dtype not in ctxs:
+        from rawops import RawOps
+        ctxs[dtype] = RawOps(dtype)
+    return ctxs[dtype]
+
+
+def _form(ops):
+    from mmduet_amd._lib import lib
+    f = (C.c_int * 2)(); lib().mmd_op_attention_last_form(ops.ctx, f)
+    return f[0]
+
+
+def _case(pattern, ops, S, nh, nkv, d, n_ctx, causal):
+    c = SI.ATTN_PATTERNS[pattern](S, nh, nkv, d, n_ctx, causal=causal, seed=S * 13 + n_ctx + d, device=ops.dev)
+    if ops.dtype != torch.bfloat16:          # the fp32 kernels read the same bf16-rounded values
+        c = c._replace(q=c.q.to(ops.dtype), K=c.K.to(ops.dtype), V=c.V.to(ops.dtype))
+    return c
+
+
+def _check(ops, pattern, c, o, nh, nkv, d, causal, want_form, tag):
+    """form, isfinite, the benign bound against float64, and the hot key's V row where one key owns the softmax; -> max-norm error"""
+    S = c.q.shape[0]
+    form = _form(ops)
+    assert form == want_form, (tag, pattern, form)
+    ref = ref_attention(c.q, c.K, c.V, nh, nkv, d, c.n_ctx, torch.float64, causal)
+    err = (o.double() - ref).abs().max().item()
+    den = max(1.0, ref.abs().max().item())
+    record(f'stress_attn_{tag}_{pattern}_S{S}_n{c.n_ctx}', rel_err=err / den, form=form)
+    print(f'stress_attn_{tag}_{pattern}_S{S}_n{c.n_ctx}: form {form}, max|o - ref| / max(1, |ref|) = {err / den:.3e}')
+    assert torch.isfinite(o.float()).all(), (tag, pattern)
+    if form in (3, 4, 5, 8):
+        tol = 1.8e-2
+    else:
+        tol = (2e-5 if ops.dtype == torch.float32 else 1.2e-2) * 1.5
+        if ops.dtype == torch.float32:          # 2 ulp_fp32 of the largest score (module docstring)
+            tol += 2 * 2.0 ** (math.frexp(max_abs_score(c.q, c.K, nh, nkv, d, c.n_ctx + S))[1] - 24)
+    tol *= den
+    assert err <= tol, (tag, pattern, S, c.n_ctx, err / den, tol / den)
+    if c.hot is not None:
+        v = c.V[:, c.hot].double().repeat_interleave(nh // nkv, 0)[None].expand(S, nh, d)
+        dv = (o.double().view(S, nh, d) - v).abs()
+        assert bool((dv <= 2.0 ** -7 * v.abs().clamp_min(1.0)).all()), (tag, pattern, 'rows differ from the hot key`s V row', dv.max().item())
+    return err / den
+
+
+def _run(ops, pattern, S, nh, nkv, d, n_ctx, causal, variant, want_form, tag):
+    c = _case(pattern, ops, S, nh, nkv, d, n_ctx, causal)
+    o = ops.attention(c.q, c.K, c.V, nh, nkv, d, c.n_ctx, causal, variant)
+    _check(ops, pattern, c, o, nh, nkv, d, causal, want_form, tag)
+    return c, o
+
+
+# ---- variants 1 and 2: the generic kernels ----------------------------------------------------------------------------------------------------------------
+GENERIC_SHAPES = [(7, 4, 2, 16, 5), (49, 4, 1, 32, 300), (130, 4, 2, 16, 41), (49, 28, 4, 128, 3000)]
+
+
+@pytest.mark.parametrize('pattern', CAUSAL_PATTERNS)
+@pytest.mark.parametrize('S,nh,nkv,d,n_ctx', GENERIC_SHAPES)
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16], ids=['f32', 'bf16'])
+def test_one_wave_per_row_kernel_under_stress(ctxs, dtype, S, nh, nkv, d, n_ctx, pattern):
+    _run(_ops(ctxs, dtype), pattern, S, nh, nkv, d, n_ctx, True, 1, 1, 'v1_' + ('f32' if dtype == torch.float32 else 'bf16'))
+
+
+@pytest.mark.parametrize('pattern', CAUSAL_PATTERNS)
+@pytest.mark.parametrize('S,nh,nkv,d,n_ctx', GENERIC_SHAPES)
+def test_mfma_16_row_kernel_under_stress(ctxs, S, nh, nkv, d, n_ctx, pattern):
+    _run(_ops(ctxs, torch.bfloat16), pattern, S, nh, nkv, d, n_ctx, True, 2, 2, 'v2')
+
+
+# ---- variant 3 at 28 / 4 / 128: decode ring, two-slot / 128-row, 256-row phase-split -------------------------------------------------------------------------
+DECODE = [(s, n) for s in (1, 2) for n in (63, 64, 1000, 16400, 70001)]
+GRID = [(49, 1000), (146, 0), (1274, 15000), (147, 1), (2058, 127)]
+
+
+@pytest.mark.parametrize('pattern', CAUSAL_PATTERNS)
+@pytest.mark.parametrize('S,n_ctx', DECODE + GRID)
+def test_gqa128_grid_forms_under_stress(ctxs, S, n_ctx, pattern):
+    _run(_ops(ctxs, torch.bfloat16), pattern, S, *Q7, n_ctx, True, 3, 3 if S * 7 <= 64 else 4, 'v3')
+
+
+# ---- variants 5 and 6, and their agreement with variant 3 on the same inputs ---------------------------------------------------------------------------------
+W1 = [(49, 15000), (49, 63), (98, 15000), (131, 15000), (3, 70001), (256, 5000)]
+CHUNK = [(1274, 15000), (1274, 0), (637, 3), (300, 70000), (40, 5000)]
+
+
+@pytest.mark.parametrize('pattern', CAUSAL_PATTERNS)
+@pytest.mark.parametrize('S,n_ctx', W1)
+def test_w1_kernel_under_stress_and_against_the_grid_form(ctxs, S, n_ctx, pattern):
+    ops = _ops(ctxs, torch.bfloat16)
+    c, o = _run(ops, pattern, S, *Q7, n_ctx, True, 5, 5, 'v5')
+    old = ops.attention(c.q, c.K, c.V, *Q7, c.n_ctx, True, 3)
+    assert rel_err(o, old.float()) <= 8e-3
+
+
+@pytest.mark.parametrize('pattern', CAUSAL_PATTERNS)
+@pytest.mark.parametrize('S,n_ctx', CHUNK)
+def test_chunk_kernel_under_stress_and_against_the_grid_and_w1_forms(ctxs, S, n_ctx, pattern):
+    ops = _ops(ctxs, torch.bfloat16)
+    c, o = _run(ops, pattern, S, *Q7, n_ctx, True, 6, 8, 'v6')
+    old = ops.attention(c.q, c.K, c.V, *Q7, c.n_ctx, True, 3)
+    assert rel_err(o, old.float()) <= 8e-3
+    w1 = ops.attention(c.q, c.K, c.V, *Q7, c.n_ctx, True, 5)
+    assert _form(ops) == 5 and rel_err(o, w1.float()) <= 8e-3
+
+
+# ---- variant 4, non-causal: the tower's kernels ----------------------------------------------------------------------------------------------------------------
+VIT = [(729, 16, 16, 72, 0, 7), (196, 16, 16, 72, 533, 7), (70, 2, 2, 72, 58, 7), (577, 16, 16, 64, 0, 6)]          # .., the form
+
+
+@pytest.mark.parametrize('pattern', NONCAUSAL_PATTERNS)
+@pytest.mark.parametrize('S,nh,nkv,d,n_ctx,form', VIT)
+def test_tower_kernels_under_stress(ctxs, S, nh, nkv, d, n_ctx, form, pattern):
+    _run(_ops(ctxs, torch.bfloat16), pattern, S, nh, nkv, d, n_ctx, False, 4, form, 'v4')
+
+
+def _staged_twin_child():
+    """(child process, MMDUET_VIT_ATTN_RING=0: the switch is read once per process) the d = 72 shapes on attn_rowmajor_kernel<3, 5>"""
+    ctxs = {}
+    ops = _ops(ctxs, torch.bfloat16)
+    for S, nh, nkv, d, n_ctx, _ in VIT[:3]:
+        for pattern in NONCAUSAL_PATTERNS:
+            _run(ops, pattern, S, nh, nkv, d, n_ctx, False, 4, 6, 'v4_staged')
+    print('TWIN OK')
+
+
+def test_register_staged_twin_of_the_d72_ring_under_stress():
+    code = ('import os, sys\nsys.path.insert(0, os.environ["MMD_ROOT"]); sys.path.insert(0, os.path.join(os.environ["MMD_ROOT"], "tests"))\n'
+            'import test_gpu_stress_attention as t\nt._staged_twin_child()\n')
+    r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, MMD_ROOT=ROOT, MMDUET_VIT_ATTN_RING='0'), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and 'TWIN OK' in r.stdout, (r.stdout[-1500:], r.stderr[-2500:])
+    assert r.stdout.count('stress_attn_v4_staged_') == 3 * len(NONCAUSAL_PATTERNS)
