@@ -171,6 +171,12 @@ int mmd_llm_step(mmd_ctx* ctx, mmd_stream* s, const void* embeds, int S, void* h
 int mmd_video_heads(mmd_ctx* ctx, const void* hidden, int M, float* out);
 /* lm_head (models/live_llava/video_head_live_llava_qwen.py:155): hidden rows [M, hidden] -> logits [M, vocab] fp32 */
 int mmd_lm_head(mmd_ctx* ctx, const void* hidden, int M, float* logits);
+/* teacher-forced scoring, the lm_loss terms of models/live_llava/video_head_live_llava_qwen.py:155,164-170 before their mean:
+ * per-row negative log-likelihood of labels under lm_head(hidden) without materialising [M,V] logits:
+ * hidden [M,hidden] (device, ctx dtype), labels [M] int64 (device); nll_out [M] fp32 (device, 0 where label == ignore_index),
+ * lse_out [M] fp32 or NULL.  chunk_cols: vocabulary columns per pass, 0 = auto.  Enqueued on the context's stream, no synchronisation.
+ * A label that is neither ignore_index nor in [0, vocab) gives NaN in its row (it is compared with column indices, never used as an address). */
+int mmd_lm_nll(mmd_ctx* ctx, const void* hidden, int M, const int64_t* labels, int64_t ignore_index, int chunk_cols, float* nll_out, float* lse_out);
 /* one fused per-frame step for the streaming loop (test/inference.py:239-244): llm_step + heads at the rows listed in
  * head_rows (host int32[n_rows], e.g. the last token of every frame in a chunk); scores_out host fp32 [n_rows,4]
  * (synchronises the stream). */
@@ -256,6 +262,9 @@ int mmd_prof_reset(mmd_ctx* ctx);
  * 1 generic tile, 2 skinny/split-K, 3 large tile, 4 DMA 128-row tile, 5 skinny slabs, 6 256x256 ring, 8 streaming kernel (32 < M <= 256; SwiGLU only in this form). */
 int mmd_op_gemm(mmd_ctx* ctx, const void* X, const void* W, const void* bias, const void* R, void* Y, int M, int N, int K,
                 int epi, int out_f32, int variant);
+/* raw form for parity tests: the same path over an explicit W [V,K] (device, ctx dtype, row-major) and X [M,K] */
+int mmd_op_lm_nll(mmd_ctx* ctx, const void* X, const void* W, int M, int V, int K, const int64_t* labels, int64_t ignore_index, int chunk_cols,
+                  float* nll_out, float* lse_out);
 /* what the dispatcher chose for the most recent GEMM of this context: out4 = {kernel (0 tile64, 1 tile128, 2 skinny, 3 gemv16, 4 big64,
  * 5 big128, 6 ring256), output tiles, K splits, blocks launched} */
 int mmd_op_gemm_last_plan(mmd_ctx* ctx, int* out4);

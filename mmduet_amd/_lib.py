@@ -83,6 +83,7 @@ _SIGS = {
     'mmd_llm_step': (_I, [_VP, _VP, _VP, _I, _VP]),
     'mmd_video_heads': (_I, [_VP, _VP, _I, _VP]),
     'mmd_lm_head': (_I, [_VP, _VP, _I, _VP]),
+    'mmd_lm_nll': (_I, [_VP, _VP, _I, _VP, _I64, _I, _VP, _VP]),
     'mmd_frame_step': (_I, [_VP, _VP, _VP, _I, _VP, _I, _VP]),
     'mmd_llm_step_multi': (_I, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), _I, _VP, _VP]),
     'mmd_frame_step_multi': (_I, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), _I, _VP, C.POINTER(C.c_int32), _I, C.POINTER(_F), C.POINTER(C.c_int32), _I, _VP, _VP]),
@@ -98,6 +99,7 @@ _SIGS = {
     'mmd_prof_reset': (_I, [_VP]),
     'mmd_op_gemm': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I]),
     'mmd_op_gemm_bench': (_I, [_VP, _I, _I, _I, _I, _I, _I, C.POINTER(_F), _VP, _VP]),
+    'mmd_op_lm_nll': (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _I64, _I, _VP, _VP]),
     'mmd_op_gemm_last_plan': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_gemm_pair': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     'mmd_op_gemm_slabs': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, C.POINTER(_I)]),

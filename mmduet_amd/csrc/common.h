@@ -142,6 +142,12 @@ struct SampleBatch { const int64_t* prev[MMD_ROUND_MAX_SAMPLERS]; int64_t* tok[M
 struct FeedBatch { const int64_t* tok[MMD_ROUND_MAX_SAMPLERS]; int32_t row[MMD_ROUND_MAX_SAMPLERS]; };
 hipError_t launch_sample_batch(const float* logits /*[n, V]*/, int V, const SampleBatch& b, int n, int64_t* toks_out_dev, void* scratch, hipStream_t st);
 size_t sample_batch_scratch_bytes();
+// streaming cross entropy over lm_head logit chunks (mmd_lm_nll; ops.hip): fold chunk `logits` [m, nc] (row stride ld, ld % 4 == 0; vocabulary columns [c0, c0 + nc)) into
+// state [m, 3] = (max, sum exp, label logit) -- `first`: the state starts empty -- through the one-writer partials part [m, lm_nll_splits(m, nc), 3]; then nll / lse from the state
+constexpr int LM_NLL_BLOCKS = 2048, LM_NLL_MAX_SPLITS = 256;          // blocks one chunk's reduce aims at; m * lm_nll_splits(m, nc) <= max(m, LM_NLL_BLOCKS)
+int lm_nll_splits(int m, int nc);
+hipError_t launch_lm_nll_chunk(const float* logits, int64_t ld, int m, int nc, int64_t c0, const int64_t* labels, int first, float* state, float* part, hipStream_t st);
+hipError_t launch_lm_nll_finalize(const float* state, const int64_t* labels, int64_t ignore_index, int m, float* nll, float* lse /* or null */, hipStream_t st);
 hipError_t launch_embed_feed(int dtype, const void* table, const FeedBatch& f, int n, int H, int64_t vocab, void* out, hipStream_t st);
 hipError_t launch_convert(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, hipStream_t st);
 hipError_t launch_copy_rows(int dtype, const void* src, int64_t lds_, void* dst, int64_t ldd, int rows, int cols, hipStream_t st);

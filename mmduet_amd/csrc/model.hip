@@ -107,6 +107,8 @@ struct mmd_ctx {
     hipEvent_t seg_event[8] = {};      // recorded behind a slot's upload: the pinned host slot is rewritten only once that copy has run (steps without a synchronisation may queue up)
     // mmd_round_multi (allocated at its first use): logits of the sampling rows, their gathered hidden rows, the two-stage argmax candidates, the drawn tokens
     float* round_logits = 0; void* round_hidden = 0; void* round_scratch = 0; int64_t* round_toks_dev = 0; int64_t* round_toks_host = 0;
+    // mmd_lm_nll (allocated at its first use): one fp32 logit chunk [rows, chunk columns], the rows' (max, sum exp, label logit) and the one-writer partials of a chunk's reduce
+    float* nll_ws = 0; size_t nll_ws_bytes = 0; float* nll_state = 0; float* nll_part = 0; int nll_rows = 0;
     Prof prof;
 };
 
@@ -1662,6 +1664,72 @@ extern "C" int mmd_lm_head(mmd_ctx* c, const void* hidden, int M, float* logits)
     return gemm(c, hidden, H, c->lm_head, H, nullptr, nullptr, 0, logits, V, M, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p);
 }
 
+// ---- teacher-forced scoring: CrossEntropyLoss(reduction='none') of labels under lm_head(hidden), the [M, V] logits never held --------------------------------
+// (models/live_llava/video_head_live_llava_qwen.py:155,164-170).  Row blocks of at most max_step_tokens rows; inside a row block the vocabulary goes through the
+// fp32 workspace one chunk at a time: the unchanged GEMM writes logits [m, nc], the reduce folds them into the rows' (max, sum exp, label logit), and after the
+// last chunk the finalize kernel writes nll (and lse).  A chunk of W is a row range of the row-major matrix, so `ldw` stays K and the planner sees an ordinary GEMM.
+// The packed copy is fragment-major over the WHOLE matrix: it is handed to the planner only for a chunk that is the whole vocabulary (every M <= 64 call at auto width).
+constexpr size_t LM_NLL_WS_MAX = (size_t)64 << 20;
+static void lm_nll_release(mmd_ctx* c) {
+    dev_free(c, c->nll_ws); dev_free(c, c->nll_state); dev_free(c, c->nll_part);
+    c->nll_ws = c->nll_state = c->nll_part = nullptr; c->nll_ws_bytes = 0; c->nll_rows = 0;
+}
+// the three buffers exist together or not at all: nll_part is allocated last and is what the guard looks at; a failure half way frees and resets all of them
+static int lm_nll_reserve(mmd_ctx* c, size_t ws_bytes, int rows) {
+    if (c->nll_part && c->nll_ws_bytes >= ws_bytes && c->nll_rows >= rows) return MMD_OK;
+    if (c->nll_part) { hipStreamSynchronize(c->stream); ws_bytes = ws_bytes > c->nll_ws_bytes ? ws_bytes : c->nll_ws_bytes; rows = rows > c->nll_rows ? rows : c->nll_rows; }
+    lm_nll_release(c);
+    int rc = dev_alloc(c, (void**)&c->nll_ws, ws_bytes, false);
+    if (!rc) rc = dev_alloc(c, (void**)&c->nll_state, (size_t)rows * 3 * sizeof(float), false);
+    if (!rc) rc = dev_alloc(c, (void**)&c->nll_part, (size_t)(rows > LM_NLL_BLOCKS ? rows : LM_NLL_BLOCKS) * 3 * sizeof(float), false);
+    if (rc) { lm_nll_release(c); return rc; }
+    c->nll_ws_bytes = ws_bytes; c->nll_rows = rows;
+    return MMD_OK;
+}
+static int lm_nll_run(mmd_ctx* c, const void* X, const void* W, const void* Wp, int M, int V, int K, const int64_t* labels, int64_t ignore_index, int chunk_cols,
+                      float* nll_out, float* lse_out) {
+    if (V <= 0 || K <= 0 || chunk_cols < 0) FAIL(c, MMD_EINVAL, "lm_nll: V = %d, K = %d, chunk_cols = %d", V, K, chunk_cols);
+    hipStream_t st = c->stream; const size_t e = es(c);
+    int rows = c->cfg.max_step_tokens < 1 ? 1 : c->cfg.max_step_tokens;
+    if (rows > 32768) rows = 32768;          // (a row is a grid row of the reduce; 256 columns of 32768 rows still fit the workspace)
+    if (rows > M) rows = M;
+    const int64_t vpad = round_up(V, 256);
+    size_t ws_bytes = (size_t)rows * vpad * sizeof(float); if (ws_bytes > LM_NLL_WS_MAX) ws_bytes = LM_NLL_WS_MAX;
+    int64_t forced = 0;
+    if (chunk_cols > 0) {
+        forced = round_up(chunk_cols, 8); if (forced > round_up(V, 8)) forced = round_up(V, 8);
+        const int64_t fit = (int64_t)(ws_bytes / (forced * sizeof(float)));
+        if (fit < 1) FAIL(c, MMD_EINVAL, "lm_nll: a chunk of %lld columns does not fit the %zu-byte workspace", (long long)forced, ws_bytes);
+        if (rows > fit) rows = (int)fit;
+    }
+    int rc = lm_nll_reserve(c, ws_bytes, rows); if (rc) return rc;
+    for (int r0 = 0; r0 < M; r0 += rows) {
+        const int m = M - r0 < rows ? M - r0 : rows;
+        // auto width: the largest multiple of 256 columns this row block's logits fit the workspace with, at most the vocabulary
+        int64_t cw = forced ? forced : (int64_t)(ws_bytes / ((size_t)m * sizeof(float))) / 256 * 256;
+        if (cw > V) cw = V;
+        const int64_t ld = round_up(cw, 8);
+        const void* x = (const char*)X + (size_t)r0 * K * e;
+        for (int64_t n0 = 0; n0 < V; n0 += cw) {
+            const int nc = (int)(V - n0 < cw ? V - n0 : cw);
+            rc = gemm(c, x, K, (const char*)W + (size_t)n0 * K * e, K, nullptr, nullptr, 0, c->nll_ws, ld, m, nc, K, EPI_NONE, /*out_f32*/1, GEMM_AUTO, nc == V ? Wp : nullptr);
+            if (rc) return rc;
+            ProfScope ps(c, MMD_K_OTHER, (double)m * nc * sizeof(float), 0);
+            HIPCHK(c, launch_lm_nll_chunk(c->nll_ws, ld, m, nc, n0, labels + r0, n0 == 0, c->nll_state, c->nll_part, st));
+        }
+        ProfScope ps(c, MMD_K_OTHER, (double)m * 5 * sizeof(float), 0);
+        HIPCHK(c, launch_lm_nll_finalize(c->nll_state, labels + r0, ignore_index, m, nll_out + r0, lse_out ? lse_out + r0 : nullptr, st));
+    }
+    return MMD_OK;
+}
+extern "C" int mmd_lm_nll(mmd_ctx* c, const void* hidden, int M, const int64_t* labels, int64_t ignore_index, int chunk_cols, float* nll_out, float* lse_out) {
+    if (!c || M < 0) return MMD_EINVAL;
+    if (M == 0) return MMD_OK;
+    if (!hidden || !labels || !nll_out) return MMD_EINVAL;
+    NEED_FINAL(c);
+    return lm_nll_run(c, hidden, c->lm_head, c->lm_head_p, M, c->cfg.vocab_size, c->cfg.hidden_size, labels, ignore_index, chunk_cols, nll_out, lse_out);
+}
+
 extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int S, const int32_t* rows_host, int n_rows, float* out_host) {
     NEED_FINAL(c);
     if (n_rows < 0 || n_rows > S) FAIL(c, MMD_EINVAL, "bad head row count");
@@ -1815,6 +1883,20 @@ extern "C" int mmd_op_gemm(mmd_ctx* c, const void* X, const void* W, const void*
     // the model holds every matrix in both layouts (or packed only): give the dispatcher the same choice, variant 0 included
     if (variant == GEMM_AUTO || variant == GEMM_SKINNY || variant == GEMM_BIG || variant == GEMM_RING256 || variant == GEMM_RING256_SPLIT || variant == GEMM_STREAM || variant >= GEMM_RINGX) { int rc = make_packed(c, W, N, K, &Wp); if (rc) return rc; }
     int rc = gemm(c, X, K, W, K, bias, R, NO, Y, NO, M, N, K, epi, out_f32, variant, Wp);
+    if (Wp) { hipStreamSynchronize(c->stream); dev_free(c, Wp); }
+    return rc;
+}
+// mmd_lm_nll's path over an explicit W [V,K] / X [M,K] (the packed copy is made only where the path uses it: bf16, the whole vocabulary in one chunk)
+extern "C" int mmd_op_lm_nll(mmd_ctx* c, const void* X, const void* W, int M, int V, int K, const int64_t* labels, int64_t ignore_index, int chunk_cols,
+                             float* nll_out, float* lse_out) {
+    if (!c || M < 0) return MMD_EINVAL;
+    if (M == 0) return MMD_OK;
+    if (!X || !W || !labels || !nll_out) return MMD_EINVAL;
+    hipSetDevice(c->device);
+    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    void* Wp = nullptr;
+    if (M <= 64 && (chunk_cols == 0 || chunk_cols >= V)) { int rc = make_packed(c, W, V, K, &Wp); if (rc) return rc; }
+    int rc = lm_nll_run(c, X, W, Wp, M, V, K, labels, ignore_index, chunk_cols, nll_out, lse_out);
     if (Wp) { hipStreamSynchronize(c->stream); dev_free(c, Wp); }
     return rc;
 }

@@ -1,6 +1,7 @@
 // ops.hip -- the HBM-bound operators of the path: norms, RoPE + KV append, embedding gather, patch im2col, pooling,
 // response heads, greedy sampling, layout helpers.  wave64 shuffles for reductions, 16-byte vector accesses.
 #include "common.h"
+#include <float.h>
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -814,6 +815,101 @@ hipError_t launch_sample_batch(const float* logits, int V, const SampleBatch& b,
     return hipGetLastError();
 }
 size_t sample_batch_scratch_bytes() { return (size_t)MMD_ROUND_MAX_SAMPLERS * ARGMAX_BLOCKS * (sizeof(float) + sizeof(int)); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// teacher-forced scoring (mmd_lm_nll): CrossEntropyLoss(reduction='none') over lm_head logits that are never held as [M, V]
+// (models/live_llava/video_head_live_llava_qwen.py:155,164-170).  The logits arrive one vocabulary chunk [m, nc] at a time; per row
+// three numbers survive a chunk: the running maximum, the running sum of exp(x - maximum) and the label's logit.
+//   chunk kernel   grid (column splits, rows), like argmax_penalty_multi_kernel: block (s, r) reduces its column slice of row r to a partial state and is the ONLY
+//                  writer of part[r][s];
+//   merge kernel   (after the kernel boundary) one thread per row folds the row's partials, in split order, into state[r];
+//   finalize       lse = max + log(sum), nll = lse - label logit (0 where the label is ignore_index).
+// No atomics and no dependence on block order: the same call gives the same bits.  The label is only ever COMPARED with a column index, never used as an address: a
+// label outside the vocabulary matches no column and leaves the row's label logit at its initial NaN.
+// An empty state is (-FLT_MAX, 0): folding it into anything multiplies its zero sum by exp(-huge) = 0, and no inf - inf can arise from it.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void lse_fold(float& m, float& s, float om, float os) {
+    const float nm = fmaxf(m, om);
+    s = s * expf(m - nm) + os * expf(om - nm);
+    m = nm;
+}
+__global__ __launch_bounds__(256) void lm_nll_chunk_kernel(const float* __restrict__ logits, long long ld, int nc, long long c0, const int64_t* __restrict__ labels,
+                                                           float* __restrict__ part) {
+    __shared__ float sm[4], ss[4], sl[4];
+    const int r = blockIdx.y;
+    const float* row = logits + (long long)r * ld;
+    const int per = (((nc + gridDim.x - 1) / gridDim.x) + 3) & ~3;          // whole 16-byte groups per split
+    const int beg = blockIdx.x * per, end = min(nc, beg + per);
+    const long long rel = (long long)labels[r] - c0;          // the label's column inside this chunk, if it has one
+    float m = -FLT_MAX, s = 0.f, lab = NAN;
+    const int vend = end > beg ? beg + ((end - beg) & ~3) : beg;
+    for (int i = beg + 4 * (int)threadIdx.x; i < vend; i += 4 * 256) {
+        const f32x4_t v = *reinterpret_cast<const f32x4_t*>(row + i);
+        const float vm = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+        if (vm > m) { s *= expf(m - vm); m = vm; }
+        s += (expf(v[0] - m) + expf(v[1] - m)) + (expf(v[2] - m) + expf(v[3] - m));
+        const long long d = rel - i;
+        if (d >= 0 && d < 4) lab = d == 0 ? v[0] : (d == 1 ? v[1] : (d == 2 ? v[2] : v[3]));
+    }
+    for (int i = vend + (int)threadIdx.x; i < end; i += 256) {          // the chunk's last columns when nc is no multiple of 4
+        const float x = row[i];
+        if (x > m) { s *= expf(m - x); m = x; }
+        s += expf(x - m);
+        if (rel == i) lab = x;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64), ol = __shfl_xor(lab, o, 64);
+        lse_fold(m, s, om, os);
+        if (ol == ol) lab = ol;          // at most one lane of the block holds the label's logit
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { sm[w] = m; ss[w] = s; sl[w] = lab; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) { lse_fold(m, s, sm[k], ss[k]); if (sl[k] == sl[k]) lab = sl[k]; }
+        float* p = part + ((long long)r * gridDim.x + blockIdx.x) * 3;
+        p[0] = m; p[1] = s; p[2] = lab;
+    }
+}
+__global__ __launch_bounds__(256) void lm_nll_merge_kernel(const float* __restrict__ part, int splits, int M, int first, float* __restrict__ state) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= M) return;
+    float m = -FLT_MAX, s = 0.f, lab = NAN;
+    if (!first) { m = state[r * 3]; s = state[r * 3 + 1]; lab = state[r * 3 + 2]; }
+    const float* p = part + (long long)r * splits * 3;
+    for (int k = 0; k < splits; ++k) { lse_fold(m, s, p[k * 3], p[k * 3 + 1]); if (p[k * 3 + 2] == p[k * 3 + 2]) lab = p[k * 3 + 2]; }
+    state[r * 3] = m; state[r * 3 + 1] = s; state[r * 3 + 2] = lab;
+}
+__global__ __launch_bounds__(256) void lm_nll_finalize_kernel(const float* __restrict__ state, const int64_t* __restrict__ labels, long long ignore_index, int M,
+                                                              float* __restrict__ nll, float* __restrict__ lse) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= M) return;
+    const float l = state[r * 3] + logf(state[r * 3 + 1]);
+    if (lse) lse[r] = l;
+    nll[r] = labels[r] == ignore_index ? 0.f : l - state[r * 3 + 2];
+}
+// column splits of one chunk: about LM_NLL_BLOCKS blocks over the rows (M = 1: the whole chip reads the one row), at least 1024 columns (one 16-byte load per lane) per block
+int lm_nll_splits(int m, int nc) {
+    int sp = LM_NLL_BLOCKS / (m > 0 ? m : 1);
+    const int by_cols = cdiv(nc, 1024);
+    if (sp > by_cols) sp = by_cols;
+    if (sp > LM_NLL_MAX_SPLITS) sp = LM_NLL_MAX_SPLITS;
+    return sp < 1 ? 1 : sp;
+}
+hipError_t launch_lm_nll_chunk(const float* logits, int64_t ld, int m, int nc, int64_t c0, const int64_t* labels, int first, float* state, float* part, hipStream_t st) {
+    if (m <= 0 || nc <= 0) return hipSuccess;
+    if ((ld & 3) != 0 || ld < nc || ((uintptr_t)logits & 15) != 0) return hipErrorInvalidValue;          // 16-byte loads from every row
+    const int splits = lm_nll_splits(m, nc);
+    hipLaunchKernelGGL(lm_nll_chunk_kernel, dim3(splits, m), dim3(256), 0, st, logits, (long long)ld, nc, (long long)c0, labels, part);
+    hipLaunchKernelGGL(lm_nll_merge_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, part, splits, m, first, state);
+    return hipGetLastError();
+}
+hipError_t launch_lm_nll_finalize(const float* state, const int64_t* labels, int64_t ignore_index, int m, float* nll, float* lse, hipStream_t st) {
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(lm_nll_finalize_kernel, dim3(cdiv(m, 256)), dim3(256), 0, st, state, labels, (long long)ignore_index, m, nll, lse);
+    return hipGetLastError();
+}
 
 // rows of a step that are the embedding of the token a sampler drew last (the feed rows of mmd_round_multi): out[row[r], :] = table[*tok[r], :]
 template <typename T>

@@ -530,11 +530,10 @@ class VideoHeadLiveLlavaQwenForCausalLM:
 
     # ---- forward ----------------------------------------------------------------------------------------------------
     def __call__(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
-                 labels=None, use_cache=None, output_attentions=None, output_hidden_states=None, frames=None,
-                 return_dict=None, **kwargs):
-        """models/live_llava/video_head_live_llava_qwen.py:121-205 (inference branch: labels must be None)."""
-        if labels is not None:
-            raise NotImplementedError('training losses are out of scope of the inference implementation')
+                 labels=None, informative_labels=None, relevance_labels=None, use_cache=None, output_attentions=None,
+                 output_hidden_states=None, frames=None, return_dict=None, **kwargs):
+        """models/live_llava/video_head_live_llava_qwen.py:121-205.  With `labels` (and the two video label tensors) the output carries the reference's
+        lm_loss / video_loss / loss, computed without gradients (teacher-forced scoring); without them the call is what it was."""
         if inputs_embeds is None:
             inputs_embeds = self.joint_embed(input_ids, frames)
         if inputs_embeds.ndim != 3 or inputs_embeds.shape[0] != 1:
@@ -550,11 +549,55 @@ class VideoHeadLiveLlavaQwenForCausalLM:
                 check(lib().mmd_llm_step(self._ctx, arena.h, _ptr(x[s0:s1]), s1 - s0, _ptr(hidden[s0:s1])), self._ctx, 'mmd_llm_step')
             cache = KVCacheHandle(arena, n + S)
         out = VideoHeadCausalLMOutputWithPast(self, hidden, cache)
+        if labels is not None or (informative_labels is not None and relevance_labels is not None):
+            self._score(out, input_ids, labels, informative_labels, relevance_labels)
         if return_dict is False:
             return (out.loss, out.logits, cache)
         return out
 
     forward = __call__
+
+    @torch.no_grad()
+    def _score(self, out, input_ids, labels, informative_labels, relevance_labels):
+        """models/live_llava/video_head_live_llava_qwen.py:163-189: labels arrive already shifted, [1, S], -100 ignored, mean over the counted rows
+        (CrossEntropyLoss() defaults); a missing part of the loss is the float 0."""
+        import torch.nn.functional as F
+        lm_loss = video_loss = 0.
+        if labels is not None:
+            if not (labels != -100).any():
+                if input_ids is None:
+                    raise TypeError('labels without a counted position need input_ids: labels[:, 0] = input_ids[:, 1]')
+                labels[:, 0] = input_ids[:, 1]          # in the caller's tensor, as the reference does (:168-169)
+            lab = labels.to(device=self.device, dtype=torch.long).flatten()
+            lm_loss = self.token_nll(out._hidden, lab).sum() / (lab != -100).sum()
+        if informative_labels is not None and relevance_labels is not None:
+            video_labels = torch.cat([informative_labels, relevance_labels], dim=0).to(device=self.device, dtype=torch.long)
+            video_logits = torch.cat([out.informative_logits, out.relevance_logits], dim=0)
+            if not (video_labels != -100).any():
+                video_labels[:, 0] = 0
+            video_loss = F.cross_entropy(video_logits.flatten(0, 1), video_labels.flatten())
+        out.lm_loss, out.video_loss = lm_loss, video_loss
+        out.loss = lm_loss * self.lm_loss_weight + video_loss * self.video_loss_weight
+
+    def token_nll(self, hidden_rows: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100, return_lse: bool = False, chunk_cols: int = 0):
+        """Per-row negative log-likelihood of `labels` [M] under lm_head(hidden_rows [M,H]) -> fp32 [M] on the device, 0 where the label is `ignore_index`
+        (CrossEntropyLoss(reduction='none')); with return_lse also logsumexp of every row's logits.  The [M, vocab] logits are never held: the vocabulary streams
+        through a workspace of at most 64 MiB (mmd_lm_nll); chunk_cols forces the columns per pass (0 = auto).  A label outside [0, vocab) raises, as torch's loss does."""
+        M = hidden_rows.shape[0]
+        hidden_rows = hidden_rows.to(device=self.device, dtype=self.dtype).contiguous()
+        labels = labels.to(device=self.device, dtype=torch.long).contiguous()
+        if hidden_rows.ndim != 2 or hidden_rows.shape[1] != self.config.hidden_size or labels.shape != (M,):
+            raise ValueError(f'token_nll takes hidden rows [M, {self.config.hidden_size}] and labels [M], got {tuple(hidden_rows.shape)} and {tuple(labels.shape)}')
+        bad = (labels != ignore_index) & ((labels < 0) | (labels >= self.config.vocab_size))
+        if bad.any():
+            raise IndexError(f'Target {int(labels[bad][0])} is out of bounds.')
+        nll = torch.empty(M, dtype=torch.float32, device=self.device)
+        lse = torch.empty(M, dtype=torch.float32, device=self.device) if return_lse else None
+        if M:
+            with self._lock:
+                self._bind_stream()
+                check(lib().mmd_lm_nll(self._ctx, _ptr(hidden_rows), M, _ptr(labels), int(ignore_index), int(chunk_cols), _ptr(nll), _ptr(lse)), self._ctx, 'mmd_lm_nll')
+        return (nll, lse) if return_lse else nll
 
     def lm_head(self, hidden_rows: torch.Tensor):
         M = hidden_rows.shape[0]
