@@ -29,6 +29,7 @@ extern "C" {
 #define MMD_ENOENT (-2)
 #define MMD_ERANGE (-34)
 #define MMD_EHIP (-5)
+#define MMD_EDOM (-33)         /* a NaN among the logits a token was to be drawn from */
 
 typedef enum { MMD_F32 = 0, MMD_BF16 = 1 } mmd_dtype;
 /* storage of the decoder's linear-layer weights (q/k/v/o/gate/up/down): MMD_W_FP8_E4M3 = OCP e4m3fn with one fp32 scale per output
@@ -216,6 +217,14 @@ int mmd_sampler_create(mmd_ctx* ctx, mmd_sampler** out);
 void mmd_sampler_destroy(mmd_sampler* sp);                /* before mmd_destroy of its context */
 int mmd_sampler_begin(mmd_sampler* sp, int64_t eos_id, float rep_penalty, const int64_t* prev_ids_host, int n_prev, int max_new);
 int mmd_sampler_prev_len(const mmd_sampler* sp);          /* entries of the penalty list that count */
+/* Sampling instead of arg-max for this sampler (DESIGN.md "Sampling": scores pen(l) / T, top-k and top-p as thresholds that keep whole tie classes, an index-order inverse
+ * CDF over fixed-point masses, the random word from Philox4x32-10 keyed by `seed` at counter (offset, lane)).  temperature <= 0 switches back to arg-max; top_k 0 (or >= vocab)
+ * and top_p 1 are off.  Called after mmd_sampler_begin or at any response boundary; the offset -- tokens drawn since the seed was set -- restarts at 0 only when the seed changes.
+ * The lane is the sampler's id within its context (mmd_sampler_lane), so a stream's tokens do not depend on which other streams share a round.  In mmd_round_multi the sampling
+ * segments of such samplers go through the sampling chain, the others keep the arg-max; a round may mix both.  A NaN among a row's logits fails the round with MMD_EDOM. */
+int mmd_sampler_set_sampling(mmd_sampler* sp, float temperature, int top_k, float top_p, uint64_t seed);
+int mmd_sampler_lane(const mmd_sampler* sp);
+int64_t mmd_sampler_offset(const mmd_sampler* sp);        /* tokens drawn since the seed was set */
 int mmd_round_multi(mmd_ctx* ctx, mmd_stream* const* streams, const int32_t* seg_rows, int n_segs, const void* const* seg_embeds, mmd_sampler* const* samplers,
                     const int32_t* seg_flags, const int32_t* head_rows, int n_head_rows, float* heads_out_host, int64_t* tokens_out_host);
 
@@ -225,6 +234,13 @@ int mmd_round_multi(mmd_ctx* ctx, mmd_stream* const* streams, const int32_t* seg
  * to out_ids but neither fed back nor added to the list.  out_ids_host int64[max_new]; n_out = tokens written. */
 int mmd_greedy_generate(mmd_ctx* ctx, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty,
                         int64_t* prev_ids_host, int* n_prev, int prev_cap, int64_t* out_ids_host, int max_new, int* n_out);
+
+/* the sampled sibling of mmd_greedy_generate (what HF `generate(do_sample=True)` does for the reference class, models/live_llava/video_head_live_llava_qwen.py:207-242):
+ * the same loop and decode step with the sampling chain in the arg-max's place and a captured step of its own.  Draw i uses Philox offset *offset_inout + i and the lane set by
+ * mmd_set_sample_lane (default 0); *offset_inout advances by the tokens drawn.  max_new == 0 enqueues nothing.  MMD_EDOM: a NaN among the logits (n_out tokens were drawn before). */
+int mmd_sample_generate(mmd_ctx* ctx, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
+                        float temperature, int top_k, float top_p, uint64_t seed, uint64_t* offset_inout, int64_t* out_ids_host, int max_new, int* n_out);
+int mmd_set_sample_lane(mmd_ctx* ctx, int lane);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------------------------------------ */
 /* The reference shards videos over N manually launched processes (--start_idx/--end_idx, test/inference.py:337) and has no
@@ -285,6 +301,11 @@ int mmd_op_gemm_w8(mmd_ctx* ctx, const void* X, const void* Wq, const uint8_t* q
 /* micro-benchmark of one GEMM shape (HIP events on the context's stream); avg ms per call incl. any split-K reduce.  X [M,K] / W [N,K]
  * (device, ctx dtype) supply the operand VALUES (random data: operand bits set the chip's clock); NULL = a constant fill */
 int mmd_op_gemm_bench(mmd_ctx* ctx, int M, int N, int K, int epi, int variant, int iters, float* avg_ms_out, const void* X, const void* W);
+/* the sampling chain on n <= 4096 rows of fp32 logits [n, V] (V <= 2^18), one set of parameters, row i on lane i; prev_ids_dev [n_prev] int64 is the penalty list of every row
+ * (rep_penalty <= 0: none).  r_host: NULL = Philox words from (seed, offset, lane), else uint64[n] explicit random words (host).  tokens_out int64[n] (-1: the row holds a NaN),
+ * info_out float[n,4] = (tau, kept count, kept mass / total mass, NaN flag), scores_out [n,V] or NULL = the scores z = pen(l) / T.  Synchronises the stream. */
+int mmd_op_sample(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                  uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out);
 int mmd_op_rmsnorm(mmd_ctx* ctx, const void* x, const void* w, void* y, int M, int H, float eps);
 int mmd_op_layernorm(mmd_ctx* ctx, const void* x, const void* w, const void* b, void* y, int M, int H, float eps);
 /* the autocast tower's residual step (models/modeling_live.py:28: `hidden (fp32) + sublayer_out (fp16)` promotes, LayerNorm returns fp32, the next linear casts to

@@ -31,6 +31,16 @@ def main(argv=None):
     from .distributed import init_distributed, shard_indices, shard_shape, gather_scores, gather_responses
     from .prefetch import ClipPrefetcher, pin
     args = parse_args('test', argv)
+    # sampled responses: flags of this CLI alone (the arguments dataclass keeps the reference's schema and skips what it does not know); the drivers read them off `args`
+    import argparse
+    sp = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    sp.add_argument('--do_sample', nargs='?', const=True, default=False, type=lambda v: str(v).lower() in ('1', 'true', 'yes'))
+    sp.add_argument('--temperature', type=float, default=1.0)
+    sp.add_argument('--top_k', type=int, default=0)
+    sp.add_argument('--top_p', type=float, default=1.0)
+    sp.add_argument('--sampling_seed', type=int, default=0)
+    for k, v in vars(sp.parse_known_args(sys.argv[1:] if argv is None else argv)[0]).items():
+        setattr(args, k, v)
     rank, world, local = init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local)

@@ -91,8 +91,13 @@ _SIGS = {
     'mmd_sampler_destroy': (None, [_VP]),
     'mmd_sampler_begin': (_I, [_VP, _I64, _F, _VP, _I, _I]),
     'mmd_sampler_prev_len': (_I, [_VP]),
+    'mmd_sampler_set_sampling': (_I, [_VP, _F, _I, _F, C.c_uint64]),
+    'mmd_sampler_lane': (_I, [_VP]),
+    'mmd_sampler_offset': (_I64, [_VP]),
     'mmd_round_multi': (_I, [_VP, C.POINTER(_VP), C.POINTER(C.c_int32), _I, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.POINTER(_F), C.POINTER(_I64)]),
     'mmd_greedy_generate': (_I, [_VP, _VP, _VP, _I, _I64, _F, _VP, C.POINTER(_I), _I, _VP, _I, C.POINTER(_I)]),
+    'mmd_sample_generate': (_I, [_VP, _VP, _VP, _I, _I64, _F, _VP, C.POINTER(_I), _I, _F, _I, _F, C.c_uint64, C.POINTER(C.c_uint64), _VP, _I, C.POINTER(_I)]),
+    'mmd_set_sample_lane': (_I, [_VP, _I]),
     'mmd_prof_enable': (_I, [_VP, _I]),
     'mmd_prof_set_stride': (_I, [_VP, _I]),
     'mmd_prof_read': (_I, [_VP, _VP, _VP, _VP, _VP]),
@@ -105,6 +110,7 @@ _SIGS = {
     'mmd_op_gemm_slabs': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, C.POINTER(_I)]),
     'mmd_op_quantize_fp8': (_I, [_VP, _VP, _I, _I, _VP, _VP]),
     'mmd_op_gemm_w8': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I]),
+    'mmd_op_sample': (_I, [_VP, _VP, _I, _I, _VP, _I, _F, _F, _I, _F, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
     'mmd_op_rmsnorm': (_I, [_VP, _VP, _VP, _VP, _I, _I, _F]),
     'mmd_op_layernorm': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _F]),
     'mmd_op_resid32_layernorm': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _F]),
@@ -139,8 +145,13 @@ def lib():
     return L
 
 
+MMD_EDOM = -33
+
+
 def check(rc, ctx=None, what=''):
     if rc == 0:
         return
     msg = lib().mmd_last_error(ctx)
+    if rc == MMD_EDOM:          # a NaN among the logits a token was to be drawn from: never turned into an index
+        raise ValueError(f'{what or "libmmduet_hip"}: {msg.decode() if msg else "NaN in the logits"}')
     raise MmduetError(f'{what or "libmmduet_hip"} failed ({rc}): {msg.decode() if msg else "?"}')

@@ -142,6 +142,18 @@ struct SampleBatch { const int64_t* prev[MMD_ROUND_MAX_SAMPLERS]; int64_t* tok[M
 struct FeedBatch { const int64_t* tok[MMD_ROUND_MAX_SAMPLERS]; int32_t row[MMD_ROUND_MAX_SAMPLERS]; };
 hipError_t launch_sample_batch(const float* logits /*[n, V]*/, int V, const SampleBatch& b, int n, int64_t* toks_out_dev, void* scratch, hipStream_t st);
 size_t sample_batch_scratch_bytes();
+// temperature / top-k / top-p sampling (sample.hip).  One SampleRow per logits row, in DEVICE memory: everything a step's kernels need to know about the row, so a captured
+// decode step is replayed unchanged when the parameters change.  n_prev_ptr (the captured step: &StepState::n_prev) overrides n_prev; `advance`: the draw kernel adds 1 to offset.
+struct SampleRow {
+    const int64_t* prev; const int* n_prev_ptr; int64_t* tok; int64_t* append;
+    unsigned long long offset;
+    int n_prev, prev_cap; float penalty, temperature; int top_k; float top_p;
+    uint32_t seed_lo, seed_hi, lane, advance;
+};
+constexpr int SMP_MAX_SLICES = 64;
+size_t sample_topkp_scratch_bytes(int V, int n, bool own_scores);          // n <= MMD_ROUND_MAX_SAMPLERS rows per launch; own_scores: the z rows live in the scratch
+hipError_t launch_sample_batch_topkp(const float* logits /*[n, V]*/, int V, int n, SampleRow* rows_dev, bool any_k, bool any_p, const unsigned long long* r_words_dev /* or null: Philox */,
+                                     int64_t* toks_out_dev, float* info_out_dev /* [n,4] or null */, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st);
 // streaming cross entropy over lm_head logit chunks (mmd_lm_nll; ops.hip): fold chunk `logits` [m, nc] (row stride ld, ld % 4 == 0; vocabulary columns [c0, c0 + nc)) into
 // state [m, 3] = (max, sum exp, label logit) -- `first`: the state starts empty -- through the one-writer partials part [m, lm_nll_splits(m, nc), 3]; then nll / lse from the state
 constexpr int LM_NLL_BLOCKS = 2048, LM_NLL_MAX_SPLITS = 256;          // blocks one chunk's reduce aims at; m * lm_nll_splits(m, nc) <= max(m, LM_NLL_BLOCKS)

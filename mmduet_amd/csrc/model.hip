@@ -109,6 +109,11 @@ struct mmd_ctx {
     float* round_logits = 0; void* round_hidden = 0; void* round_scratch = 0; int64_t* round_toks_dev = 0; int64_t* round_toks_host = 0;
     // mmd_lm_nll (allocated at its first use): one fp32 logit chunk [rows, chunk columns], the rows' (max, sum exp, label logit) and the one-writer partials of a chunk's reduce
     float* nll_ws = 0; size_t nll_ws_bytes = 0; float* nll_state = 0; float* nll_part = 0; int nll_rows = 0;
+    // sampled decoding (allocated at its first use): row descriptors on the device ([0] mmd_sample_generate's, [1..] a round's) with their pinned staging, the chain's scratch
+    // for MMD_ROUND_MAX_SAMPLERS rows, and the captured sampled decode step -- an instance of its own beside dec_graph, re-captured only when a filter is switched on or off
+    SampleRow* samp_rows_dev = nullptr; SampleRow* samp_rows_host = nullptr; void* samp_scratch = nullptr;
+    hipGraphExec_t sdec_graph = nullptr; hipGraph_t sdec_graph_src = nullptr; int sdec_pen = 0, sdec_sel = 0; int64_t sdec_eos = 0;
+    uint32_t sample_lane = 0; uint32_t n_samplers = 0;
     Prof prof;
 };
 
@@ -279,6 +284,9 @@ extern "C" void mmd_destroy(mmd_ctx* c) {
     if (c->step_host) hipHostFree(c->step_host);
     if (c->seg_host) hipHostFree(c->seg_host);
     if (c->round_toks_host) hipHostFree(c->round_toks_host);
+    if (c->samp_rows_host) hipHostFree(c->samp_rows_host);
+    if (c->sdec_graph) hipGraphExecDestroy(c->sdec_graph);
+    if (c->sdec_graph_src) hipGraphDestroy(c->sdec_graph_src);
     for (auto& ev : c->seg_event) if (ev) hipEventDestroy(ev);
     if (c->dec_graph) hipGraphExecDestroy(c->dec_graph);
     if (c->dec_graph_src) hipGraphDestroy(c->dec_graph_src);
@@ -1527,14 +1535,32 @@ struct mmd_sampler {
     int64_t* tok_dev = nullptr;                  // the token drawn last (fed back by the next round's embedding gather)
     int64_t* prev_dev = nullptr; int prev_cap = 0; int n_prev = 0;          // repetition-penalty list (device) and the number of entries that count
     int64_t eos = -1; float penalty = 0.f;
+    // sampling (mmd_sampler_set_sampling): off = arg-max.  `offset` counts the tokens drawn since the seed was set; `lane` is the sampler's id within its context
+    bool sampling = false, seeded = false; float temperature = 1.f, top_p = 1.f; int top_k = 0; uint64_t seed = 0, offset = 0; uint32_t lane = 0;
 };
+
+static void drop_sample_graph(mmd_ctx* c) {
+    if (c->sdec_graph) { hipGraphExecDestroy(c->sdec_graph); c->sdec_graph = nullptr; }
+    if (c->sdec_graph_src) { hipGraphDestroy(c->sdec_graph_src); c->sdec_graph_src = nullptr; }
+}
+static int sample_reserve(mmd_ctx* c) {
+    if (c->samp_scratch) return MMD_OK;
+    int rc = dev_alloc(c, (void**)&c->samp_rows_dev, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(SampleRow)); if (rc) return rc;
+    HIPCHK(c, hipHostMalloc((void**)&c->samp_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(SampleRow)));
+    return dev_alloc(c, &c->samp_scratch, sample_topkp_scratch_bytes(c->cfg.vocab_size, MMD_ROUND_MAX_SAMPLERS, true), false);
+}
+static int check_sampling(mmd_ctx* c, float temperature, int top_k, float top_p) {
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1 (got %g, %d, %g)", temperature, top_k, top_p);
+    if (c->cfg.vocab_size > (1 << 18)) FAIL(c, MMD_ERANGE, "sampling handles vocabularies up to 2^18 entries");
+    return MMD_OK;
+}
 
 extern "C" int mmd_sampler_create(mmd_ctx* c, mmd_sampler** out) {
     NEED_FINAL(c);
     if (!out) FAIL(c, MMD_EINVAL, "null out pointer");
     mmd_sampler* sp = new (std::nothrow) mmd_sampler();
     if (!sp) FAIL(c, MMD_ENOMEM, "out of host memory");
-    sp->ctx = c;
+    sp->ctx = c; sp->lane = c->n_samplers++;
     if (hipMalloc((void**)&sp->tok_dev, 64) != hipSuccess) { delete sp; FAIL(c, MMD_ENOMEM, "hipMalloc of a sampler failed"); }
     hipMemsetAsync(sp->tok_dev, 0, 64, c->stream);
     *out = sp;
@@ -1569,6 +1595,17 @@ extern "C" int mmd_sampler_begin(mmd_sampler* sp, int64_t eos_id, float rep_pena
     return MMD_OK;
 }
 extern "C" int mmd_sampler_prev_len(const mmd_sampler* sp) { return sp ? sp->n_prev : MMD_EINVAL; }
+extern "C" int mmd_sampler_set_sampling(mmd_sampler* sp, float temperature, int top_k, float top_p, uint64_t seed) {
+    if (!sp) return MMD_EINVAL;
+    mmd_ctx* c = sp->ctx;
+    if (!(temperature > 0.f)) { sp->sampling = false; return MMD_OK; }
+    int rc = check_sampling(c, temperature, top_k, top_p); if (rc) return rc;
+    if (!sp->seeded || seed != sp->seed) { sp->seed = seed; sp->offset = 0; sp->seeded = true; }
+    sp->sampling = true; sp->temperature = temperature; sp->top_k = top_k; sp->top_p = top_p;
+    return MMD_OK;
+}
+extern "C" int mmd_sampler_lane(const mmd_sampler* sp) { return sp ? (int)sp->lane : MMD_EINVAL; }
+extern "C" int64_t mmd_sampler_offset(const mmd_sampler* sp) { return sp ? (int64_t)sp->offset : MMD_EINVAL; }
 
 extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int32_t* seg_rows, int n_segs, const void* const* seg_embeds, mmd_sampler* const* samplers,
                                const int32_t* seg_flags, const int32_t* head_rows, int n_head_rows, float* heads_out_host, int64_t* tokens_out_host) {
@@ -1582,11 +1619,28 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
     hipStream_t st = c->stream; const int H = c->cfg.hidden_size, V = c->cfg.vocab_size; const size_t e = es(c);
     // the round's input rows: embeddings handed in per segment, or -- FEED -- the embedding of the token the segment's sampler drew in the round before
     FeedBatch feed; int n_feed = 0;
+    // sampling rows: the arg-max ones first, the ones whose sampler has sampling on behind them (two passes over the segments), so each kind is one block of logits rows
     SampleBatch sb; int n_sample = 0; int32_t sample_row[MMD_ROUND_MAX_SAMPLERS]; int sample_seg[MMD_ROUND_MAX_SAMPLERS];
+    int n_greedy = 0; bool any_k = false, any_p = false;
+    for (int pass = 0; pass < 2; ++pass)
     for (int j = 0; j < n_segs; ++j) {
         const int fl = seg_flags ? seg_flags[j] : 0;
         mmd_sampler* sp = samplers ? samplers[j] : nullptr;
         if ((fl & (MMD_SEG_FEED | MMD_SEG_SAMPLE)) && (!sp || sp->ctx != c)) FAIL(c, MMD_EINVAL, "segment %d feeds / samples without a sampler of this context", j);
+        if (pass == 1) {
+            if (!(fl & MMD_SEG_SAMPLE) || !sp->sampling) continue;
+            if (n_sample >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d sampling segments", MMD_ROUND_MAX_SAMPLERS);
+            for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
+            if (n_sample == n_greedy) { rc = sample_reserve(c); if (rc) return rc; }
+            const bool pen = sp->penalty > 0.f;
+            SampleRow& r = c->samp_rows_host[1 + n_sample - n_greedy];
+            r.prev = sp->prev_dev; r.n_prev_ptr = nullptr; r.tok = sp->tok_dev; r.append = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
+            r.offset = sp->offset; r.n_prev = pen ? sp->n_prev : 0; r.prev_cap = sp->prev_cap; r.penalty = pen ? sp->penalty : 1.f; r.temperature = sp->temperature;
+            r.top_k = sp->top_k; r.top_p = sp->top_p; r.seed_lo = (uint32_t)sp->seed; r.seed_hi = (uint32_t)(sp->seed >> 32); r.lane = sp->lane; r.advance = 0;
+            any_k |= sp->top_k > 0 && sp->top_k < V; any_p |= sp->top_p < 1.f;
+            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample;
+            continue;
+        }
         if (fl & MMD_SEG_FEED) {
             if (segs[j].rows != 1) FAIL(c, MMD_EINVAL, "a feed segment is one row (segment %d has %d)", j, segs[j].rows);
             if (n_feed >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d feed segments", MMD_ROUND_MAX_SAMPLERS);
@@ -1596,13 +1650,13 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             void* dst = (char*)c->l_h + (size_t)segs[j].row0 * H * e;
             if (seg_embeds[j] != dst) HIPCHK(c, hipMemcpyAsync(dst, seg_embeds[j], (size_t)segs[j].rows * H * e, hipMemcpyDeviceToDevice, st));
         }
-        if (fl & MMD_SEG_SAMPLE) {
+        if ((fl & MMD_SEG_SAMPLE) && !sp->sampling) {
             if (n_sample >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d sampling segments", MMD_ROUND_MAX_SAMPLERS);
             for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
             const bool pen = sp->penalty > 0.f;
             sb.prev[n_sample] = sp->prev_dev; sb.n_prev[n_sample] = pen ? sp->n_prev : 0; sb.penalty[n_sample] = pen ? sp->penalty : 1.f;
             sb.tok[n_sample] = sp->tok_dev; sb.append[n_sample] = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
-            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample;
+            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample; n_greedy = n_sample;
         }
     }
     if (n_sample && !tokens_out_host) FAIL(c, MMD_EINVAL, "sampling segments need tokens_out_host");
@@ -1629,7 +1683,14 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             rows = c->round_hidden;
         }
         rc = gemm(c, rows, H, c->lm_head, H, nullptr, nullptr, 0, c->round_logits, V, n_sample, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-        { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_sample_batch(c->round_logits, V, sb, n_sample, c->round_toks_dev, c->round_scratch, st)); }
+        if (n_greedy) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_sample_batch(c->round_logits, V, sb, n_greedy, c->round_toks_dev, c->round_scratch, st)); }
+        if (n_sample > n_greedy) {
+            const int ns = n_sample - n_greedy;
+            HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev + 1, c->samp_rows_host + 1, sizeof(SampleRow) * ns, hipMemcpyHostToDevice, st));          // (the round's synchronisation frees the staging)
+            ProfScope ps(c, MMD_K_OTHER, 0, 0);
+            HIPCHK(c, launch_sample_batch_topkp(c->round_logits + (size_t)n_greedy * V, V, ns, c->samp_rows_dev + 1, any_k, any_p, nullptr, c->round_toks_dev + n_greedy, nullptr, nullptr,
+                                                c->samp_scratch, st));
+        }
         HIPCHK(c, hipMemcpyAsync(c->round_toks_host, c->round_toks_dev, sizeof(int64_t) * n_sample, hipMemcpyDeviceToHost, st));
     }
     if (n_head_rows) {
@@ -1646,6 +1707,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         const int64_t tok = c->round_toks_host[i];
         mmd_sampler* sp = samplers[sample_seg[i]];
         tokens_out_host[sample_seg[i]] = tok;
+        if (i >= n_greedy) { sp->offset += 1; if (tok < 0) FAIL(c, MMD_EDOM, "NaN in the logits of segment %d: no token drawn", sample_seg[i]); }
         if (sp->penalty > 0.f && tok != sp->eos && sp->n_prev < sp->prev_cap) sp->n_prev += 1;          // (EOS is neither fed back nor penalised: models/modeling_live.py:66-72)
     }
     return MMD_OK;
@@ -1752,12 +1814,19 @@ extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int
 
 // one decode step (feed the previously sampled token, sample the next) enqueued on the stream; `dyn` selects the
 // graph-capturable form that reads position / arena / penalty-list length from device state
-static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn) {
+// `samp`: the sampled sibling (mmd_sample_generate) -- the sampling chain over row descriptor 0 takes the arg-max's place; its penalty list always grows on the device
+struct SampleCall { bool any_k, any_p; };
+static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const SampleCall* samp = nullptr) {
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size;
     // the next token's embedding is gathered straight into the residual-stream buffer (llm_step_segs skips its copy when embeds == l_h)
     HIPCHK(c, launch_embed(g.dtype, c->embed, c->tok_dev, 1, H, g.vocab_size, c->l_h, st));
     int rc = llm_step_impl(c, s, c->l_h, 1, nullptr, dyn); if (rc) return rc;
     rc = gemm(c, c->l_hid, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, g.vocab_size, 1, g.vocab_size, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
+    if (samp) {
+        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, g.vocab_size, 1, c->samp_rows_dev, samp->any_k, samp->any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st));
+        HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st));
+        return MMD_OK;
+    }
     HIPCHK(c, launch_argmax_penalty(c->logits_ws, g.vocab_size, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, dyn, c->argmax_scratch));
     if (dyn) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st));
     return MMD_OK;
@@ -1778,6 +1847,7 @@ extern "C" int mmd_greedy_generate(mmd_ctx* c, mmd_stream* s, const void* prompt
         HIPCHK(c, hipStreamSynchronize(st));
         if (c->dec_graph) { hipGraphExecDestroy(c->dec_graph); c->dec_graph = nullptr; }
         if (c->dec_graph_src) { hipGraphDestroy(c->dec_graph_src); c->dec_graph_src = nullptr; }
+        drop_sample_graph(c);
         dev_free(c, c->prev_dev); c->prev_dev = nullptr; c->prev_cap = 0;
         int rc0 = dev_alloc(c, (void**)&c->prev_dev, (size_t)ncap * sizeof(int64_t)); if (rc0) return rc0;
         c->prev_cap = ncap;
@@ -1854,6 +1924,145 @@ extern "C" int mmd_greedy_generate(mmd_ctx* c, mmd_stream* s, const void* prompt
     *n_out = produced;
     if (pen && n_prev) *n_prev = np;
     return MMD_OK;
+}
+
+// ---- sampled decoding: the sibling of mmd_greedy_generate ------------------------------------------------------------------------------------------------
+// Same loop, same decode step (decode_step_enqueue / llm_step_impl); the sampling chain of sample.hip stands where the arg-max stood.  Everything the chain needs per step
+// is in row descriptor 0 on the device: the penalty-list length is read through &step_dev->n_prev and grown by advance_state_kernel, the Philox offset is advanced by the
+// draw kernel, so the captured step is replayed as it is for any temperature / top_k / top_p / seed.  Draw i of the call uses offset *offset_inout + i; on return
+// *offset_inout has advanced by the tokens drawn (EOS included).
+extern "C" int mmd_set_sample_lane(mmd_ctx* c, int lane) { if (!c || lane < 0) return MMD_EINVAL; c->sample_lane = (uint32_t)lane; return MMD_OK; }
+
+extern "C" int mmd_sample_generate(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
+                                   float temperature, int top_k, float top_p, uint64_t seed, uint64_t* offset_inout, int64_t* out_ids_host, int max_new, int* n_out) {
+    NEED_FINAL(c);
+    if (!n_out || max_new < 0 || (max_new > 0 && !out_ids_host) || !offset_inout) FAIL(c, MMD_EINVAL, "bad generate arguments");
+    *n_out = 0;
+    if (max_new == 0) return MMD_OK;          // nothing asked for: nothing is enqueued, the stream is not extended
+    if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
+    int rc = check_sampling(c, temperature, top_k, top_p); if (rc) return rc;
+    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size, V = g.vocab_size; const size_t e = es(c);
+    const bool pen = rep_penalty > 0.f;
+    int np = (pen && n_prev) ? *n_prev : 0;
+    if (pen && np + max_new > c->prev_cap) {          // (as in mmd_greedy_generate: the list has no cap; both captured steps hold the old pointer)
+        int ncap = c->prev_cap > 0 ? c->prev_cap : 16384;
+        while (ncap < np + max_new) ncap *= 2;
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (c->dec_graph) { hipGraphExecDestroy(c->dec_graph); c->dec_graph = nullptr; }
+        if (c->dec_graph_src) { hipGraphDestroy(c->dec_graph_src); c->dec_graph_src = nullptr; }
+        drop_sample_graph(c);
+        dev_free(c, c->prev_dev); c->prev_dev = nullptr; c->prev_cap = 0;
+        rc = dev_alloc(c, (void**)&c->prev_dev, (size_t)ncap * sizeof(int64_t)); if (rc) return rc;
+        c->prev_cap = ncap;
+    }
+    rc = sample_reserve(c); if (rc) return rc;
+    if (np > 0) HIPCHK(c, hipMemcpyAsync(c->prev_dev, prev_ids_host, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
+    const SampleCall call{top_k > 0 && top_k < V, top_p < 1.f};
+    uint64_t offset = *offset_inout;
+    auto post_row = [&](bool dynamic) -> int {          // (every earlier upload from this staging slot has been waited for: a token read lies in between)
+        SampleRow& r = c->samp_rows_host[0];
+        r.prev = c->prev_dev; r.n_prev_ptr = dynamic ? &c->step_dev->n_prev : nullptr; r.tok = c->tok_dev; r.append = nullptr; r.offset = offset;
+        r.n_prev = pen ? (np < c->prev_cap ? np : c->prev_cap) : 0; r.prev_cap = c->prev_cap; r.penalty = pen ? rep_penalty : 1.f; r.temperature = temperature; r.top_k = top_k; r.top_p = top_p;
+        r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32); r.lane = c->sample_lane; r.advance = 1;
+        HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
+        return MMD_OK;
+    };
+    int produced = 0;
+    auto read_token = [&](int64_t* tok) -> int {
+        HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        *tok = c->tok_host[0]; ++offset; *offset_inout = offset;
+        if (*tok < 0) FAIL(c, MMD_EDOM, "NaN in the logits: no token drawn");
+        return MMD_OK;
+    };
+    // step 0: the prompt (eager)
+    rc = llm_step_impl(c, s, prompt_embeds, S, nullptr, nullptr); if (rc) return rc;
+    {
+        const void* last = (const char*)c->l_hid + (size_t)(S - 1) * H * e;
+        rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, V, 1, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
+        rc = post_row(false); if (rc) return rc;
+        ProfScope ps(c, MMD_K_OTHER, 0, 0);
+        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st));
+    }
+    int64_t tok = 0;
+    rc = read_token(&tok); if (rc) return rc;
+    out_ids_host[produced++] = tok; *n_out = produced;
+    bool stop = tok == eos_id;
+    if (!stop && pen) {
+        if (np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
+        ++np;
+    }
+    if (!stop && max_new > 1) {
+        const bool can_graph = !c->no_graph && !c->no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr && g.hidden_size <= 4096 && g.head_dim == 128;
+        if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
+        StepState* hs = c->step_host;
+        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->pad = 0;
+        HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
+        rc = post_row(true); if (rc) return rc;
+        const int sel = (call.any_k ? 1 : 0) | (call.any_p ? 2 : 0);
+        if (can_graph && (!c->sdec_graph || c->sdec_pen != (pen ? 1 : 0) || c->sdec_eos != eos_id || c->sdec_sel != sel)) {
+            drop_sample_graph(c);
+            HIPCHK(c, hipStreamSynchronize(st));
+            c->stream = c->own_stream;          // (capture on the context's own stream, launch on the caller's: as the greedy step)
+            hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
+            if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
+            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, &call);
+            hipError_t ce = hipStreamEndCapture(c->own_stream, &c->sdec_graph_src);
+            c->stream = st;
+            if (rc) { if (c->sdec_graph_src) { hipGraphDestroy(c->sdec_graph_src); c->sdec_graph_src = nullptr; } return rc; }
+            HIPCHK(c, ce);
+            HIPCHK(c, hipGraphInstantiate(&c->sdec_graph, c->sdec_graph_src, nullptr, nullptr, 0));
+            c->sdec_pen = pen ? 1 : 0; c->sdec_eos = eos_id; c->sdec_sel = sel;
+        }
+        for (int i = 1; i < max_new; ++i) {
+            if (can_graph) { HIPCHK(c, hipGraphLaunch(c->sdec_graph, st)); s->len += 1; }
+            else { rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, &call); if (rc) return rc; }
+            rc = read_token(&tok); if (rc) return rc;
+            out_ids_host[produced++] = tok; *n_out = produced;
+            if (tok == eos_id) break;
+            if (pen) { if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok; ++np; }
+        }
+    }
+    if (pen && n_prev) *n_prev = np;
+    return MMD_OK;
+}
+
+// raw operator: n rows of logits through the sampling chain, one set of parameters, row i on lane i (MMD_ROUND_MAX_SAMPLERS rows per launch)
+extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                             uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out) {
+    if (!c) return MMD_EINVAL;
+    hipSetDevice(c->device);
+    if (!logits || !tokens_out || !info_out || n < 1 || n > 4096 || V < 1 || V > (1 << 18) || n_prev < 0 || (n_prev > 0 && !prev_ids_dev)) FAIL(c, MMD_EINVAL, "bad mmd_op_sample arguments");
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1");
+    hipStream_t st = c->stream;
+    const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS;
+    std::vector<SampleRow> rows((size_t)n);
+    const bool pen = rep_penalty > 0.f && n_prev > 0;
+    for (int i = 0; i < n; ++i) {
+        SampleRow& r = rows[i];
+        r.prev = prev_ids_dev; r.n_prev_ptr = nullptr; r.tok = nullptr; r.append = nullptr; r.offset = offset; r.n_prev = pen ? n_prev : 0; r.prev_cap = n_prev; r.penalty = pen ? rep_penalty : 1.f;
+        r.temperature = temperature; r.top_k = top_k; r.top_p = top_p; r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32); r.lane = (uint32_t)i; r.advance = 0;
+    }
+    SampleRow* rows_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
+    int rc = MMD_OK;
+    auto release = [&]() { hipStreamSynchronize(st); if (rows_dev) hipFree(rows_dev); if (r_dev) hipFree(r_dev); if (scratch) hipFree(scratch); };
+#define OPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { release(); FAIL(c, MMD_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
+    OPCHK(hipMalloc((void**)&rows_dev, sizeof(SampleRow) * n));
+    OPCHK(hipMalloc(&scratch, sample_topkp_scratch_bytes(V, chunk, scores_out == nullptr)));
+    OPCHK(hipMemcpyAsync(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice, st));
+    if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpyAsync(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st)); }
+    const bool any_k = top_k > 0 && top_k < V, any_p = top_p < 1.f;
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = n - i0 < chunk ? n - i0 : chunk;
+        ProfScope ps(c, MMD_K_OTHER, 0, 0);
+        OPCHK(launch_sample_batch_topkp(logits + (size_t)i0 * V, V, m, rows_dev + i0, any_k, any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4,
+                                        scores_out ? scores_out + (size_t)i0 * V : nullptr, scratch, st));
+    }
+    OPCHK(hipStreamSynchronize(st));
+#undef OPCHK
+    release();
+    return rc;
 }
 
 // ---- measurement -------------------------------------------------------------------------------------------------------

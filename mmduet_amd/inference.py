@@ -21,7 +21,7 @@ import os
 from dataclasses import asdict
 import torch
 
-from .modeling_live import build_model_and_tokenizer, fast_greedy_generate
+from .modeling_live import build_model_and_tokenizer, fast_greedy_generate, fast_sample_generate
 from .tokenization_live import chat_ids
 
 VIT_BATCH = 32          # test/inference.py:208 (frames per tower call; results do not depend on it)
@@ -92,6 +92,12 @@ class LiveInferForBenchmark:
             raise ValueError('--first_n_frames_no_generate must be set when --threshold_z is set')
         self.remove_assistant_turns = args.remove_assistant_turns
         self.repetition_penalty = args.repetition_penalty
+        # sampled responses (off by default: arg-max, today's ids).  The arguments dataclass keeps the reference's schema; the CLI's own parser sets these on it.
+        self.do_sample = bool(getattr(args, 'do_sample', False))
+        self.temperature = float(getattr(args, 'temperature', 1.0))
+        self.top_k = int(getattr(args, 'top_k', 0) or 0)
+        self.top_p = float(getattr(args, 'top_p', 1.0))
+        self.sampling_seed = int(getattr(args, 'sampling_seed', 0) or 0)
         self.frames_per_forward = max(1, int(getattr(args, 'frames_per_forward', 1)))
         self.overlap_vision = bool(getattr(args, 'overlap_vision', True))
         self.record_head_logits = False          # diagnostics (parity tests, bench.py's self-check): debug_data entries also carry the 4 raw head logits of the frame
@@ -138,6 +144,7 @@ class LiveInferForBenchmark:
         self.past_key_values = None
         self.debug_data_list = list()
         self.generated_token_ids = list()
+        self._sample_offset = 0          # tokens drawn in this video: the Philox offset of the next response's first draw
         self.num_frames_no_reply = 0
         self.stream_end_prob_list = list()
         self.stream_end_score_sum = 0
@@ -379,10 +386,17 @@ class LiveInferForBenchmark:
         """test/inference.py:257-274."""
         self.last_ids = self._added_stream_generation_ids
         self._issue_vit_burst()
-        output_ids, past_key_values, self.generated_token_ids = fast_greedy_generate(
-            model=self.model, inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values,
-            eos_token_id=self.eos_token_id, inplace_output_ids=self.inplace_output_ids,
-            repetition_penalty=self.repetition_penalty, generated_token_ids=self.generated_token_ids)
+        if self.do_sample:
+            output_ids, past_key_values, self.generated_token_ids, self._sample_offset = fast_sample_generate(
+                model=self.model, inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values,
+                eos_token_id=self.eos_token_id, inplace_output_ids=self.inplace_output_ids,
+                repetition_penalty=self.repetition_penalty, generated_token_ids=self.generated_token_ids,
+                temperature=self.temperature, top_k=self.top_k, top_p=self.top_p, seed=self.sampling_seed, offset=self._sample_offset)
+        else:
+            output_ids, past_key_values, self.generated_token_ids = fast_greedy_generate(
+                model=self.model, inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values,
+                eos_token_id=self.eos_token_id, inplace_output_ids=self.inplace_output_ids,
+                repetition_penalty=self.repetition_penalty, generated_token_ids=self.generated_token_ids)
         self.last_generated_ids = output_ids[0].tolist()
         n_tok = len(self.last_generated_ids)
         self._resp_tokens_mean = n_tok if self._resp_tokens_mean is None else 0.7 * self._resp_tokens_mean + 0.3 * n_tok

@@ -101,6 +101,23 @@ class KVCacheHandle:
         return self.length
 
 
+_U64 = (1 << 64) - 1
+# generate() arguments that ask for something this package does not build: the value that means "off" is accepted, anything else raises
+_GENERATE_OFF = {'num_beams': 1, 'num_beam_groups': 1, 'num_return_sequences': 1, 'min_p': None, 'typical_p': 1.0, 'penalty_alpha': None, 'epsilon_cutoff': 0.0, 'eta_cutoff': 0.0,
+                 'diversity_penalty': 0.0, 'length_penalty': 1.0, 'no_repeat_ngram_size': 0, 'encoder_repetition_penalty': 1.0, 'bad_words_ids': None, 'force_words_ids': None,
+                 'constraints': None, 'logits_processor': None, 'stopping_criteria': None, 'prefix_allowed_tokens_fn': None, 'min_length': 0, 'min_new_tokens': None,
+                 'sequence_bias': None, 'guidance_scale': None, 'assistant_model': None, 'streamer': None, 'output_scores': False, 'output_logits': False,
+                 'output_attentions': False, 'output_hidden_states': False, 'early_stopping': False, 'renormalize_logits': False}
+_GENERATE_IGNORED = ('attention_mask', 'position_ids', 'use_cache', 'return_dict', 'pad_token_id', 'bos_token_id', 'synced_gpus')
+
+
+class GenerateOutput:
+    """What generate(return_dict_in_generate=True) returns."""
+
+    def __init__(self, sequences, past_key_values):
+        self.sequences, self.past_key_values = sequences, past_key_values
+
+
 class SamplerHandle:
     """mmd_sampler: greedy sampling state of one stream on the device (models/modeling_live.py:51-77 run by mmd_round_multi)."""
 
@@ -111,14 +128,33 @@ class SamplerHandle:
             check(lib().mmd_sampler_create(model._ctx, C.byref(h)), model._ctx, 'mmd_sampler_create')
         self.h = h.value
 
-    def begin(self, eos_token_id, repetition_penalty, generated_token_ids, max_new_tokens):
-        """Start of a response: the penalty list is every id generated so far in this video (it persists across turns, models/modeling_live.py:60-66)."""
+    def begin(self, eos_token_id, repetition_penalty, generated_token_ids, max_new_tokens, sampling=None):
+        """Start of a response: the penalty list is every id generated so far in this video (it persists across turns, models/modeling_live.py:60-66).
+        sampling: None = arg-max, or dict(temperature, top_k, top_p, seed) handed to mmd_sampler_set_sampling (the Philox offset restarts only when the seed changes)."""
         pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
         prev = list(generated_token_ids) if (generated_token_ids is not None and pen > 0) else []
         arr = (C.c_int64 * max(1, len(prev)))(*prev)
         with self.model._lock:
             self.model._bind_stream()
             check(lib().mmd_sampler_begin(self.h, int(eos_token_id if eos_token_id is not None else -1), pen, arr, len(prev), int(max_new_tokens)), self.model._ctx, 'mmd_sampler_begin')
+            if sampling is None and not getattr(self, '_sampling_on', False):
+                return          # arg-max, as the sampler was created: nothing to switch
+            sm = sampling or {}
+            self._sampling_on = sampling is not None
+            if sm.get('restart'):          # a new video on this sampler: the offset restarts although the seed stays (the native call restarts it on a seed change only)
+                check(lib().mmd_sampler_set_sampling(self.h, 1.0, 0, 1.0, (int(sm.get('seed', 0)) + 1) & _U64), self.model._ctx, 'mmd_sampler_set_sampling')
+            check(lib().mmd_sampler_set_sampling(self.h, float(sm.get('temperature', 1.0)) if sampling else 0.0, int(sm.get('top_k', 0) or 0), float(sm.get('top_p', 1.0)),
+                                                 int(sm.get('seed', 0)) & _U64), self.model._ctx, 'mmd_sampler_set_sampling')
+
+    @property
+    def lane(self):
+        """The sampler's id within its context: the Philox lane of its draws."""
+        return int(lib().mmd_sampler_lane(self.h))
+
+    @property
+    def offset(self):
+        """Tokens drawn since the seed was set."""
+        return int(lib().mmd_sampler_offset(self.h))
 
     def __del__(self):
         try:
@@ -784,6 +820,114 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             generated_token_ids[:] = [int(prev_arr[i]) for i in range(n_prev.value)]
         return ids, cache
 
+    def sample_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None,
+                        temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, lane=0):
+        """mmd_sample_generate, the sampled sibling of `greedy_generate`: -> (ids, cache, offset behind the last draw).  Draw i uses the Philox word of
+        (seed, offset + i, lane).  Zero new tokens posts nothing; the penalty list is extended only when the penalty is > 0.  NaN logits raise ValueError."""
+        x = inputs_embeds.reshape(-1, self.config.hidden_size).to(device=self.device, dtype=self.dtype).contiguous()
+        S = x.shape[0]
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens <= 0:
+            return [], past_key_values, int(offset)
+        if S == 0:
+            raise ValueError('empty prompt')
+        pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
+        grow = generated_token_ids is not None and pen > 0
+        prev = list(generated_token_ids) if grow else []
+        cap = len(prev) + max_new_tokens + 1
+        prev_arr = (C.c_int64 * cap)(*prev)
+        n_prev = C.c_int(len(prev))
+        out_ids = (C.c_int64 * max_new_tokens)()
+        n_out = C.c_int(0)
+        off = C.c_uint64(int(offset))
+        with self._lock:
+            arena, n = self._resolve_cache(past_key_values)
+            self._bind_stream()
+            check(lib().mmd_set_sample_lane(self._ctx, int(lane)), self._ctx, 'mmd_set_sample_lane')
+            check(lib().mmd_sample_generate(self._ctx, arena.h, _ptr(x), S, int(eos_token_id if eos_token_id is not None else -1), pen, prev_arr, C.byref(n_prev), cap,
+                                            float(temperature), int(top_k or 0), float(top_p), int(seed) & _U64, C.byref(off), out_ids, max_new_tokens, C.byref(n_out)),
+                  self._ctx, 'mmd_sample_generate')
+            cache = KVCacheHandle(arena, arena.length())
+        ids = [int(out_ids[i]) for i in range(n_out.value)]
+        if grow:
+            generated_token_ids[:] = [int(prev_arr[i]) for i in range(n_prev.value)]
+        return ids, cache, int(off.value)
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, inputs_embeds=None, frames=None, past_key_values=None, max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
+                 repetition_penalty=None, eos_token_id=None, seed=None, return_dict_in_generate=False, **kwargs):
+        """models/live_llava/video_head_live_llava_qwen.py:210-242 (HF `generate` for batch 1).  do_sample=False is the greedy path; do_sample=True draws with temperature,
+        top-k and top-p on the device (DESIGN.md "Sampling"), seeded by `seed` (None: one draw from torch.initial_seed() per call).  Returns a LongTensor [1, n]: with
+        `input_ids` the prompt followed by the new tokens, with `inputs_embeds` only the new tokens; with return_dict_in_generate an object with .sequences and
+        .past_key_values.  Arguments that ask for what is not built (beam search, min_p, typical_p, ...) raise NotImplementedError."""
+        if 'max_length' in kwargs and kwargs['max_length'] is not None:
+            raise NotImplementedError('generate: max_length is not supported, pass max_new_tokens')
+        kwargs.pop('max_length', None)
+        for k, v in kwargs.items():
+            if k in _GENERATE_IGNORED:
+                continue
+            if k not in _GENERATE_OFF:
+                raise NotImplementedError(f'generate: argument {k!r} is not supported')
+            if v is not None and v != _GENERATE_OFF[k]:
+                raise NotImplementedError(f'generate: {k}={v!r} is not supported')
+        prompt = input_ids
+        if inputs_embeds is None:
+            if input_ids is None:
+                raise ValueError('generate needs input_ids or inputs_embeds')
+            if input_ids.ndim == 1:
+                input_ids = input_ids[None]
+            inputs_embeds = self.joint_embed(input_ids, frames)
+        if inputs_embeds.ndim == 2:
+            inputs_embeds = inputs_embeds[None]
+        if inputs_embeds.shape[0] != 1:
+            raise NotImplementedError('generate: batch size 1 only (streaming is batch 1)')
+        if eos_token_id is None:
+            eos_token_id = getattr(self.config, 'eos_token_id', None)
+        if isinstance(eos_token_id, (list, tuple)):
+            if len(eos_token_id) > 1:
+                raise NotImplementedError('generate: one eos_token_id only')
+            eos_token_id = eos_token_id[0] if eos_token_id else None
+        pen = float(repetition_penalty) if repetition_penalty not in (None, 1.0) else None
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens <= 0:
+            ids, cache = [], past_key_values
+        elif not do_sample:
+            ids, cache = self.greedy_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, pen, [] if pen else None)
+        else:
+            if seed is None:
+                seed = torch.initial_seed()
+            ids, cache, _ = self.sample_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, pen, [] if pen else None,
+                                                 temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        new = torch.tensor([ids], dtype=torch.long, device=self.device).view(1, -1)
+        seq = new if prompt is None else torch.cat([prompt.reshape(1, -1).to(device=self.device, dtype=torch.long), new], dim=1)
+        return GenerateOutput(seq, cache) if return_dict_in_generate else seq
+
+    def generate_after_embed(self, input_ids, frames, **kwargs):
+        """models/live_llava/video_head_live_llava_qwen.py:207-208: generate over joint_embed(input_ids, frames); like HF with inputs_embeds only, the new tokens are returned."""
+        return self.generate(inputs_embeds=self.joint_embed(input_ids, frames), **kwargs)
+
+    def sample_op(self, logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, r=None, prev_ids=None, repetition_penalty=None, return_scores=False):
+        """The sampling chain on rows of fp32 logits [n, V] (mmd_op_sample; row i draws on lane i).  r: None = Philox words, else n explicit 64-bit random words.
+        -> (tokens int64 [n], info fp32 [n, 4] = (tau, kept count, kept mass / total mass, NaN flag), scores [n, V] or None), on the device."""
+        lg = logits.to(device=self.device, dtype=torch.float32).contiguous()
+        if lg.ndim == 1:
+            lg = lg[None]
+        n, V = lg.shape
+        toks = torch.empty(n, dtype=torch.long, device=self.device)
+        info = torch.empty(n, 4, dtype=torch.float32, device=self.device)
+        scores = torch.empty(n, V, dtype=torch.float32, device=self.device) if return_scores else None
+        prev = torch.as_tensor(prev_ids, dtype=torch.long).to(self.device).contiguous() if prev_ids is not None and len(prev_ids) else None
+        r_arr = None
+        if r is not None:
+            if len(r) != n:
+                raise ValueError('one random word per row')
+            r_arr = (C.c_uint64 * n)(*[int(v) & _U64 for v in r])
+        with self._lock:
+            self._bind_stream()
+            check(lib().mmd_op_sample(self._ctx, _ptr(lg), n, V, _ptr(prev), 0 if prev is None else prev.numel(), float(repetition_penalty or 0.0), float(temperature),
+                                      int(top_k or 0), float(top_p), int(seed) & _U64, int(offset) & _U64, r_arr, _ptr(toks), _ptr(info), _ptr(scores)), self._ctx, 'mmd_op_sample')
+        return toks, info, scores
+
     # ---- measurement --------------------------------------------------------------------------------------------------
     def prof_enable(self, classes=True):
         """classes: True = all kernel classes, False = off, or an iterable of class names from _lib.K_NAMES."""
@@ -826,6 +970,19 @@ def fast_greedy_generate(*, model, inputs_embeds: torch.Tensor, past_key_values,
     n = len(ids)
     inplace_output_ids[:, :n] = torch.tensor(ids, dtype=inplace_output_ids.dtype, device=inplace_output_ids.device)
     return inplace_output_ids[:, :n], cache, generated_token_ids
+
+
+def fast_sample_generate(*, model, inputs_embeds: torch.Tensor, past_key_values, eos_token_id: int, inplace_output_ids: torch.Tensor, repetition_penalty=None,
+                         generated_token_ids=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0):
+    """The sampled sibling of `fast_greedy_generate` (mmd_sample_generate, or the scheduler rounds behind a multi-stream proxy): -> (ids, cache, generated_token_ids,
+    the Philox offset behind the last draw).  There is no host fallback: a model without `sample_generate` is an error."""
+    if generated_token_ids is None:
+        generated_token_ids = list()
+    ids, cache, offset = model.sample_generate(inputs_embeds, past_key_values, eos_token_id, inplace_output_ids.size(1), repetition_penalty, generated_token_ids,
+                                               temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, offset=offset)
+    n = len(ids)
+    inplace_output_ids[:, :n] = torch.tensor(ids, dtype=inplace_output_ids.dtype, device=inplace_output_ids.device)
+    return inplace_output_ids[:, :n], cache, generated_token_ids, offset
 
 
 def _greedy_generate_by_calls(model, x, cache, eos_token_id, out_ids, penalty, seen):

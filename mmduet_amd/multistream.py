@@ -68,6 +68,24 @@ class _ModelProxy:
 
     forward = __call__
 
+    def sample_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None,
+                        temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, lane=None):
+        """The sampled response of one slot, a scheduler round per token: the slot's sampler draws on the device (mmd_round_multi) on its own Philox lane, so the ids do
+        not depend on which other streams share the rounds.  offset 0 (a new video) restarts the sampler's offset.  Zero new tokens posts nothing; the penalty list is
+        extended only when the penalty is > 0."""
+        if not hasattr(self._real, 'round_multi') or self._slot.sched.python_decode:
+            raise NotImplementedError('sampled responses of several streams need the native rounds (mmd_round_multi)')
+        if int(max_new_tokens) <= 0:
+            return [], past_key_values, int(offset)
+        pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
+        grow = generated_token_ids is not None and pen > 0
+        gen = dict(slot=self._slot, eos=eos_token_id, max_new=int(max_new_tokens), ids=[], penalty=pen if pen > 0 else None, prev=list(generated_token_ids) if grow else None,
+                   sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, restart=int(offset) == 0))
+        r = self._slot.post(_Request('generate', inputs_embeds, past_key_values, gen=gen))
+        if grow:
+            generated_token_ids.extend(t for t in r['ids'] if t != eos_token_id)
+        return r['ids'], r['cache'], int(offset) + len(r['ids'])
+
     def greedy_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None):
         """models/modeling_live.py:51-77 with one scheduler round per token (same rule as mmd_greedy_generate: the EOS token is
         written but neither fed back nor penalised; HF repetition penalty over every token generated so far in this video)."""
@@ -266,7 +284,10 @@ class MultiStreamInfer:
                     if slot.sampler is None:
                         slot.sampler = self.model.new_sampler()
                     g['sampler'] = slot.sampler
-                    g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'])
+                    if g.get('sampling') is not None:
+                        g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'], sampling=g['sampling'])
+                    else:
+                        g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'])
                     segs.append(dict(x=r.x, cache=r.cache, sampler=g['sampler'], sample=True))
                 else:
                     segs.append(dict(x=None, cache=g['cache'], sampler=g['sampler'], feed=True, sample=True))
