@@ -235,8 +235,8 @@ int mmd_round_multi(mmd_ctx* ctx, mmd_stream* const* streams, const int32_t* seg
 int mmd_greedy_generate(mmd_ctx* ctx, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty,
                         int64_t* prev_ids_host, int* n_prev, int prev_cap, int64_t* out_ids_host, int max_new, int* n_out);
 
-/* the sampled sibling of mmd_greedy_generate (what HF `generate(do_sample=True)` does for the reference class, models/live_llava/video_head_live_llava_qwen.py:207-242):
- * the same loop and decode step with the sampling chain in the arg-max's place and a captured step of its own.  Draw i uses Philox offset *offset_inout + i and the lane set by
+/* mmd_greedy_generate's loop with the sampling chain in the arg-max's place (what HF `generate(do_sample=True)` does for the reference class,
+ * models/live_llava/video_head_live_llava_qwen.py:207-242): one loop and one decode step serve both; each draw keeps its own captured step.  Draw i uses Philox offset *offset_inout + i and the lane set by
  * mmd_set_sample_lane (default 0); *offset_inout advances by the tokens drawn.  max_new == 0 enqueues nothing.  MMD_EDOM: a NaN among the logits (n_out tokens were drawn before). */
 int mmd_sample_generate(mmd_ctx* ctx, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
                         float temperature, int top_k, float top_p, uint64_t seed, uint64_t* offset_inout, int64_t* out_ids_host, int max_new, int* n_out);
@@ -328,6 +328,9 @@ int mmd_op_attention_bench(mmd_ctx* ctx, int S, int nh, int nkv, int d, int64_t 
  * attn_d72_ring_kernel (SigLIP-so400m), 8 attn_gqa128_chunk_kernel (multi-frame chunks, contiguous decomposition), 9 the decode rows of several streams in one launch
  * (mmd_round_multi); out2 = {form, key splits or the most blocks sharing a unit} */
 int mmd_op_attention_last_form(mmd_ctx* ctx, int* out2);
+/* what the decode steps of the most recent mmd_greedy_generate / mmd_sample_generate of this context did: 0 none or launched one by one, 1 replayed an existing captured
+ * step, 2 captured the step in that call, then replayed it (tests of the replay assert that it ran) */
+int mmd_op_decode_last_route(mmd_ctx* ctx);
 int mmd_op_pool(mmd_ctx* ctx, const void* x, void* y, int B, int grid, int H, int mode, int stride);
 
 #ifdef __cplusplus

@@ -32,6 +32,16 @@ struct Prof {
     double ms[MMD_K_COUNT] = {0}; int64_t n[MMD_K_COUNT] = {0}; double bytes[MMD_K_COUNT] = {0}; double flops[MMD_K_COUNT] = {0};
 };
 
+// one captured decode step: the instantiated graph, its source, and the (penalty, EOS, filter selection) it was captured for
+struct DecodeGraph {
+    hipGraphExec_t exec = nullptr; hipGraph_t src = nullptr;
+    float pen = 0.f; int64_t eos = 0; int sel = 0;
+    void drop() {
+        if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
+        if (src) { hipGraphDestroy(src); src = nullptr; }
+    }
+};
+
 struct LlmLayer { void *ln1 = 0, *ln2 = 0, *wqkv = 0, *bqkv = 0, *wo = 0, *wgu = 0, *wdown = 0;
                   void *wqkv_p = 0, *wo_p = 0, *wgu_p = 0, *wdown_p = 0;       // *_p: MFMA-fragment-major copies (skinny GEMM)
                   void *wqkv_8 = 0, *wo_8 = 0, *wgu_8 = 0, *wdown_8 = 0;       // fp8 e4m3 fragment-major copies (weight_dtype = fp8: the streaming kernels read these)
@@ -82,10 +92,10 @@ struct mmd_ctx {
     int lb_W = 0, lb_H = 0, lb_R = 0; int32_t* lb_xtab = 0; int32_t* lb_ytab = 0;      // letterbox tap tables (mmd_letterbox_frames)
     int pp_R = 0; int32_t* pp_coef = 0; int32_t* pp_bounds = 0; int pp_ksize = 0; uint8_t* pp_tmp = 0; size_t pp_tmp_bytes = 0;
     int last_vit_B = 0;
-    // graph-captured decode step (one per context; per-call state lives in *step_dev)
+    // graph-captured decode steps (generate_impl): the arg-max one, keyed by penalty value and EOS, and the sampled one, keyed by penalty on/off, EOS and which filters run;
+    // per-call state lives in *step_dev.  dec_route: what the most recent generate call's decode steps did (mmd_op_decode_last_route)
     StepState* step_dev = nullptr; StepState* step_host = nullptr;
-    hipGraphExec_t dec_graph = nullptr; hipGraph_t dec_graph_src = nullptr;
-    float dec_pen = 0.f; int64_t dec_eos = 0; bool no_graph = false;
+    DecodeGraph dec_greedy, dec_sampled; int dec_route = 0; bool no_graph = false;
     int last_form[2] = {0, 0};          // form / splits of the most recent LLM / raw-operator attention launch of THIS context (mmd_op_attention_last_form)
     int last_plan[4] = {-1, 0, 0, 0};   // kernel / tiles / splits / blocks of the most recent gemm() (mmd_op_gemm_last_plan)
     bool no_fuse = false;              // MMDUET_NO_FUSE=1: keep the unfused launch schedule (A/B and parity cross-check)
@@ -110,9 +120,8 @@ struct mmd_ctx {
     // mmd_lm_nll (allocated at its first use): one fp32 logit chunk [rows, chunk columns], the rows' (max, sum exp, label logit) and the one-writer partials of a chunk's reduce
     float* nll_ws = 0; size_t nll_ws_bytes = 0; float* nll_state = 0; float* nll_part = 0; int nll_rows = 0;
     // sampled decoding (allocated at its first use): row descriptors on the device ([0] mmd_sample_generate's, [1..] a round's) with their pinned staging, the chain's scratch
-    // for MMD_ROUND_MAX_SAMPLERS rows, and the captured sampled decode step -- an instance of its own beside dec_graph, re-captured only when a filter is switched on or off
+    // for MMD_ROUND_MAX_SAMPLERS rows
     SampleRow* samp_rows_dev = nullptr; SampleRow* samp_rows_host = nullptr; void* samp_scratch = nullptr;
-    hipGraphExec_t sdec_graph = nullptr; hipGraph_t sdec_graph_src = nullptr; int sdec_pen = 0, sdec_sel = 0; int64_t sdec_eos = 0;
     uint32_t sample_lane = 0; uint32_t n_samplers = 0;
     Prof prof;
 };
@@ -285,11 +294,8 @@ extern "C" void mmd_destroy(mmd_ctx* c) {
     if (c->seg_host) hipHostFree(c->seg_host);
     if (c->round_toks_host) hipHostFree(c->round_toks_host);
     if (c->samp_rows_host) hipHostFree(c->samp_rows_host);
-    if (c->sdec_graph) hipGraphExecDestroy(c->sdec_graph);
-    if (c->sdec_graph_src) hipGraphDestroy(c->sdec_graph_src);
     for (auto& ev : c->seg_event) if (ev) hipEventDestroy(ev);
-    if (c->dec_graph) hipGraphExecDestroy(c->dec_graph);
-    if (c->dec_graph_src) hipGraphDestroy(c->dec_graph_src);
+    c->dec_greedy.drop(); c->dec_sampled.drop();
     hipStreamDestroy(c->own_stream);
     delete c;
 }
@@ -1495,6 +1501,23 @@ extern "C" int mmd_llm_step_multi(mmd_ctx* c, mmd_stream* const* streams, const 
     return llm_step_segs(c, segs.data(), n_segs, embeds, S, hidden_out, nullptr);
 }
 
+// the rows whose final hidden state a step's caller reads, `a` first and `b` behind it (llm_step_segs may then leave l_hid compact, in this order); more than 64: no list
+static int build_need_list(const int32_t* a, int na, const int32_t* b, int nb, int32_t need[64]) {
+    int n = 0;
+    if (na + nb <= 64) { for (int i = 0; i < na; ++i) need[n++] = a[i]; for (int i = 0; i < nb; ++i) need[n++] = b[i]; }
+    return n;
+}
+// enqueue the 4 head logits of n rows of l_hid (`compact`: its first n rows) and their copy into heads_host; the caller synchronises and reads heads_host
+static int read_head_rows(mmd_ctx* c, const int32_t* rows, int n, bool compact) {
+    hipStream_t st = c->stream; const int H = c->cfg.hidden_size;
+    for (int i = 0; i < n; ++i) c->rows_host[i] = compact ? i : rows[i];
+    HIPCHK(c, hipMemcpyAsync(c->rows_dev, c->rows_host, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    { ProfScope ps(c, MMD_K_OTHER, 0, 0);
+      HIPCHK(c, launch_heads(c->cfg.dtype, c->l_hid, H, c->rows_dev, n, c->heads4, H, c->heads_dev, st)); }
+    HIPCHK(c, hipMemcpyAsync(c->heads_host, c->heads_dev, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, st));
+    return MMD_OK;
+}
+
 extern "C" int mmd_frame_step_multi(mmd_ctx* c, mmd_stream* const* streams, const int32_t* seg_rows, int n_segs, const void* embeds,
                                     const int32_t* head_rows, int n_head_rows, float* heads_out_host,
                                     const int32_t* hidden_rows, int n_hidden_rows, void* hidden_rows_out, float* logits_out) {
@@ -1506,9 +1529,7 @@ extern "C" int mmd_frame_step_multi(mmd_ctx* c, mmd_stream* const* streams, cons
     if ((n_head_rows && (!head_rows || !heads_out_host)) || (n_hidden_rows && (!hidden_rows || !hidden_rows_out))) FAIL(c, MMD_EINVAL, "null row/result pointer");
     for (int i = 0; i < n_head_rows; ++i) if (head_rows[i] < 0 || head_rows[i] >= S) FAIL(c, MMD_ERANGE, "head row %d outside the step", head_rows[i]);
     for (int i = 0; i < n_hidden_rows; ++i) if (hidden_rows[i] < 0 || hidden_rows[i] >= S) FAIL(c, MMD_ERANGE, "hidden row %d outside the step", hidden_rows[i]);
-    // the rows whose final hidden state is read: heads first, then the hidden / logit rows (llm_step_segs may then leave l_hid compact, in this order)
-    int32_t need[64]; int n_need = 0;
-    if (n_head_rows + n_hidden_rows <= 64) { for (int i = 0; i < n_head_rows; ++i) need[n_need++] = head_rows[i]; for (int i = 0; i < n_hidden_rows; ++i) need[n_need++] = hidden_rows[i]; }
+    int32_t need[64]; const int n_need = build_need_list(head_rows, n_head_rows, hidden_rows, n_hidden_rows, need);          // heads first, then the hidden / logit rows
     rc = llm_step_segs(c, segs.data(), n_segs, embeds, S, nullptr, nullptr, n_need ? need : nullptr, n_need); if (rc) return rc;
     const bool compact = c->hid_compact > 0;
     hipStream_t st = c->stream; const int H = c->cfg.hidden_size; const size_t e = es(c);
@@ -1516,11 +1537,7 @@ extern "C" int mmd_frame_step_multi(mmd_ctx* c, mmd_stream* const* streams, cons
         HIPCHK(c, hipMemcpyAsync((char*)hidden_rows_out + (size_t)i * H * e, (char*)c->l_hid + (size_t)(compact ? n_head_rows + i : hidden_rows[i]) * H * e, (size_t)H * e, hipMemcpyDeviceToDevice, st));
     if (n_hidden_rows && logits_out) { rc = mmd_lm_head(c, hidden_rows_out, n_hidden_rows, logits_out); if (rc) return rc; }
     if (n_head_rows) {
-        for (int i = 0; i < n_head_rows; ++i) c->rows_host[i] = compact ? i : head_rows[i];
-        HIPCHK(c, hipMemcpyAsync(c->rows_dev, c->rows_host, sizeof(int32_t) * n_head_rows, hipMemcpyHostToDevice, st));
-        { ProfScope ps(c, MMD_K_OTHER, 0, 0);
-          HIPCHK(c, launch_heads(c->cfg.dtype, c->l_hid, H, c->rows_dev, n_head_rows, c->heads4, H, c->heads_dev, st)); }
-        HIPCHK(c, hipMemcpyAsync(c->heads_host, c->heads_dev, sizeof(float) * 4 * n_head_rows, hipMemcpyDeviceToHost, st));
+        rc = read_head_rows(c, head_rows, n_head_rows, compact); if (rc) return rc;
         HIPCHK(c, hipStreamSynchronize(st));
         memcpy(heads_out_host, c->heads_host, sizeof(float) * 4 * n_head_rows);
     }
@@ -1539,9 +1556,16 @@ struct mmd_sampler {
     bool sampling = false, seeded = false; float temperature = 1.f, top_p = 1.f; int top_k = 0; uint64_t seed = 0, offset = 0; uint32_t lane = 0;
 };
 
-static void drop_sample_graph(mmd_ctx* c) {
-    if (c->sdec_graph) { hipGraphExecDestroy(c->sdec_graph); c->sdec_graph = nullptr; }
-    if (c->sdec_graph_src) { hipGraphDestroy(c->sdec_graph_src); c->sdec_graph_src = nullptr; }
+// one draw's parameters; SampleCall: which of the chain's filter kernels a launch over such rows needs
+struct SampleArgs { float temperature; int top_k; float top_p; uint64_t seed; uint64_t* offset_inout; };
+struct SampleCall { bool any_k, any_p; };
+static SampleCall sample_call(const SampleArgs& a, int V) { return SampleCall{a.top_k > 0 && a.top_k < V, a.top_p < 1.f}; }
+// every field of a row descriptor.  pen off: no list entry counts and the penalty is 1; n_prev_ptr (a decode step: &StepState::n_prev) overrides n_prev on the device
+static void fill_sample_row(SampleRow& r, const SampleArgs& a, const int64_t* prev, bool pen, int n_prev, int prev_cap, float penalty, const int* n_prev_ptr, int64_t* tok,
+                            int64_t* append, uint32_t lane, uint32_t advance) {
+    r.prev = prev; r.n_prev_ptr = n_prev_ptr; r.tok = tok; r.append = append; r.offset = *a.offset_inout;
+    r.n_prev = pen ? n_prev : 0; r.prev_cap = prev_cap; r.penalty = pen ? penalty : 1.f; r.temperature = a.temperature; r.top_k = a.top_k; r.top_p = a.top_p;
+    r.seed_lo = (uint32_t)a.seed; r.seed_hi = (uint32_t)(a.seed >> 32); r.lane = lane; r.advance = advance;
 }
 static int sample_reserve(mmd_ctx* c) {
     if (c->samp_scratch) return MMD_OK;
@@ -1633,11 +1657,10 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
             if (n_sample == n_greedy) { rc = sample_reserve(c); if (rc) return rc; }
             const bool pen = sp->penalty > 0.f;
-            SampleRow& r = c->samp_rows_host[1 + n_sample - n_greedy];
-            r.prev = sp->prev_dev; r.n_prev_ptr = nullptr; r.tok = sp->tok_dev; r.append = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
-            r.offset = sp->offset; r.n_prev = pen ? sp->n_prev : 0; r.prev_cap = sp->prev_cap; r.penalty = pen ? sp->penalty : 1.f; r.temperature = sp->temperature;
-            r.top_k = sp->top_k; r.top_p = sp->top_p; r.seed_lo = (uint32_t)sp->seed; r.seed_hi = (uint32_t)(sp->seed >> 32); r.lane = sp->lane; r.advance = 0;
-            any_k |= sp->top_k > 0 && sp->top_k < V; any_p |= sp->top_p < 1.f;
+            const SampleArgs a{sp->temperature, sp->top_k, sp->top_p, sp->seed, &sp->offset};
+            fill_sample_row(c->samp_rows_host[1 + n_sample - n_greedy], a, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr, sp->tok_dev,
+                            (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr, sp->lane, 0);
+            any_k |= sample_call(a, V).any_k; any_p |= sample_call(a, V).any_p;
             sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample;
             continue;
         }
@@ -1668,9 +1691,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         rc = dev_alloc(c, (void**)&c->round_toks_dev, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)); if (rc) return rc;
         HIPCHK(c, hipHostMalloc((void**)&c->round_toks_host, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)));
     }
-    // rows whose final hidden state is read: the heads' rows first, then the sampling rows (llm_step_segs may leave l_hid compact, in this order)
-    int32_t need[64]; int n_need = 0;
-    if (n_head_rows + n_sample <= 64) { for (int i = 0; i < n_head_rows; ++i) need[n_need++] = head_rows[i]; for (int i = 0; i < n_sample; ++i) need[n_need++] = sample_row[i]; }
+    int32_t need[64]; const int n_need = build_need_list(head_rows, n_head_rows, sample_row, n_sample, need);          // the heads' rows first, then the sampling rows
     rc = llm_step_segs(c, segs.data(), n_segs, c->l_h, S, nullptr, nullptr, n_need ? need : nullptr, n_need); if (rc) return rc;
     const bool compact = c->hid_compact > 0;
     if (n_sample) {
@@ -1693,13 +1714,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         }
         HIPCHK(c, hipMemcpyAsync(c->round_toks_host, c->round_toks_dev, sizeof(int64_t) * n_sample, hipMemcpyDeviceToHost, st));
     }
-    if (n_head_rows) {
-        for (int i = 0; i < n_head_rows; ++i) c->rows_host[i] = compact ? i : head_rows[i];
-        HIPCHK(c, hipMemcpyAsync(c->rows_dev, c->rows_host, sizeof(int32_t) * n_head_rows, hipMemcpyHostToDevice, st));
-        { ProfScope ps(c, MMD_K_OTHER, 0, 0);
-          HIPCHK(c, launch_heads(c->cfg.dtype, c->l_hid, H, c->rows_dev, n_head_rows, c->heads4, H, c->heads_dev, st)); }
-        HIPCHK(c, hipMemcpyAsync(c->heads_host, c->heads_dev, sizeof(float) * 4 * n_head_rows, hipMemcpyDeviceToHost, st));
-    }
+    if (n_head_rows) { rc = read_head_rows(c, head_rows, n_head_rows, compact); if (rc) return rc; }
     if (n_head_rows || n_sample) HIPCHK(c, hipStreamSynchronize(st));          // the round's ONE synchronisation: head logits and drawn tokens cross together
     if (n_head_rows) memcpy(heads_out_host, c->heads_host, sizeof(float) * 4 * n_head_rows);
     if (tokens_out_host) for (int j = 0; j < n_segs; ++j) tokens_out_host[j] = -1;
@@ -1798,24 +1813,18 @@ extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int
     for (int i = 0; i < n_rows; ++i) if (rows_host[i] < 0 || rows_host[i] >= S) FAIL(c, MMD_ERANGE, "head row %d outside the step", rows_host[i]);
     if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
     StepSeg one{s, 0, S};
-    int rc = S > 0 ? llm_step_segs(c, &one, 1, embeds, S, nullptr, nullptr, (n_rows > 0 && n_rows <= 64) ? rows_host : nullptr, n_rows) : MMD_OK; if (rc) return rc;
+    int32_t need[64]; const int n_need = build_need_list(rows_host, n_rows, nullptr, 0, need);
+    int rc = S > 0 ? llm_step_segs(c, &one, 1, embeds, S, nullptr, nullptr, n_need ? need : nullptr, n_need) : MMD_OK; if (rc) return rc;
     if (n_rows == 0) return MMD_OK;
-    const bool compact = c->hid_compact > 0;
-    for (int i = 0; i < n_rows; ++i) c->rows_host[i] = compact ? i : rows_host[i];
-    hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->rows_dev, c->rows_host, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, st));
-    { ProfScope ps(c, MMD_K_OTHER, 0, 0);
-      HIPCHK(c, launch_heads(c->cfg.dtype, c->l_hid, c->cfg.hidden_size, c->rows_dev, n_rows, c->heads4, c->cfg.hidden_size, c->heads_dev, st)); }
-    HIPCHK(c, hipMemcpyAsync(c->heads_host, c->heads_dev, sizeof(float) * 4 * n_rows, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
+    rc = read_head_rows(c, rows_host, n_rows, c->hid_compact > 0); if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(out_host, c->heads_host, sizeof(float) * 4 * n_rows);
     return MMD_OK;
 }
 
-// one decode step (feed the previously sampled token, sample the next) enqueued on the stream; `dyn` selects the
+// one decode step (feed the previously drawn token, draw the next) enqueued on the stream; `dyn` selects the
 // graph-capturable form that reads position / arena / penalty-list length from device state
-// `samp`: the sampled sibling (mmd_sample_generate) -- the sampling chain over row descriptor 0 takes the arg-max's place; its penalty list always grows on the device
-struct SampleCall { bool any_k, any_p; };
+// `samp`: the sampling chain over row descriptor 0 takes the arg-max's place; its penalty list always grows on the device
 static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const SampleCall* samp = nullptr) {
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size;
     // the next token's embedding is gathered straight into the residual-stream buffer (llm_step_segs skips its copy when embeds == l_h)
@@ -1832,46 +1841,88 @@ static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_pe
     return MMD_OK;
 }
 
-extern "C" int mmd_greedy_generate(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty,
-                                   int64_t* prev_ids_host, int* n_prev, int prev_cap, int64_t* out_ids_host, int max_new, int* n_out) {
-    NEED_FINAL(c);
-    if (!n_out || !out_ids_host || max_new <= 0) FAIL(c, MMD_EINVAL, "bad generate arguments");
-    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size; const size_t e = es(c);
+// captures one dynamic decode step into dg for the key (key_pen, eos_id, sel).  Capture runs on the context's own stream (the legacy null stream -- torch's default --
+// cannot be captured); the instantiated graph is then launched on whatever stream the caller bound
+static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, bool pen, float rep_penalty, int np, int64_t eos_id, const SampleCall* samp, float key_pen, int sel) {
+    hipStream_t st = c->stream;
+    dg.drop();
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->stream = c->own_stream;
+    hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
+    if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
+    int rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, samp);
+    hipError_t ce = hipStreamEndCapture(c->own_stream, &dg.src);
+    c->stream = st;
+    if (rc) { dg.drop(); return rc; }
+    HIPCHK(c, ce);
+    HIPCHK(c, hipGraphInstantiate(&dg.exec, dg.src, nullptr, nullptr, 0));
+    dg.pen = key_pen; dg.eos = eos_id; dg.sel = sel;
+    return MMD_OK;
+}
+
+// The reference penalises EVERY id generated so far in the video (models/modeling_live.py:60-66; the list persists across turns): the device copy grows
+// with it (doubling; both captured decode steps hold the old pointer and are dropped).  No cap.
+static int penalty_reserve(mmd_ctx* c, int need) {
+    if (need <= c->prev_cap) return MMD_OK;
+    int ncap = c->prev_cap > 0 ? c->prev_cap : 16384;
+    while (ncap < need) ncap *= 2;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->dec_greedy.drop(); c->dec_sampled.drop();
+    dev_free(c, c->prev_dev); c->prev_dev = nullptr; c->prev_cap = 0;
+    int rc = dev_alloc(c, (void**)&c->prev_dev, (size_t)ncap * sizeof(int64_t)); if (rc) return rc;
+    c->prev_cap = ncap;
+    return MMD_OK;
+}
+
+// ---- the token loop of a response: prompt step, then one token in, one token out --------------------------------------------------------------------------
+// samp == nullptr: arg-max (+ repetition penalty).  Otherwise the sampling chain of sample.hip stands where the arg-max stood.  Everything the chain needs per step is
+// in row descriptor 0 on the device: the penalty-list length is read through &step_dev->n_prev and grown by advance_state_kernel, the Philox offset is advanced by the
+// draw kernel, so the captured step is replayed as it is for any temperature / top_k / top_p / seed.  Draw i of the call uses offset *offset_inout + i; *offset_inout
+// advances with every token read (EOS included).  *n_out is up to date whenever the call returns.
+static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
+                         int64_t* out_ids_host, int max_new, int* n_out, const SampleArgs* samp) {
+    c->dec_route = 0; *n_out = 0;
+    if (max_new == 0) return MMD_OK;          // nothing asked for: nothing is enqueued, the stream is not extended
+    if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
+    if (S < 1) FAIL(c, MMD_EINVAL, "empty prompt");
+    int rc;
+    if (samp) { rc = check_sampling(c, samp->temperature, samp->top_k, samp->top_p); if (rc) return rc; }
+    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size, V = g.vocab_size; const size_t e = es(c);
     const bool pen = rep_penalty > 0.f;
     int np = (pen && n_prev) ? *n_prev : 0;
-    // The reference penalises EVERY id generated so far in the video (models/modeling_live.py:60-66; the list persists across turns): the device copy grows
-    // with it (doubling; a captured decode graph holds the old pointer and is dropped).  No cap.
-    if (pen && np + max_new > c->prev_cap) {
-        int ncap = c->prev_cap > 0 ? c->prev_cap : 16384;
-        while (ncap < np + max_new) ncap *= 2;
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->dec_graph) { hipGraphExecDestroy(c->dec_graph); c->dec_graph = nullptr; }
-        if (c->dec_graph_src) { hipGraphDestroy(c->dec_graph_src); c->dec_graph_src = nullptr; }
-        drop_sample_graph(c);
-        dev_free(c, c->prev_dev); c->prev_dev = nullptr; c->prev_cap = 0;
-        int rc0 = dev_alloc(c, (void**)&c->prev_dev, (size_t)ncap * sizeof(int64_t)); if (rc0) return rc0;
-        c->prev_cap = ncap;
-    }
+    if (pen) { rc = penalty_reserve(c, np + max_new); if (rc) return rc; }
+    if (samp) { rc = sample_reserve(c); if (rc) return rc; }
     if (np > 0) HIPCHK(c, hipMemcpyAsync(c->prev_dev, prev_ids_host, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
+    const SampleCall call = samp ? sample_call(*samp, V) : SampleCall{false, false};
+    const SampleCall* callp = samp ? &call : nullptr;
+    auto post_row = [&](bool dynamic) -> int {          // (every earlier upload from this staging slot has been waited for: a token read lies in between)
+        fill_sample_row(c->samp_rows_host[0], *samp, c->prev_dev, pen, np < c->prev_cap ? np : c->prev_cap, c->prev_cap, rep_penalty, dynamic ? &c->step_dev->n_prev : nullptr,
+                        c->tok_dev, nullptr, c->sample_lane, 1);
+        HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
+        return MMD_OK;
+    };
     int produced = 0;
     auto read_token = [&](int64_t* tok) -> int {
         HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         *tok = c->tok_host[0];
+        if (samp) { ++*samp->offset_inout; if (*tok < 0) FAIL(c, MMD_EDOM, "NaN in the logits: no token drawn"); }
         return MMD_OK;
     };
     // step 0: the prompt (eager)
-    int rc = llm_step_impl(c, s, prompt_embeds, S, nullptr, nullptr); if (rc) return rc;
+    rc = llm_step_impl(c, s, prompt_embeds, S, nullptr, nullptr); if (rc) return rc;
     {
         const void* last = (const char*)c->l_hid + (size_t)(S - 1) * H * e;
-        rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, g.vocab_size, 1, g.vocab_size, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
+        rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, V, 1, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
+        if (samp) { rc = post_row(false); if (rc) return rc; }
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        HIPCHK(c, launch_argmax_penalty(c->logits_ws, g.vocab_size, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, nullptr, c->argmax_scratch));
+        if (samp) HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st));
+        else HIPCHK(c, launch_argmax_penalty(c->logits_ws, V, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, nullptr, c->argmax_scratch));
     }
     int64_t tok = 0;
     rc = read_token(&tok); if (rc) return rc;
-    out_ids_host[produced++] = tok;
-    bool stop = tok == eos_id;
+    out_ids_host[produced++] = tok; *n_out = produced;
+    const bool stop = tok == eos_id;
     if (!stop && pen) {
         if (np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
@@ -1880,152 +1931,58 @@ extern "C" int mmd_greedy_generate(mmd_ctx* c, mmd_stream* s, const void* prompt
     // steps 1..: one token in, one token out.  bf16 + fused schedule: replay a captured hipGraph of the whole step
     // (~255 kernels) instead of launching them one by one -- the decode step is made of 5-50 us kernels and is otherwise
     // paced by host launch latency.
-    const bool can_graph = !stop && max_new > 1 && !c->no_graph && !c->no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr &&
+    const bool more = !stop && max_new > 1;
+    const bool can_graph = more && !c->no_graph && !c->no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr &&
                            g.hidden_size <= 4096 && g.head_dim == 128;     // head_dim 128: the attention kernel that reads *dyn
-    if (can_graph) {
-        rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc;
+    if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
+    if (can_graph || (samp && more)) {          // the sampled step reads the list length through *step_dev on the eager route too
         StepState* hs = c->step_host;
         hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->pad = 0;
         HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
-        if (!c->dec_graph || c->dec_pen != (pen ? rep_penalty : 0.f) || c->dec_eos != eos_id) {
-            if (c->dec_graph) { hipGraphExecDestroy(c->dec_graph); c->dec_graph = nullptr; }
-            if (c->dec_graph_src) { hipGraphDestroy(c->dec_graph_src); c->dec_graph_src = nullptr; }
-            HIPCHK(c, hipStreamSynchronize(st));
-            // capture on the context's own stream (the legacy null stream -- torch's default -- cannot be captured);
-            // the instantiated graph is then launched on whatever stream the caller bound
-            c->stream = c->own_stream;
-            hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
-            if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
-            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev);
-            hipError_t ce = hipStreamEndCapture(c->own_stream, &c->dec_graph_src);
-            c->stream = st;
-            if (rc) { if (c->dec_graph_src) { hipGraphDestroy(c->dec_graph_src); c->dec_graph_src = nullptr; } return rc; }
-            HIPCHK(c, ce);
-            HIPCHK(c, hipGraphInstantiate(&c->dec_graph, c->dec_graph_src, nullptr, nullptr, 0));
-            c->dec_pen = pen ? rep_penalty : 0.f; c->dec_eos = eos_id;
+    }
+    if (samp && more) { rc = post_row(true); if (rc) return rc; }
+    DecodeGraph& dg = samp ? c->dec_sampled : c->dec_greedy;
+    if (can_graph) {
+        // arg-max: the penalty value rides in a kernel argument.  sampled: the value is in the row descriptor, the step holds penalty on / off and which filters run
+        const float key_pen = pen ? (samp ? 1.f : rep_penalty) : 0.f;
+        const int sel = (call.any_k ? 1 : 0) | (call.any_p ? 2 : 0);
+        c->dec_route = 1;
+        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != sel) {
+            rc = capture_decode_step(c, s, dg, pen, rep_penalty, np, eos_id, callp, key_pen, sel); if (rc) { c->dec_route = 0; return rc; }
+            c->dec_route = 2;
         }
     }
     for (int i = 1; i < max_new && !stop; ++i) {
-        if (can_graph) {
-            HIPCHK(c, hipGraphLaunch(c->dec_graph, st));
-            s->len += 1;
-        } else {
-            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr); if (rc) return rc;
-        }
+        if (can_graph) { HIPCHK(c, hipGraphLaunch(dg.exec, st)); s->len += 1; }
+        else { rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, callp); if (rc) return rc; }
         rc = read_token(&tok); if (rc) return rc;
-        out_ids_host[produced++] = tok;
+        out_ids_host[produced++] = tok; *n_out = produced;
         if (tok == eos_id) break;
-        if (pen) {
-            if (!can_graph && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (pen) {          // (arg-max, eager: the list grows by a copy here; every other route grows it in advance_state_kernel)
+            if (!samp && !can_graph && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
             if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
             ++np;
         }
     }
-    *n_out = produced;
     if (pen && n_prev) *n_prev = np;
     return MMD_OK;
 }
 
-// ---- sampled decoding: the sibling of mmd_greedy_generate ------------------------------------------------------------------------------------------------
-// Same loop, same decode step (decode_step_enqueue / llm_step_impl); the sampling chain of sample.hip stands where the arg-max stood.  Everything the chain needs per step
-// is in row descriptor 0 on the device: the penalty-list length is read through &step_dev->n_prev and grown by advance_state_kernel, the Philox offset is advanced by the
-// draw kernel, so the captured step is replayed as it is for any temperature / top_k / top_p / seed.  Draw i of the call uses offset *offset_inout + i; on return
-// *offset_inout has advanced by the tokens drawn (EOS included).
+extern "C" int mmd_greedy_generate(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty,
+                                   int64_t* prev_ids_host, int* n_prev, int prev_cap, int64_t* out_ids_host, int max_new, int* n_out) {
+    NEED_FINAL(c);
+    if (!n_out || !out_ids_host || max_new <= 0) FAIL(c, MMD_EINVAL, "bad generate arguments");
+    return generate_impl(c, s, prompt_embeds, S, eos_id, rep_penalty, prev_ids_host, n_prev, prev_cap, out_ids_host, max_new, n_out, nullptr);
+}
+
 extern "C" int mmd_set_sample_lane(mmd_ctx* c, int lane) { if (!c || lane < 0) return MMD_EINVAL; c->sample_lane = (uint32_t)lane; return MMD_OK; }
 
 extern "C" int mmd_sample_generate(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
                                    float temperature, int top_k, float top_p, uint64_t seed, uint64_t* offset_inout, int64_t* out_ids_host, int max_new, int* n_out) {
     NEED_FINAL(c);
     if (!n_out || max_new < 0 || (max_new > 0 && !out_ids_host) || !offset_inout) FAIL(c, MMD_EINVAL, "bad generate arguments");
-    *n_out = 0;
-    if (max_new == 0) return MMD_OK;          // nothing asked for: nothing is enqueued, the stream is not extended
-    if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
-    int rc = check_sampling(c, temperature, top_k, top_p); if (rc) return rc;
-    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size, V = g.vocab_size; const size_t e = es(c);
-    const bool pen = rep_penalty > 0.f;
-    int np = (pen && n_prev) ? *n_prev : 0;
-    if (pen && np + max_new > c->prev_cap) {          // (as in mmd_greedy_generate: the list has no cap; both captured steps hold the old pointer)
-        int ncap = c->prev_cap > 0 ? c->prev_cap : 16384;
-        while (ncap < np + max_new) ncap *= 2;
-        HIPCHK(c, hipStreamSynchronize(st));
-        if (c->dec_graph) { hipGraphExecDestroy(c->dec_graph); c->dec_graph = nullptr; }
-        if (c->dec_graph_src) { hipGraphDestroy(c->dec_graph_src); c->dec_graph_src = nullptr; }
-        drop_sample_graph(c);
-        dev_free(c, c->prev_dev); c->prev_dev = nullptr; c->prev_cap = 0;
-        rc = dev_alloc(c, (void**)&c->prev_dev, (size_t)ncap * sizeof(int64_t)); if (rc) return rc;
-        c->prev_cap = ncap;
-    }
-    rc = sample_reserve(c); if (rc) return rc;
-    if (np > 0) HIPCHK(c, hipMemcpyAsync(c->prev_dev, prev_ids_host, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
-    const SampleCall call{top_k > 0 && top_k < V, top_p < 1.f};
-    uint64_t offset = *offset_inout;
-    auto post_row = [&](bool dynamic) -> int {          // (every earlier upload from this staging slot has been waited for: a token read lies in between)
-        SampleRow& r = c->samp_rows_host[0];
-        r.prev = c->prev_dev; r.n_prev_ptr = dynamic ? &c->step_dev->n_prev : nullptr; r.tok = c->tok_dev; r.append = nullptr; r.offset = offset;
-        r.n_prev = pen ? (np < c->prev_cap ? np : c->prev_cap) : 0; r.prev_cap = c->prev_cap; r.penalty = pen ? rep_penalty : 1.f; r.temperature = temperature; r.top_k = top_k; r.top_p = top_p;
-        r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32); r.lane = c->sample_lane; r.advance = 1;
-        HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
-        return MMD_OK;
-    };
-    int produced = 0;
-    auto read_token = [&](int64_t* tok) -> int {
-        HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        *tok = c->tok_host[0]; ++offset; *offset_inout = offset;
-        if (*tok < 0) FAIL(c, MMD_EDOM, "NaN in the logits: no token drawn");
-        return MMD_OK;
-    };
-    // step 0: the prompt (eager)
-    rc = llm_step_impl(c, s, prompt_embeds, S, nullptr, nullptr); if (rc) return rc;
-    {
-        const void* last = (const char*)c->l_hid + (size_t)(S - 1) * H * e;
-        rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, V, 1, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-        rc = post_row(false); if (rc) return rc;
-        ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st));
-    }
-    int64_t tok = 0;
-    rc = read_token(&tok); if (rc) return rc;
-    out_ids_host[produced++] = tok; *n_out = produced;
-    bool stop = tok == eos_id;
-    if (!stop && pen) {
-        if (np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
-        ++np;
-    }
-    if (!stop && max_new > 1) {
-        const bool can_graph = !c->no_graph && !c->no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr && g.hidden_size <= 4096 && g.head_dim == 128;
-        if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
-        StepState* hs = c->step_host;
-        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->pad = 0;
-        HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
-        rc = post_row(true); if (rc) return rc;
-        const int sel = (call.any_k ? 1 : 0) | (call.any_p ? 2 : 0);
-        if (can_graph && (!c->sdec_graph || c->sdec_pen != (pen ? 1 : 0) || c->sdec_eos != eos_id || c->sdec_sel != sel)) {
-            drop_sample_graph(c);
-            HIPCHK(c, hipStreamSynchronize(st));
-            c->stream = c->own_stream;          // (capture on the context's own stream, launch on the caller's: as the greedy step)
-            hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
-            if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
-            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, &call);
-            hipError_t ce = hipStreamEndCapture(c->own_stream, &c->sdec_graph_src);
-            c->stream = st;
-            if (rc) { if (c->sdec_graph_src) { hipGraphDestroy(c->sdec_graph_src); c->sdec_graph_src = nullptr; } return rc; }
-            HIPCHK(c, ce);
-            HIPCHK(c, hipGraphInstantiate(&c->sdec_graph, c->sdec_graph_src, nullptr, nullptr, 0));
-            c->sdec_pen = pen ? 1 : 0; c->sdec_eos = eos_id; c->sdec_sel = sel;
-        }
-        for (int i = 1; i < max_new; ++i) {
-            if (can_graph) { HIPCHK(c, hipGraphLaunch(c->sdec_graph, st)); s->len += 1; }
-            else { rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, &call); if (rc) return rc; }
-            rc = read_token(&tok); if (rc) return rc;
-            out_ids_host[produced++] = tok; *n_out = produced;
-            if (tok == eos_id) break;
-            if (pen) { if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok; ++np; }
-        }
-    }
-    if (pen && n_prev) *n_prev = np;
-    return MMD_OK;
+    const SampleArgs samp{temperature, top_k, top_p, seed, offset_inout};
+    return generate_impl(c, s, prompt_embeds, S, eos_id, rep_penalty, prev_ids_host, n_prev, prev_cap, out_ids_host, max_new, n_out, &samp);
 }
 
 // raw operator: n rows of logits through the sampling chain, one set of parameters, row i on lane i (MMD_ROUND_MAX_SAMPLERS rows per launch)
@@ -2038,12 +1995,8 @@ extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, cons
     hipStream_t st = c->stream;
     const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS;
     std::vector<SampleRow> rows((size_t)n);
-    const bool pen = rep_penalty > 0.f && n_prev > 0;
-    for (int i = 0; i < n; ++i) {
-        SampleRow& r = rows[i];
-        r.prev = prev_ids_dev; r.n_prev_ptr = nullptr; r.tok = nullptr; r.append = nullptr; r.offset = offset; r.n_prev = pen ? n_prev : 0; r.prev_cap = n_prev; r.penalty = pen ? rep_penalty : 1.f;
-        r.temperature = temperature; r.top_k = top_k; r.top_p = top_p; r.seed_lo = (uint32_t)seed; r.seed_hi = (uint32_t)(seed >> 32); r.lane = (uint32_t)i; r.advance = 0;
-    }
+    const SampleArgs a{temperature, top_k, top_p, seed, &offset};
+    for (int i = 0; i < n; ++i) fill_sample_row(rows[i], a, prev_ids_dev, rep_penalty > 0.f && n_prev > 0, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
     SampleRow* rows_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
     int rc = MMD_OK;
     auto release = [&]() { hipStreamSynchronize(st); if (rows_dev) hipFree(rows_dev); if (r_dev) hipFree(r_dev); if (scratch) hipFree(scratch); };
@@ -2052,11 +2005,11 @@ extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, cons
     OPCHK(hipMalloc(&scratch, sample_topkp_scratch_bytes(V, chunk, scores_out == nullptr)));
     OPCHK(hipMemcpyAsync(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice, st));
     if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpyAsync(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st)); }
-    const bool any_k = top_k > 0 && top_k < V, any_p = top_p < 1.f;
+    const SampleCall call = sample_call(a, V);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = n - i0 < chunk ? n - i0 : chunk;
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        OPCHK(launch_sample_batch_topkp(logits + (size_t)i0 * V, V, m, rows_dev + i0, any_k, any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4,
+        OPCHK(launch_sample_batch_topkp(logits + (size_t)i0 * V, V, m, rows_dev + i0, call.any_k, call.any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4,
                                         scores_out ? scores_out + (size_t)i0 * V : nullptr, scratch, st));
     }
     OPCHK(hipStreamSynchronize(st));
@@ -2177,6 +2130,8 @@ extern "C" int mmd_op_gemm_last_plan(mmd_ctx* c, int* out4) {
     for (int i = 0; i < 4; ++i) out4[i] = c->last_plan[i];
     return MMD_OK;
 }
+// the decode steps of the most recent generate call: 0 none or eager, 1 replayed an existing captured step, 2 captured in that call, then replayed
+extern "C" int mmd_op_decode_last_route(mmd_ctx* c) { return c ? c->dec_route : MMD_EINVAL; }
 // times one GEMM shape on the context's stream with HIP events (weights packed once, outside the timed region)
 extern "C" int mmd_op_gemm_bench(mmd_ctx* c, int M, int N, int K, int epi, int variant, int iters, float* avg_ms_out, const void* Xin, const void* Win) {
     if (!c || !avg_ms_out || iters <= 0) return MMD_EINVAL;

@@ -798,37 +798,11 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             hp += k
         return out
 
-    def greedy_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None,
-                        generated_token_ids=None):
+    def _native_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty, generated_token_ids, sampling=None):
+        """The marshalling of mmd_greedy_generate (sampling None) / mmd_sample_generate (sampling = (temperature, top_k, top_p, seed, offset, lane)):
+        -> (ids, cache, offset behind the last draw).  `generated_token_ids` is read and written back only when the penalty is > 0."""
         x = inputs_embeds.reshape(-1, self.config.hidden_size).to(device=self.device, dtype=self.dtype).contiguous()
         S = x.shape[0]
-        pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
-        prev = list(generated_token_ids) if (generated_token_ids is not None and pen > 0) else []
-        cap = len(prev) + max_new_tokens + 1
-        prev_arr = (C.c_int64 * cap)(*prev)
-        n_prev = C.c_int(len(prev))
-        out_ids = (C.c_int64 * max_new_tokens)()
-        n_out = C.c_int(0)
-        with self._lock:
-            arena, n = self._resolve_cache(past_key_values)
-            self._bind_stream()
-            check(lib().mmd_greedy_generate(self._ctx, arena.h, _ptr(x), S, int(eos_token_id if eos_token_id is not None else -1), pen, prev_arr,
-                                            C.byref(n_prev), cap, out_ids, int(max_new_tokens), C.byref(n_out)), self._ctx, 'mmd_greedy_generate')
-            cache = KVCacheHandle(arena, arena.length())
-        ids = [int(out_ids[i]) for i in range(n_out.value)]
-        if generated_token_ids is not None and pen > 0:
-            generated_token_ids[:] = [int(prev_arr[i]) for i in range(n_prev.value)]
-        return ids, cache
-
-    def sample_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None,
-                        temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, lane=0):
-        """mmd_sample_generate, the sampled sibling of `greedy_generate`: -> (ids, cache, offset behind the last draw).  Draw i uses the Philox word of
-        (seed, offset + i, lane).  Zero new tokens posts nothing; the penalty list is extended only when the penalty is > 0.  NaN logits raise ValueError."""
-        x = inputs_embeds.reshape(-1, self.config.hidden_size).to(device=self.device, dtype=self.dtype).contiguous()
-        S = x.shape[0]
-        max_new_tokens = int(max_new_tokens)
-        if max_new_tokens <= 0:
-            return [], past_key_values, int(offset)
         if S == 0:
             raise ValueError('empty prompt')
         pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
@@ -839,19 +813,44 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         n_prev = C.c_int(len(prev))
         out_ids = (C.c_int64 * max_new_tokens)()
         n_out = C.c_int(0)
-        off = C.c_uint64(int(offset))
+        eos = int(eos_token_id if eos_token_id is not None else -1)
+        off = C.c_uint64(0)
         with self._lock:
             arena, n = self._resolve_cache(past_key_values)
             self._bind_stream()
-            check(lib().mmd_set_sample_lane(self._ctx, int(lane)), self._ctx, 'mmd_set_sample_lane')
-            check(lib().mmd_sample_generate(self._ctx, arena.h, _ptr(x), S, int(eos_token_id if eos_token_id is not None else -1), pen, prev_arr, C.byref(n_prev), cap,
-                                            float(temperature), int(top_k or 0), float(top_p), int(seed) & _U64, C.byref(off), out_ids, max_new_tokens, C.byref(n_out)),
-                  self._ctx, 'mmd_sample_generate')
+            if sampling is None:
+                check(lib().mmd_greedy_generate(self._ctx, arena.h, _ptr(x), S, eos, pen, prev_arr, C.byref(n_prev), cap, out_ids, int(max_new_tokens), C.byref(n_out)),
+                      self._ctx, 'mmd_greedy_generate')
+            else:
+                temperature, top_k, top_p, seed, offset, lane = sampling
+                off.value = int(offset)
+                check(lib().mmd_set_sample_lane(self._ctx, int(lane)), self._ctx, 'mmd_set_sample_lane')
+                check(lib().mmd_sample_generate(self._ctx, arena.h, _ptr(x), S, eos, pen, prev_arr, C.byref(n_prev), cap, float(temperature), int(top_k or 0), float(top_p),
+                                                int(seed) & _U64, C.byref(off), out_ids, max_new_tokens, C.byref(n_out)), self._ctx, 'mmd_sample_generate')
             cache = KVCacheHandle(arena, arena.length())
         ids = [int(out_ids[i]) for i in range(n_out.value)]
         if grow:
             generated_token_ids[:] = [int(prev_arr[i]) for i in range(n_prev.value)]
         return ids, cache, int(off.value)
+
+    def greedy_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None,
+                        generated_token_ids=None):
+        return self._native_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty, generated_token_ids)[:2]
+
+    def sample_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None,
+                        temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, lane=0):
+        """mmd_sample_generate, `greedy_generate` with a draw in the arg-max's place: -> (ids, cache, offset behind the last draw).  Draw i uses the Philox word of
+        (seed, offset + i, lane).  Zero new tokens posts nothing; the penalty list is extended only when the penalty is > 0.  NaN logits raise ValueError."""
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens <= 0:
+            return [], past_key_values, int(offset)
+        return self._native_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty, generated_token_ids,
+                                     (temperature, top_k, top_p, seed, offset, lane))
+
+    def decode_last_route(self):
+        """What the decode steps of the most recent greedy_generate / sample_generate did (mmd_op_decode_last_route): 0 none or launched one by one,
+        1 replayed an existing captured step, 2 captured the step in that call, then replayed it."""
+        return int(lib().mmd_op_decode_last_route(self._ctx))
 
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, frames=None, past_key_values=None, max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
@@ -967,22 +966,24 @@ def fast_greedy_generate(*, model, inputs_embeds: torch.Tensor, past_key_values,
         return _greedy_generate_by_calls(model, inputs_embeds, past_key_values, eos_token_id, inplace_output_ids,
                                          repetition_penalty, generated_token_ids)
     ids, cache = model.greedy_generate(inputs_embeds, past_key_values, eos_token_id, max_new, repetition_penalty, generated_token_ids)
-    n = len(ids)
-    inplace_output_ids[:, :n] = torch.tensor(ids, dtype=inplace_output_ids.dtype, device=inplace_output_ids.device)
-    return inplace_output_ids[:, :n], cache, generated_token_ids
+    return _write_ids(inplace_output_ids, ids), cache, generated_token_ids
 
 
 def fast_sample_generate(*, model, inputs_embeds: torch.Tensor, past_key_values, eos_token_id: int, inplace_output_ids: torch.Tensor, repetition_penalty=None,
                          generated_token_ids=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0):
-    """The sampled sibling of `fast_greedy_generate` (mmd_sample_generate, or the scheduler rounds behind a multi-stream proxy): -> (ids, cache, generated_token_ids,
+    """`fast_greedy_generate` with a draw per token (mmd_sample_generate, or the scheduler rounds behind a multi-stream proxy): -> (ids, cache, generated_token_ids,
     the Philox offset behind the last draw).  There is no host fallback: a model without `sample_generate` is an error."""
     if generated_token_ids is None:
         generated_token_ids = list()
     ids, cache, offset = model.sample_generate(inputs_embeds, past_key_values, eos_token_id, inplace_output_ids.size(1), repetition_penalty, generated_token_ids,
                                                temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, offset=offset)
+    return _write_ids(inplace_output_ids, ids), cache, generated_token_ids, offset
+
+
+def _write_ids(inplace_output_ids, ids):
     n = len(ids)
     inplace_output_ids[:, :n] = torch.tensor(ids, dtype=inplace_output_ids.dtype, device=inplace_output_ids.device)
-    return inplace_output_ids[:, :n], cache, generated_token_ids, offset
+    return inplace_output_ids[:, :n]
 
 
 def _greedy_generate_by_calls(model, x, cache, eos_token_id, out_ids, penalty, seen):

@@ -6,7 +6,7 @@ at most V * 2^-40 ~ 1.4e-7: more than 20x margin, and far below any probability 
 End to end the logits are replayed through other launches (accumulation order: ~1e-6 on logits of scale 4, times 1/T), so DELTA_E2E = 1e-4 there.
 
 The tiny golden config has head_dim 16, so its bf16 context does not meet the captured-graph conditions of the decode loop: the graph route of mmd_sample_generate
-is exercised by tools/sampling_probe.py at true width, not here."""
+is tested at true width in tests/test_gpu_trueshape.py (test_sampled_replay_*), not here."""
 import numpy as np
 import pytest
 import torch

@@ -81,24 +81,36 @@ def test_chunked_forward_equals_per_frame_forward(true_shape):
     assert torch.equal(sc_a, sc_b)
 
 
-@pytest.mark.parametrize('penalty', [None, 1.3])
-def test_graph_replayed_decode_equals_call_loop(penalty, monkeypatch):
-    """mmd_greedy_generate replays a captured hipGraph per token (position / arena / penalty list in device state);
-    it must produce the tokens of the plain call-by-call loop, leave the same KV length, and be reusable across
-    streams (different arenas) and contexts lengths."""
-    from mmduet_amd.modeling_live import fast_greedy_generate, VideoHeadLiveLlavaQwenForCausalLM
+@pytest.fixture(scope='module')
+def graph_model():
+    """The true-width model with the captured decode step switched on (MMDUET_GRAPH is read when the native context is created)."""
+    from mmduet_amd.modeling_live import VideoHeadLiveLlavaQwenForCausalLM
     from mmduet_amd.configuration_live import VideoHeadLiveLlavaQwenConfig
-    monkeypatch.setenv('MMDUET_GRAPH', '1')            # read when the native context is created
     ocfg = O.OracleConfig(vocab_size=2048, num_hidden_layers=2, vit_layers=1)
     w = O.random_weights(ocfg, seed=3, dtype=torch.bfloat16, scale='unit')
     pcfg = VideoHeadLiveLlavaQwenConfig(vocab_size=2048, num_hidden_layers=2, vit_num_hidden_layers=2, vit_layers_removed=1,
                                         frame_num_tokens=49, frame_resolution=384, v_placeholder='<image>')
-    m = VideoHeadLiveLlavaQwenForCausalLM(pcfg, torch_dtype=torch.bfloat16, max_vit_batch=1, max_step_tokens=1024, kv_initial_tokens=1024)
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv('MMDUET_GRAPH', '1')
+        m = VideoHeadLiveLlavaQwenForCausalLM(pcfg, torch_dtype=torch.bfloat16, max_vit_batch=1, max_step_tokens=1024, kv_initial_tokens=1024)
     m.load_state_dict(w)
+    return m
+
+
+def _rand(g, rows):
+    return (torch.randn(1, rows, 3584, generator=g) * 0.5).to(torch.bfloat16).cuda()
+
+
+@pytest.mark.parametrize('penalty', [None, 1.3])
+def test_graph_replayed_decode_equals_call_loop(penalty, graph_model):
+    """mmd_greedy_generate replays a captured hipGraph per token (position / arena / penalty list in device state);
+    it must produce the tokens of the plain call-by-call loop, leave the same KV length, and be reusable across
+    streams (different arenas) and contexts lengths."""
+    from mmduet_amd.modeling_live import fast_greedy_generate
+    m = graph_model
     g = torch.Generator().manual_seed(7)
     for ctx_len in (30, 700):
-        ctx = (torch.randn(1, ctx_len, 3584, generator=g) * 0.5).to(torch.bfloat16).cuda()
-        prompt = (torch.randn(1, 13, 3584, generator=g) * 0.5).to(torch.bfloat16).cuda()
+        ctx, prompt = _rand(g, ctx_len), _rand(g, 13)
         res = []
         for loop in (False, True):
             base = m(inputs_embeds=ctx).past_key_values                   # a fresh arena each time
@@ -109,11 +121,71 @@ def test_graph_replayed_decode_equals_call_loop(penalty, monkeypatch):
                                                         inplace_output_ids=out, repetition_penalty=penalty, generated_token_ids=seen)
             finally:
                 m.python_generate_loop = False
+            if not loop:
+                assert m.decode_last_route() in (1, 2)                    # the native call really replayed a captured step
             nxt = m(inputs_embeds=prompt[:, :3], past_key_values=cache)   # the context left behind is usable and identical
             res.append((ids[0].tolist(), list(seen), len(cache), nxt.informative_logits[0, -1].tolist()))
         assert res[0][0] == res[1][0], (res[0][0], res[1][0])
         assert res[0][1] == res[1][1] and res[0][2] == res[1][2] == ctx_len + 13 + 11
         assert res[0][3] == pytest.approx(res[1][3], abs=2e-2)
+
+
+@pytest.mark.parametrize('penalty', [None, 1.3])
+def test_sampled_replay_top_k_1_equals_greedy_replay(penalty, graph_model):
+    """Both replayed steps enqueue the same decode step and lm_head GEMM, so the logits are the same bits; temperature 1.0 leaves them untouched and top-k 1 keeps
+    the maximum alone: the sampled replay must return the greedy replay's ids (an exact fp32 tie at the maximum aside, the exposure the greedy test above has too).
+    The sampled step is captured at the first call with its (penalty on/off, EOS, filters) key and replayed as it is afterwards."""
+    m = graph_model
+    g = torch.Generator().manual_seed(8)
+    for want_route, ctx_len in ((2, 30), (1, 700)):
+        ctx, prompt = _rand(g, ctx_len), _rand(g, 13)
+        seen_g, seen_s = [5, 9], [5, 9]
+        ids_g, cache_g = m.greedy_generate(prompt, m(inputs_embeds=ctx).past_key_values, -1, 12, penalty, seen_g)
+        assert m.decode_last_route() in (1, 2)
+        ids_s, cache_s, off = m.sample_generate(prompt, m(inputs_embeds=ctx).past_key_values, -1, 12, penalty, seen_s, temperature=1.0, top_k=1, top_p=1.0, seed=11, offset=0)
+        assert m.decode_last_route() == want_route
+        assert ids_s == ids_g, (ids_s, ids_g)
+        assert seen_s == seen_g and len(cache_s) == len(cache_g) == ctx_len + 13 + 11
+        assert off == len(ids_s) == 12
+
+
+def test_sampled_replay_repeats_and_recaptures_on_key_change(graph_model):
+    """The same (seed, offset) gives the same ids on the replay route, through a re-capture and through a plain replay; switching a filter off or changing the EOS
+    re-captures.  EOS: written, neither fed back nor added to the penalty list, and it still counts as a draw.  (No comparison with the eager route's ids: the two
+    routes may take different attention forms, so a draw may legitimately differ.)"""
+    m = graph_model
+    g = torch.Generator().manual_seed(9)
+    for ctx_len in (30, 700):
+        ctx, prompt = _rand(g, ctx_len), _rand(g, 13)
+
+        def run(top_p, eos=-1):
+            seen = [5, 9]
+            ids, cache, off = m.sample_generate(prompt, m(inputs_embeds=ctx).past_key_values, eos, 12, 1.3, seen, temperature=0.8, top_k=40, top_p=top_p, seed=5, offset=0)
+            return ids, len(cache), seen, off, m.decode_last_route()
+
+        a1 = run(0.9); assert a1[4] == 2
+        b = run(1.0); assert b[4] == 2          # top-p off: another selection of filter kernels
+        a2 = run(0.9); assert a2[4] == 2 and a2[0] == a1[0]
+        a3 = run(0.9); assert a3[4] == 1 and a3[0] == a1[0]
+        A = a1[0]
+        assert len(A) == 12 and a1[1] == ctx_len + 13 + 11 and a1[3] == 12
+        eos = A[4]; j = A.index(eos)
+        ids, n_cache, seen, off, route = run(0.9, eos)
+        assert route == 2
+        assert ids == A[:j + 1]
+        assert n_cache == ctx_len + 13 + j
+        assert seen == [5, 9] + A[:j] and eos not in seen[2:]
+        assert off == j + 1
+
+
+def test_greedy_generate_rejects_an_empty_prompt(graph_model):
+    from mmduet_amd.modeling_live import fast_greedy_generate
+    m = graph_model
+    empty = torch.zeros(1, 0, 3584, dtype=torch.bfloat16, device='cuda')
+    with pytest.raises(ValueError):
+        m.greedy_generate(empty, None, -1, 4)
+    with pytest.raises(ValueError):
+        fast_greedy_generate(model=m, inputs_embeds=empty, past_key_values=None, eos_token_id=-1, inplace_output_ids=torch.zeros(1, 4, dtype=torch.long, device='cuda'))
 
 
 def test_fused_and_unfused_schedules_agree(true_shape, monkeypatch):
