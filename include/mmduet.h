@@ -331,6 +331,10 @@ int mmd_op_attention_last_form(mmd_ctx* ctx, int* out2);
 /* what the decode steps of the most recent mmd_greedy_generate / mmd_sample_generate of this context did: 0 none or launched one by one, 1 replayed an existing captured
  * step, 2 captured the step in that call, then replayed it (tests of the replay assert that it ran) */
 int mmd_op_decode_last_route(mmd_ctx* ctx);
+/* the schedule the most recent LLM step of this context took (step_plan() of mmduet_amd/csrc/step_plan.h; tests assert that a step, or an A/B switch, took the schedule they
+ * mean): out9 = {schedule (0 tile, 1 fused slabs, 2 decode chain), rope_fused, chunk_rope, sparse_last, run0, run_n, run_all (the batched decode attention's run of segments),
+ * down_slab_norm, mlp_pm} */
+int mmd_op_step_last_plan(mmd_ctx* ctx, int* out9);
 int mmd_op_pool(mmd_ctx* ctx, const void* x, void* y, int B, int grid, int H, int mode, int stride);
 
 #ifdef __cplusplus

@@ -98,6 +98,7 @@ static inline size_t dtype_size(int dt) { return dt == MMD_F32 ? 4 : 2; }
 struct StepState { long long n_ctx; long long cap; void* K; void* V; int n_prev; int pad; };
 
 // ---- the GEMM family (arguments, epilogues, kernel ids and the dispatch decision: gemm_plan.h) ---------------------------
+const GemmTuning& gemm_tuning();          // the process's GemmTuning (MMDUET_GEMV_KSPLIT_SHORT, read once)
 GemmPlan gemm_plan_for(int dtype, const GemmArgs& a);          // gemm_plan with the process's GemmTuning: what launch_gemm(dtype, a, ...) would launch
 bool gemm_can_slab(int dtype, const GemmArgs& a);          // would a weight-streaming kernel leave X . W^T as fp32 K slabs in splitk_ws (GemmArgs::slabs_out)?
 bool gemm_ring_auto(int dtype, const GemmArgs& a, bool plain_only = false);          // would the automatic dispatch run this GEMM on gemm_ringx_kernel (plain or split-K; plain_only: not the split-K form)?  (what a piece-major operand needs; a piece-major OUTPUT needs the plain form)

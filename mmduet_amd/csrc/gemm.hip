@@ -1246,10 +1246,11 @@ static hipError_t launch_t(const GemmArgs& a, const GemmPlan& pl, hipStream_t st
 }
 
 // the process's GemmTuning: read from the environment once
-GemmPlan gemm_plan_for(int dtype, const GemmArgs& a) {
+const GemmTuning& gemm_tuning() {
     static const GemmTuning tune = [] { GemmTuning t; if (const char* s = getenv("MMDUET_GEMV_KSPLIT_SHORT")) t.gemv_ksplit_short = atoi(s); return t; }();
-    return gemm_plan(dtype, a, tune);
+    return tune;
 }
+GemmPlan gemm_plan_for(int dtype, const GemmArgs& a) { return gemm_plan(dtype, a, gemm_tuning()); }
 bool gemm_can_slab(int dtype, const GemmArgs& a) {
     int dummy = 0; GemmArgs b = a; b.slabs_out = &dummy; b.epi = EPI_NONE;
     const int k = gemm_plan_for(dtype, b).kernel;

@@ -7,6 +7,7 @@
 //       mmd_video_heads + mmd_lm_head
 //   fast_greedy_generate (models/modeling_live.py:51-77) -> mmd_greedy_generate
 #include "common.h"
+#include "step_plan.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -98,8 +99,8 @@ struct mmd_ctx {
     DecodeGraph dec_greedy, dec_sampled; int dec_route = 0; bool no_graph = false;
     int last_form[2] = {0, 0};          // form / splits of the most recent LLM / raw-operator attention launch of THIS context (mmd_op_attention_last_form)
     int last_plan[4] = {-1, 0, 0, 0};   // kernel / tiles / splits / blocks of the most recent gemm() (mmd_op_gemm_last_plan)
-    bool no_fuse = false;              // MMDUET_NO_FUSE=1: keep the unfused launch schedule (A/B and parity cross-check)
-    bool no_pm = false;                // MMDUET_NO_FUSE=1 | 2: MLP intermediates stay row-major (gemm_pair_pm)
+    StepSwitches sw;                   // the A/B switches of the step schedule (step_plan.h), read from the environment in mmd_create
+    int step_last[STEP_PLAN_FIELDS] = {0};          // the plan of the most recent LLM step of THIS context (mmd_op_step_last_plan)
     bool gemm_half = false;            // the GEMMs issued right now belong to the fp16 vision tower (cfg.tower_f16): IEEE-half operands
     int tower_ring_flags = -1, tower_ring_blocks = 0;   // mmd_set_tower_share: persistent-grid cap of the tower's ring GEMMs beside a response's decoding
     int hid_compact = 0;               // > 0: l_hid holds that many compact rows (in the order of the `need` list) instead of all S rows of the step
@@ -107,11 +108,7 @@ struct mmd_ctx {
     bool last_sparse = false;          // the most recent vit_tower ran its last layer on the pooled rows only (v_h then holds no full output: the debug taps refuse)
     bool tower_compact = false;        // the tower's output of the current batch is the compact [B * (2 out)^2, C] block in v_col (set by vit_tower, consumed by connector_pool)
     bool full_projector = false;       // set while mmd_vit_debug_tap(stage 1) recomputes the projector over ALL tokens (the shipped path runs it on the tokens the bilinear pool reads)
-    bool no_slab_norm = false;         // MMDUET_NO_SLAB_NORM=1: a chunk's split-K down_proj keeps splitk_reduce + a separate RMSNorm launch (A/B)
-    bool full_last_layer = false;      // MMDUET_FULL_LAST_LAYER=1: a chunk's last decoder layer keeps o_proj / MLP / final norm on all rows (A/B)
-    bool no_chain = false;             // MMDUET_NO_CHAIN=1: decode steps keep the separate reduce+residual+RMSNorm launches (A/B)
     void* rope_tab = 0;                // (cos, sin) of a decode step's positions (launch_rope_table), read by the attention kernel's fused q/k/v preparation
-    bool no_rope_fuse = false;         // MMDUET_NO_ROPE_FUSE=1: decode steps keep the slab_rope_append launch (A/B)
     float* chain_ssq = 0;              // GemvChain scratch: per-row, per-n-tile sums of squares
     StepState* seg_dev = nullptr; StepState* seg_host = nullptr; int seg_slot = 0;          // per-stream (context, capacity, arena) of a step's batched decode attention: 8 slots of 64, rotated per step
     hipEvent_t seg_event[8] = {};      // recorded behind a slot's upload: the pinned host slot is rewritten only once that copy has run (steps without a synchronisation may queue up)
@@ -234,7 +231,7 @@ static int gemm(mmd_ctx* c, const void* X, int64_t ldx, const void* W, int64_t l
 // Yes when the automatic dispatch runs BOTH on gemm_ringx_kernel (gemm_ring_auto asks the planner about the very arguments gemm() will launch with).
 static bool gemm_pair_pm(mmd_ctx* c, bool tower, const void* X1, int64_t ldx1, const void* W1p, const void* b1, int N1w, int K1, int epi1, void* T, int64_t ldt,
                          const void* W2p, int N2, const void* R2, int64_t ldr2, void* Y2, int64_t ldy2, int epi2, int M) {
-    if (c->no_pm) return false;
+    if (c->sw.no_pm) return false;
     const int dt = c->gemm_half ? MMD_F16 : c->cfg.dtype;
     const GemmArgs a = gemm_args(c, X1, ldx1, nullptr, 0, b1, nullptr, 0, T, ldt, M, N1w, K1, epi1, 0, GEMM_AUTO, W1p, tower);
     const GemmArgs b = gemm_args(c, T, ldt, nullptr, 0, nullptr, R2, ldr2, Y2, ldy2, M, N2, (int)ldt, epi2, 0, GEMM_AUTO, W2p, tower);
@@ -267,11 +264,11 @@ extern "C" int mmd_create(const mmd_config* cfg, int device, mmd_ctx** out) {
     c->vit_kpad = (int)round_up(3 * cfg->vit_patch * cfg->vit_patch, 64);
     c->vit_ipad = (int)round_up(cfg->vit_intermediate, 64);
     c->qkv_w = cfg->vision_only ? 0 : (cfg->num_heads + 2 * cfg->num_kv_heads) * cfg->head_dim;
-    { const char* nf = getenv("MMDUET_NO_FUSE"); c->no_fuse = nf && nf[0] == '1'; c->no_pm = nf && (nf[0] == '1' || nf[0] == '2'); }          // (2: only the piece-major MLP intermediates off -- their A/B)
-    { const char* nf = getenv("MMDUET_NO_CHAIN"); c->no_chain = nf && nf[0] == '1'; }
-    { const char* nf = getenv("MMDUET_NO_SLAB_NORM"); c->no_slab_norm = nf && nf[0] == '1'; }
-    { const char* nf = getenv("MMDUET_FULL_LAST_LAYER"); c->full_last_layer = nf && nf[0] == '1'; }
-    { const char* nf = getenv("MMDUET_NO_ROPE_FUSE"); c->no_rope_fuse = nf && nf[0] == '1'; }
+    auto is1 = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
+    StepSwitches& sw = c->sw;
+    { const char* nf = getenv("MMDUET_NO_FUSE"); sw.no_fuse = nf && nf[0] == '1'; sw.no_pm = nf && (nf[0] == '1' || nf[0] == '2'); }          // (2: only the piece-major MLP intermediates off -- their A/B)
+    sw.no_chain = is1("MMDUET_NO_CHAIN"); sw.no_slab_norm = is1("MMDUET_NO_SLAB_NORM"); sw.full_last_layer = is1("MMDUET_FULL_LAST_LAYER"); sw.no_rope_fuse = is1("MMDUET_NO_ROPE_FUSE");
+    sw.no_multi_fuse = getenv("MMDUET_NO_MULTI_FUSE") != nullptr; sw.no_multi_attn = getenv("MMDUET_NO_MULTI_ATTN") != nullptr; sw.no_chunk_rope = getenv("MMDUET_NO_CHUNK_ROPE") != nullptr;
     // graph replay of the decode step is opt-in (MMDUET_GRAPH=1): measured on MI355X it is not faster than eager launches
     // from this C++ loop (458 vs 480-500 ms for 128 tokens) -- the step is bound by the ~1.5 us GPU-side kernel boundaries,
     // which a graph does not remove, not by host launch latency.
@@ -626,8 +623,8 @@ static int alloc_workspaces(mmd_ctx* c) {
     HIPCHK(c, hipHostMalloc((void**)&c->rows_host, (size_t)S * sizeof(int32_t)));
     HIPCHK(c, hipHostMalloc((void**)&c->tok_host, 64));
     HIPCHK(c, hipHostMalloc((void**)&c->step_host, sizeof(StepState)));
-    HIPCHK(c, hipHostMalloc((void**)&c->seg_host, 8 * 64 * sizeof(StepState)));
-    rc = dev_alloc(c, (void**)&c->seg_dev, 8 * 64 * sizeof(StepState)); if (rc) return rc;
+    HIPCHK(c, hipHostMalloc((void**)&c->seg_host, 8 * STEP_MULTI_ATTN_MAX_RUN * sizeof(StepState)));
+    rc = dev_alloc(c, (void**)&c->seg_dev, 8 * STEP_MULTI_ATTN_MAX_RUN * sizeof(StepState)); if (rc) return rc;
     rc = dev_alloc(c, (void**)&c->step_dev, sizeof(StepState)); if (rc) return rc;
     return MMD_OK;
 }
@@ -1243,231 +1240,233 @@ static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need) {
 // host-side allocation / bookkeeping / event recording may happen here.
 // One causal forward over `nseg` video streams: segment j is rows [row0, row0 + rows) of the step and extends stream j's
 // arena; every GEMM / norm runs once over all S rows, RoPE + KV append + attention run per segment on that stream's arena.
+// Which launches that takes is decided once per step by step_plan() (step_plan.h); the functions below read the plan and launch.
 struct StepSeg { mmd_stream* s; int row0; int rows; };
-
+// one step in flight: its arguments, its plan, and the little state the layers hand on
+struct StepRun {
+    mmd_ctx* c; const StepSeg* segs; int nseg; int S; const StepState* dyn; const int32_t* need_rows; int n_need;
+    StepPlan p;
+    const StepState* seg_states = nullptr;          // device copy of the batched attention run's per-stream states
+    GemvChain ch_fin, ch_xn;                        // decode chain: producer / consumer side
+    bool xn_ready = false;                          // tile schedule: the previous layer's fused slab consumer already left this layer's normalised input in l_xn
+};
+static StepModel step_model(const mmd_ctx* c) {
+    const mmd_config& g = c->cfg; static const LlmLayer none; const LlmLayer& L = c->L.empty() ? none : c->L[0]; StepModel m;          // (no layers: nothing packed, the tile schedule)
+    m.dtype = g.dtype; m.H = g.hidden_size; m.I = g.intermediate_size; m.nh = g.num_heads; m.nkv = g.num_kv_heads; m.d = g.head_dim; m.qkv_w = c->qkv_w; m.layers = g.num_layers;
+    m.qkv_p = L.wqkv_p != nullptr; m.o_p = L.wo_p != nullptr; m.gu_p = L.wgu_p != nullptr; m.down_p = L.wdown_p != nullptr; m.fp8 = L.sgu != nullptr;
+    m.attn_ws = c->attn_ws != nullptr; m.splitk_ws_bytes = c->splitk_ws ? c->splitk_bytes : 0; return m;
+}
+// the GemmArgs of a slab-mode GEMM of a step: the weight-streaming kernels leave fp32 K slabs in the split-K workspace and the NEXT operator consumes them
+// (reduce + bias + RoPE + KV append; reduce + residual + RMSNorm) -- identical rounding points, fewer launches
+static GemmArgs slab_args(mmd_ctx* c, const void* X, int64_t ldx, const void* Wp, int M, int N, int K) {
+    GemmArgs a; memset(&a, 0, sizeof(a));
+    a.X = X; a.ldx = ldx; a.Wp = Wp; a.M = M; a.N = N; a.K = K; a.epi = EPI_NONE; a.variant = GEMM_SKINNY;
+    a.splitk_ws = c->splitk_ws; a.splitk_ws_bytes = c->splitk_bytes;
+    return a;
+}
+// Mrows > 0: the GEMM runs on that many gathered rows (sparse last layer)
+static int slab_gemm(const StepRun& r, const void* X, int64_t ldx, const void* Wp, int N, int K, int* splits, const void* Wp8, const float* wscale, const GemvChain* chn = nullptr, int Mrows = 0) {
+    mmd_ctx* c = r.c; const int S = r.S; const double e = (double)es(c);
+    GemmArgs a = slab_args(c, X, ldx, Wp, Mrows > 0 ? Mrows : S, N, K);
+    a.chain = chn; a.Wp8 = Wp8; a.wscale = wscale; a.slabs_out = splits;
+    ProfScope ps(c, MMD_K_GEMM_SKINNY, (double)S * K * e + (double)N * K * (Wp8 ? 1.0 : e) + (double)S * N * e, 2.0 * S * N * K);
+    HIPCHK(c, launch_gemm(c->cfg.dtype, a, c->stream));
+    return MMD_OK;
+}
+// the per-stream (context, capacity, arena) of the batched decode attention's run, uploaded through one of eight rotating pinned slots
+static int upload_seg_states(StepRun& r) {
+    mmd_ctx* c = r.c; hipStream_t st = c->stream;
+    const int slot = c->seg_slot;
+    StepState* hs = c->seg_host + (size_t)slot * STEP_MULTI_ATTN_MAX_RUN; StepState* ds = c->seg_dev + (size_t)slot * STEP_MULTI_ATTN_MAX_RUN;
+    c->seg_slot = (slot + 1) & 7;
+    if (!c->seg_event[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->seg_event[slot], hipEventDisableTiming));
+    else HIPCHK(c, hipEventSynchronize(c->seg_event[slot]));          // (eight steps old: long done unless the caller queues steps without ever synchronising)
+    for (int j = 0; j < r.p.run_n; ++j) { mmd_stream* sj = r.segs[r.p.run0 + j].s; hs[j].n_ctx = sj->len; hs[j].cap = sj->cap; hs[j].K = sj->K; hs[j].V = sj->V; hs[j].n_prev = 0; hs[j].pad = 0; }
+    HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(StepState) * r.p.run_n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(c->seg_event[slot], st));
+    r.seg_states = ds;
+    return MMD_OK;
+}
+// layer i: the qkv GEMM, then RoPE + KV append per segment (unless the attention kernel prepares q / k / v from the slabs itself); *splits = the qkv slabs left in the workspace
+static int layer_qkv(StepRun& r, int i, int* splits) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg; LlmLayer& L = c->L[i]; hipStream_t st = c->stream;
+    const int dt = g.dtype, S = r.S, H = g.hidden_size, nh = g.num_heads, nkv = g.num_kv_heads, d = g.head_dim; const size_t e = es(c); int rc;
+    if (r.p.schedule != STEP_TILE) {
+        r.ch_xn.xn_gamma = L.ln1;
+        rc = slab_gemm(r, c->l_xn, H, L.wqkv_p, c->qkv_w, H, splits, L.wqkv_8, L.sqkv, r.p.schedule == STEP_CHAIN && i > 0 ? &r.ch_xn : nullptr); if (rc) return rc;
+        if (r.p.rope_fused) return MMD_OK;
+    } else {
+        if (!r.xn_ready) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, L.ln1, c->l_xn, S, H, g.rms_norm_eps, st)); }
+        r.xn_ready = false;
+        rc = gemm(c, c->l_xn, H, L.wqkv, H, L.bqkv, nullptr, 0, c->l_qkv, c->qkv_w, S, c->qkv_w, H, EPI_NONE, 0, GEMM_AUTO, L.wqkv_p, false, L.wqkv_8, L.sqkv); if (rc) return rc;
+    }
+    ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * c->qkv_w * e, 0);
+    for (int j = 0; j < r.nseg; ++j) {
+        const StepSeg& sg = r.segs[j]; mmd_stream* sj = sg.s;
+        const size_t le = kv_layer_elems(c, sj->cap);
+        void* q = (char*)c->l_q + (size_t)sg.row0 * nh * d * e; void* K = (char*)sj->K + (size_t)i * le * e; void* V = (char*)sj->V + (size_t)i * le * e;
+        if (r.p.schedule != STEP_TILE)
+            HIPCHK(c, launch_slab_rope_append(c->splitk_ws + (size_t)sg.row0 * c->qkv_w, *splits, L.bqkv, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, st, r.dyn, i, S));
+        else if (r.p.chunk_rope)          // vectorised form over the step's (cos, sin) table (built once, before the layer loop)
+            HIPCHK(c, launch_rope_append_chunk((char*)c->l_qkv + (size_t)sg.row0 * c->qkv_w * e, sg.rows, nh, nkv, (char*)c->rope_tab + (size_t)sg.row0 * 64 * 8, sj->len, q, K, V, sj->cap, st));
+        else
+            HIPCHK(c, launch_rope_append(dt, (char*)c->l_qkv + (size_t)sg.row0 * c->qkv_w * e, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, 1, st));
+    }
+    return MMD_OK;
+}
+// what the batched and the per-stream attention launch of layer i share: `rows` query rows from step row `row0` on
+static AttnArgs attn_args(const StepRun& r, int i, int row0, int rows, int splits) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg;
+    const int nh = g.num_heads, d = g.head_dim; const size_t e = es(c);
+    AttnArgs a; memset(&a, 0, sizeof(a));
+    a.q = (char*)c->l_q + (size_t)row0 * nh * d * e; a.ldq = (int64_t)nh * d; a.out = (char*)c->l_attn + (size_t)row0 * nh * d * e; a.ldo = (int64_t)nh * d;
+    a.k_ts = d; a.v_ts = d; a.v_transposed = 1;
+    a.S = rows; a.nh = nh; a.nkv = g.num_kv_heads; a.d = d; a.causal = 1; a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.layer = i;
+    // few rows, head_dim 128: the attention kernel prepares q / k / v from the qkv slabs itself (AttnArgs::qkv_slabs)
+    if (r.p.rope_fused) { a.qkv_slabs = c->splitk_ws + (size_t)row0 * c->qkv_w; a.slab_rows = r.S; a.n_slabs = splits; a.qkv_bias = c->L[i].bqkv; a.rope_tab = (char*)c->rope_tab + (size_t)row0 * 64 * 8; }
+    return a;
+}
+// layer i: ONE launch for the plan's run of talking streams (a quarter of the launches, partials and merge work of per-stream launches whose 64-way key splits each fill
+// the chip alone), one launch per other segment on its stream's arena
+static int layer_attention(const StepRun& r, int i, int splits) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg; hipStream_t st = c->stream;
+    const int nh = g.num_heads, nkv = g.num_kv_heads, d = g.head_dim, run0 = r.p.run0, run_n = r.p.run_n; const size_t e = es(c);
+    if (run_n > 0) {
+        const int rr = r.segs[run0].rows;
+        AttnArgs a = attn_args(r, i, r.segs[run0].row0, rr, splits);
+        a.segs = r.seg_states; a.nseg = run_n;
+        double kvb = 0, fl = 0;
+        for (int j = run0; j < run0 + run_n; ++j) { const double nk = (double)(r.segs[j].s->len + r.segs[j].rows); kvb += 2.0 * nk * nkv * d * e; fl += 4.0 * r.segs[j].rows * nk * nh * d; }
+        ProfScope ps(c, MMD_K_ATTN_LLM, kvb + 2.0 * rr * run_n * nh * d * e, fl);
+        { const hipError_t le = launch_attention_decode_multi(a, st); attn_last_form(c->last_form); HIPCHK(c, le); }
+    }
+    for (int j = 0; j < r.nseg; ++j) {
+        if (j >= run0 && j < run0 + run_n) continue;
+        mmd_stream* sj = r.segs[j].s;
+        const size_t le = kv_layer_elems(c, sj->cap);
+        const int Sj = r.segs[j].rows; const int64_t nj = sj->len;
+        AttnArgs a = attn_args(r, i, r.segs[j].row0, Sj, splits);
+        a.K = (char*)sj->K + (size_t)i * le * e; a.V = (char*)sj->V + (size_t)i * le * e;
+        a.k_hs = sj->cap * d; a.v_hs = sj->cap * d; a.n_ctx = nj;
+        a.dyn = r.dyn; a.dyn_splits = 64;
+        double kvb = 2.0 * (double)(nj + Sj) * nkv * d * e;
+        ProfScope ps(c, MMD_K_ATTN_LLM, kvb + 2.0 * Sj * nh * d * e, 4.0 * Sj * (double)(nj + Sj) * nh * d);
+        { const hipError_t le = launch_attention(g.dtype, a, st); attn_last_form(c->last_form); HIPCHK(c, le); }
+    }
+    return MMD_OK;
+}
+// the norm weight and the destination of the normalised rows behind layer i: the next layer's input, or the final norm into l_hid
+static const void* next_norm(const mmd_ctx* c, int i) { return i + 1 < c->cfg.num_layers ? c->L[i + 1].ln1 : c->fnorm; }
+static void* next_xn(const mmd_ctx* c, int i) { return i + 1 < c->cfg.num_layers ? c->l_xn : c->l_hid; }
+// Decode chain (every GEMM is the weight-streaming GEMV): o_proj / down_proj fold their result into the residual stream themselves and leave the row sums of squares,
+// qkv / gate_up build the normalised activation per lane (GemvChain, gemm_plan.h): 7 launches per layer
+static int layer_tail_chain(StepRun& r, int i) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg; LlmLayer& L = c->L[i];
+    const int S = r.S, H = g.hidden_size, I = g.intermediate_size, nh = g.num_heads, d = g.head_dim; const size_t e = es(c); int splits = 1;
+    int rc = slab_gemm(r, c->l_attn, (int64_t)nh * d, L.wo_p, H, nh * d, &splits, L.wo_8, L.so, &r.ch_fin); if (rc) return rc;
+    r.ch_xn.xn_gamma = L.ln2;
+    rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, S, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu, &r.ch_xn); if (rc) return rc;
+    const bool last = i + 1 == g.num_layers;              // the caller wants the final norm's output materialised
+    rc = slab_gemm(r, c->l_act, I, L.wdown_p, H, I, &splits, L.wdown_8, L.sdown, last ? nullptr : &r.ch_fin); if (rc) return rc;
+    if (last) {
+        ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e, 0);
+        HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, splits, S, H, c->l_h, c->l_h, next_norm(c, i), g.rms_norm_eps, next_xn(c, i), c->stream));
+    }
+    return MMD_OK;
+}
+// Fused slabs: o_proj and down_proj leave slabs, one reduce + residual + RMSNorm pass each consumes them: 9 launches per layer instead of 12
+static int layer_tail_fused(StepRun& r, int i) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg; LlmLayer& L = c->L[i]; hipStream_t st = c->stream;
+    const int S = r.S, H = g.hidden_size, I = g.intermediate_size, nh = g.num_heads, d = g.head_dim; const size_t e = es(c); int splits = 1;
+    int rc = slab_gemm(r, c->l_attn, (int64_t)nh * d, L.wo_p, H, nh * d, &splits, L.wo_8, L.so); if (rc) return rc;
+    { ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e, 0);
+      HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, splits, S, H, c->l_h, c->l_h, L.ln2, g.rms_norm_eps, c->l_xn, st)); }
+    rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, S, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu); if (rc) return rc;
+    rc = slab_gemm(r, c->l_act, I, L.wdown_p, H, I, &splits, L.wdown_8, L.sdown); if (rc) return rc;
+    ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e, 0);
+    HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, splits, S, H, c->l_h, c->l_h, next_norm(c, i), g.rms_norm_eps, next_xn(c, i), st));
+    return MMD_OK;
+}
+// Tile schedule: every GEMM applies its own epilogue; the plan says whether the SwiGLU product is piece-major and whether down_proj's split-K slabs go to ONE pass that
+// sums them, adds the residual stream and normalises for the next layer (or the final norm) -- instead of splitk_reduce (+ residual) and a separate RMSNorm launch
+static int layer_tail_tile(StepRun& r, int i) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg; LlmLayer& L = c->L[i]; hipStream_t st = c->stream;
+    const int dt = g.dtype, S = r.S, H = g.hidden_size, I = g.intermediate_size, nh = g.num_heads, d = g.head_dim; const size_t e = es(c); const bool pm = r.p.mlp_pm;
+    int rc = gemm(c, c->l_attn, (int64_t)nh * d, L.wo, (int64_t)nh * d, nullptr, c->l_h, H, c->l_h, H, S, H, nh * d, EPI_RESID, 0, GEMM_AUTO, L.wo_p, false, L.wo_8, L.so); if (rc) return rc;
+    { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, L.ln2, c->l_xn, S, H, g.rms_norm_eps, st)); }
+    rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, S, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu, nullptr, nullptr, pm ? 2 : 0); if (rc) return rc;
+    int rs = 0;
+    rc = gemm(c, c->l_act, I, L.wdown, I, nullptr, c->l_h, H, c->l_h, H, S, H, I, EPI_RESID, 0, GEMM_AUTO, L.wdown_p, false, L.wdown_8, L.sdown, nullptr,
+              r.p.down_slab_norm ? &rs : nullptr, pm ? 1 : 0); if (rc) return rc;
+    if (r.p.down_slab_norm) {
+        ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e + 4.0 * rs * S * H, 0);
+        HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, rs, S, H, c->l_h, c->l_h, next_norm(c, i), g.rms_norm_eps, next_xn(c, i), st, L.sdown));          // (fp8 matrices: the tile GEMM's slabs are unscaled)
+        r.xn_ready = true;
+    }
+    return MMD_OK;
+}
+// The hidden states of a chunk's LAST layer are read at a few rows only (the frame-end rows of the two heads, the row whose logits are wanted); its K / V must exist
+// for every token, but its o_proj and MLP are row-wise: they run on the rows somebody reads, through the weight-streaming kernels.  The reference computes all
+// rows and drops them (the lm_head over all positions is "pure waste the build skips" -- the same holds one layer down).  l_hid is left compact.
+static int layer_tail_sparse_last(StepRun& r, int i) {
+    mmd_ctx* c = r.c; const mmd_config& g = c->cfg; LlmLayer& L = c->L[i]; hipStream_t st = c->stream;
+    const int H = g.hidden_size, I = g.intermediate_size, nh = g.num_heads, d = g.head_dim, n_need = r.n_need; const size_t e = es(c);
+    void* attn_c = c->l_q; void* h_c = c->l_qkv;          // (both dead here: the queries were consumed by the attention above, the fused qkv rows by RoPE + append)
+    { ProfScope ps(c, MMD_K_OTHER, 0, 0);
+      HIPCHK(c, launch_gather_rows2(c->l_attn, (int64_t)nh * d, attn_c, nh * d, c->l_h, H, h_c, H, r.need_rows, n_need, st)); }
+    int sp = 1, rc = slab_gemm(r, attn_c, (int64_t)nh * d, L.wo_p, H, nh * d, &sp, L.wo_8, L.so, nullptr, n_need); if (rc) return rc;
+    { ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * n_need * H * e, 0);
+      HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, sp, n_need, H, h_c, h_c, L.ln2, g.rms_norm_eps, c->l_xn, st)); }
+    rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, n_need, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu); if (rc) return rc;
+    rc = slab_gemm(r, c->l_act, I, L.wdown_p, H, I, &sp, L.wdown_8, L.sdown, nullptr, n_need); if (rc) return rc;
+    { ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * n_need * H * e, 0);
+      HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, sp, n_need, H, h_c, h_c, c->fnorm, g.rms_norm_eps, c->l_hid, st)); }
+    c->hid_compact = n_need;
+    r.xn_ready = true;          // (the final norm is done)
+    return MMD_OK;
+}
 static int llm_step_segs(mmd_ctx* c, const StepSeg* segs, int nseg, const void* embeds, int S, void* hidden_out, const StepState* dyn, const int32_t* need_rows = nullptr, int n_need = 0) {
     NEED_FINAL(c);
     c->hid_compact = 0;
     if (S <= 0 || nseg <= 0) return MMD_OK;
-    const mmd_config& g = c->cfg; const int dt = g.dtype; const size_t e = es(c); hipStream_t st = c->stream;
+    const mmd_config& g = c->cfg; const int dt = g.dtype, H = g.hidden_size; const size_t e = es(c); hipStream_t st = c->stream;
     if (S > g.max_step_tokens) FAIL(c, MMD_ERANGE, "step of %d tokens exceeds max_step_tokens %d", S, g.max_step_tokens);
-    int rc = MMD_OK;
+    int rc = MMD_OK; int rows_few[16]; std::vector<int> rows_many(nseg > 16 ? nseg : 0); int* seg_rows = nseg > 16 ? rows_many.data() : rows_few;          // (no allocation for the usual few streams)
     {
         int at = 0;
         for (int j = 0; j < nseg; ++j) {
             if (!segs[j].s || segs[j].s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
             if (segs[j].rows <= 0 || segs[j].row0 != at) FAIL(c, MMD_EINVAL, "segments must be non-empty and consecutive");
             for (int k = 0; k < j; ++k) if (segs[k].s == segs[j].s) FAIL(c, MMD_EINVAL, "a stream may appear once per step");
-            at += segs[j].rows;
+            at += segs[j].rows; seg_rows[j] = segs[j].rows;
         }
         if (at != S) FAIL(c, MMD_EINVAL, "segments cover %d rows of a %d-row step", at, S);
     }
-    if (dyn && nseg != 1) FAIL(c, MMD_EINVAL, "graph decode is single-stream");
     if (!dyn) for (int j = 0; j < nseg; ++j) { rc = kv_reserve(c, segs[j].s, segs[j].s->len + segs[j].rows); if (rc) return rc; }
-    const int H = g.hidden_size, I = g.intermediate_size, nh = g.num_heads, nkv = g.num_kv_heads, d = g.head_dim;
+    StepShape shape;
+    shape.S = S; shape.seg_rows = seg_rows; shape.nseg = nseg; shape.n_need = need_rows ? n_need : 0; shape.hidden_out = hidden_out != nullptr; shape.dyn = dyn != nullptr;
+    StepRun r{c, segs, nseg, S, dyn, need_rows, n_need, step_plan(step_model(c), shape, c->sw, gemm_tuning())};
+    const StepPlan& p = r.p;
+    if (p.rc) FAIL(c, p.rc, "%s", p.error);
+    if (p.sparse_last) for (int k = 0; k < n_need; ++k) if (need_rows[k] < 0 || need_rows[k] >= S) FAIL(c, MMD_ERANGE, "needed row %d outside the step", need_rows[k]);
+    p.fields(c->step_last);
     if (embeds != c->l_h) HIPCHK(c, hipMemcpyAsync(c->l_h, embeds, (size_t)S * H * e, hipMemcpyDeviceToDevice, st));
 
-    // Fused schedule for the weight-streaming regime (S <= 256, packed bf16 weights): the skinny / streaming GEMMs leave fp32 split-K
-    // slabs and the NEXT operator consumes them (reduce + bias + RoPE + KV append; reduce + residual + RMSNorm):
-    // 9 launches per layer instead of 12, identical rounding points.
-    // the GemmArgs of a slab-mode GEMM of this step (the weight-streaming kernels leave fp32 K slabs in the split-K workspace): what slab_gemm launches and the probes below ask about
-    auto slab_args = [&](const void* X, int64_t ldx, const void* Wp, int M, int N, int K) {
-        GemmArgs a; memset(&a, 0, sizeof(a));
-        a.X = X; a.ldx = ldx; a.Wp = Wp; a.M = M; a.N = N; a.K = K; a.epi = EPI_NONE; a.variant = GEMM_SKINNY;
-        a.splitk_ws = c->splitk_ws; a.splitk_ws_bytes = c->splitk_bytes;
-        return a;
-    };
-    bool fused = false;
-    // (several streams in one step -- mmd_round_multi's decode rounds: every talking stream's row, a few short segments -- take the same schedule: the GEMVs and the
-    //  slab consumers are row-wise, RoPE + KV append + attention read each stream's rows of the slabs at its row offset; MMDUET_NO_MULTI_FUSE=1 keeps the unfused form, A/B)
-    static const bool no_multi_fuse = getenv("MMDUET_NO_MULTI_FUSE") != nullptr;
-    if ((nseg == 1 || !no_multi_fuse) && dt == MMD_BF16 && S <= 256 && H <= 4096 && (H & 3) == 0 && !c->no_fuse) {          // (S > 64: gemm_stream_kernel's slabs -- gemm_can_slab says whether the shapes qualify)
-        fused = gemm_can_slab(dt, slab_args(c->l_xn, H, c->L[0].wqkv_p, S, c->qkv_w, H)) && gemm_can_slab(dt, slab_args(c->l_act, I, c->L[0].wdown_p, S, H, I)) &&
-                gemm_can_slab(dt, slab_args(c->l_attn, nh * d, c->L[0].wo_p, S, H, nh * d));
-    }
-    // Decode chain (S <= 4: every GEMM is the weight-streaming GEMV): o_proj / down_proj fold their result into the residual stream themselves
-    // and leave the row sums of squares, qkv / gate_up build the normalised activation per lane (GemvChain, common.h): 7 launches per layer.
-    const bool chain = fused && S <= GEMV_CHAIN_ROWS && !c->no_chain && H % 64 == 0 && H <= 4096;
-    GemvChain ch_fin, ch_xn;
-    ch_fin.fin_h = c->l_h; ch_fin.fin_ssq = c->chain_ssq;
-    ch_xn.xn_h = c->l_h; ch_xn.xn_ssq = c->chain_ssq; ch_xn.xn_eps = g.rms_norm_eps;
-    auto slab_gemm = [&](const void* X, int64_t ldx, const void* Wp, int N, int K, int* splits, const void* Wp8, const float* wscale, const GemvChain* chn = nullptr, int Mrows = 0) -> int {
-        GemmArgs a = slab_args(X, ldx, Wp, Mrows > 0 ? Mrows : S, N, K);
-        a.chain = chn; a.Wp8 = Wp8; a.wscale = wscale; a.slabs_out = splits;
-        ProfScope ps(c, MMD_K_GEMM_SKINNY, (double)S * K * e + (double)N * K * (Wp8 ? 1.0 : e) + (double)S * N * e, 2.0 * S * N * K);
-        HIPCHK(c, launch_gemm(dt, a, st));
-        return MMD_OK;
-    };
-    if (dyn && !fused) FAIL(c, MMD_EINVAL, "graph decode needs the fused bf16 schedule");
-    if (fused) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, c->L[0].ln1, c->l_xn, S, H, g.rms_norm_eps, st)); }
-
-    // Several streams, each with the same one or two rows (the talking streams of a scheduler round): ONE attention launch for all of them (launch_attention_decode_multi) -- a
-    // quarter of the launches, partials and merge work of four per-stream launches whose 64-way key splits each fill the chip alone.  MMDUET_NO_MULTI_ATTN=1: per stream (A/B)
-    static const bool no_multi_attn = getenv("MMDUET_NO_MULTI_ATTN") != nullptr;
-    // (the longest run of consecutive segments with the same one or two rows: the scheduler puts the talking streams' rows behind the watching streams' chunks)
-    int run0 = 0, run_n = 0;
-    if (nseg > 1 && dt == MMD_BF16 && d == 128 && !no_multi_attn && !dyn && !c->no_fuse && c->attn_ws) {
-        for (int j = 0; j < nseg;) {
-            int k = j + 1;
-            while (k < nseg && segs[k].rows == segs[j].rows) ++k;
-            if (segs[j].rows * (nh / nkv) <= 16 && k - j > run_n) { run0 = j; run_n = k - j; }
-            j = k;
-        }
-        if (run_n < 2 || run_n > 64 || run_n * nkv > 256) run_n = 0;
-    }
-    const bool multi_attn = run_n > 0;
-    const bool all_multi = multi_attn && run_n == nseg;          // every segment of the step is in the run (a round of talking streams only)
-    const StepState* seg_states = nullptr;
-    if (multi_attn) {
-        const int slot = c->seg_slot;
-        StepState* hs = c->seg_host + (size_t)slot * 64; StepState* ds = c->seg_dev + (size_t)slot * 64;
-        c->seg_slot = (slot + 1) & 7;
-        if (!c->seg_event[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->seg_event[slot], hipEventDisableTiming));
-        else HIPCHK(c, hipEventSynchronize(c->seg_event[slot]));          // (eight steps old: long done unless the caller queues steps without ever synchronising)
-        for (int j = 0; j < run_n; ++j) { mmd_stream* sj = segs[run0 + j].s; hs[j].n_ctx = sj->len; hs[j].cap = sj->cap; hs[j].K = sj->K; hs[j].V = sj->V; hs[j].n_prev = 0; hs[j].pad = 0; }
-        HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(StepState) * run_n, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipEventRecord(c->seg_event[slot], st));
-        seg_states = ds;
-    }
-    // rows <= 4, head_dim 128: the attention kernel prepares q / k / v from the qkv slabs itself (AttnArgs::qkv_slabs)
-    const bool rope_fused = (chain || (fused && all_multi && S <= 16)) && d == 128 && !c->no_rope_fuse;
-    if (rope_fused) for (int j = 0; j < nseg; ++j) HIPCHK(c, launch_rope_table((char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8, segs[j].rows, 64, c->inv_freq, segs[j].s->len, st, dyn));
-    // chunks (bf16, head_dim 128): one (cos, sin) table per step and segment, read by the vectorised RoPE + append kernel of every layer; MMDUET_NO_CHUNK_ROPE=1 keeps the scalar kernel
-    static const bool no_chunk_rope = getenv("MMDUET_NO_CHUNK_ROPE") != nullptr;
-    const bool chunk_rope = !fused && dt == MMD_BF16 && d == 128 && S >= 64 && !no_chunk_rope && !c->no_fuse;
-    if (chunk_rope) for (int j = 0; j < nseg; ++j) HIPCHK(c, launch_rope_table((char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8, segs[j].rows, 64, c->inv_freq, segs[j].s->len, st, nullptr));
-    // The hidden states of a chunk's LAST layer are read at a few rows only (the frame-end rows of the two heads, the row whose logits are wanted); its K / V must exist
-    // for every token, but its o_proj and MLP are row-wise: they run on the rows somebody reads, through the weight-streaming kernels (M <= 64).  The reference computes all
-    // rows and drops them (the lm_head over all positions is "pure waste the build skips" -- the same holds one layer down).
-    // (Not for the fused schedule, S <= 256 -- ADVICE r04: there every GEMM of the layer is bound by the 466 MB of weights it streams, not by its rows; the row-gathered
-    //  last layer would stream the same weights for fewer rows and add the gather launches: nothing to win, so the gate is `!fused`, not a row count.)
-    bool sparse_last = false;
-    if (need_rows && n_need > 0 && n_need <= 64 && !fused && S > 64 && dt == MMD_BF16 && H <= 4096 && (H & 3) == 0 && !c->no_fuse && !c->full_last_layer && !hidden_out && !dyn) {
-        sparse_last = gemm_can_slab(dt, slab_args(c->l_q, nh * d, c->L[0].wo_p, n_need, H, nh * d)) && gemm_can_slab(dt, slab_args(c->l_act, I, c->L[0].wdown_p, n_need, H, I));
-        if (sparse_last) {
-            for (int k = 0; k < n_need; ++k) if (need_rows[k] < 0 || need_rows[k] >= S) FAIL(c, MMD_ERANGE, "needed row %d outside the step", need_rows[k]);
-        }
-    }
-    bool xn_ready = false;             // the previous layer's fused slab consumer already left this layer's normalised input in l_xn
+    const bool tile = p.schedule == STEP_TILE;
+    r.ch_fin.fin_h = c->l_h; r.ch_fin.fin_ssq = c->chain_ssq; r.ch_xn.xn_h = c->l_h; r.ch_xn.xn_ssq = c->chain_ssq; r.ch_xn.xn_eps = g.rms_norm_eps;
+    if (!tile) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, c->L[0].ln1, c->l_xn, S, H, g.rms_norm_eps, st)); }
+    if (p.run_n > 0) { rc = upload_seg_states(r); if (rc) return rc; }
+    // one (cos, sin) table per step and segment: read by the attention kernel's own q / k / v preparation, or by the vectorised RoPE + append kernel of every layer of a chunk
+    if (p.rope_fused || p.chunk_rope) for (int j = 0; j < nseg; ++j) HIPCHK(c, launch_rope_table((char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8, segs[j].rows, 64, c->inv_freq, segs[j].s->len, st, dyn));
     for (int i = 0; i < g.num_layers; ++i) {
-        LlmLayer& L = c->L[i];
         int splits = 1;
-        if (fused) {
-            ch_xn.xn_gamma = L.ln1;
-            rc = slab_gemm(c->l_xn, H, L.wqkv_p, c->qkv_w, H, &splits, L.wqkv_8, L.sqkv, chain && i > 0 ? &ch_xn : nullptr); if (rc) return rc;
-            if (!rope_fused || splits > 4) {          // (the attention kernel's own q / k / v preparation sums at most four slabs)
-                ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * c->qkv_w * e, 0);
-                for (int j = 0; j < nseg; ++j) {
-                    mmd_stream* sj = segs[j].s;
-                    const size_t le = kv_layer_elems(c, sj->cap);
-                    HIPCHK(c, launch_slab_rope_append(c->splitk_ws + (size_t)segs[j].row0 * c->qkv_w, splits, L.bqkv, segs[j].rows, nh, nkv, d, c->inv_freq, sj->len,
-                                                      (char*)c->l_q + (size_t)segs[j].row0 * nh * d * e, (char*)sj->K + (size_t)i * le * e, (char*)sj->V + (size_t)i * le * e, sj->cap, st, dyn, i, S));
-                }
-            }
-        } else {
-            if (!xn_ready) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, L.ln1, c->l_xn, S, H, g.rms_norm_eps, st)); }
-            xn_ready = false;
-            rc = gemm(c, c->l_xn, H, L.wqkv, H, L.bqkv, nullptr, 0, c->l_qkv, c->qkv_w, S, c->qkv_w, H, EPI_NONE, 0, GEMM_AUTO, L.wqkv_p, false, L.wqkv_8, L.sqkv); if (rc) return rc;
-            ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * c->qkv_w * e, 0);
-            for (int j = 0; j < nseg; ++j) {
-                mmd_stream* sj = segs[j].s;
-                const size_t le = kv_layer_elems(c, sj->cap);
-                if (chunk_rope) {          // vectorised form over the step's (cos, sin) table (built once, before the layer loop)
-                    HIPCHK(c, launch_rope_append_chunk((char*)c->l_qkv + (size_t)segs[j].row0 * c->qkv_w * e, segs[j].rows, nh, nkv, (char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8, sj->len,
-                                                       (char*)c->l_q + (size_t)segs[j].row0 * nh * d * e, (char*)sj->K + (size_t)i * le * e, (char*)sj->V + (size_t)i * le * e, sj->cap, st));
-                    continue;
-                }
-                HIPCHK(c, launch_rope_append(dt, (char*)c->l_qkv + (size_t)segs[j].row0 * c->qkv_w * e, segs[j].rows, nh, nkv, d, c->inv_freq, sj->len,
-                                             (char*)c->l_q + (size_t)segs[j].row0 * nh * d * e, (char*)sj->K + (size_t)i * le * e, (char*)sj->V + (size_t)i * le * e,
-                                             sj->cap, 1, st));
-            }
-        }
-        if (multi_attn) {
-            const int r0 = segs[run0].row0, rr = segs[run0].rows;
-            AttnArgs a; memset(&a, 0, sizeof(a));
-            a.q = (char*)c->l_q + (size_t)r0 * nh * d * e; a.ldq = (int64_t)nh * d; a.out = (char*)c->l_attn + (size_t)r0 * nh * d * e; a.ldo = (int64_t)nh * d;
-            a.k_ts = d; a.v_ts = d; a.v_transposed = 1;
-            a.S = rr; a.nh = nh; a.nkv = nkv; a.d = d; a.causal = 1; a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.layer = i;
-            a.segs = seg_states; a.nseg = run_n;
-            if (fused && rope_fused && splits <= 4) { a.qkv_slabs = c->splitk_ws + (size_t)r0 * c->qkv_w; a.slab_rows = S; a.n_slabs = splits; a.qkv_bias = L.bqkv; a.rope_tab = (char*)c->rope_tab + (size_t)r0 * 64 * 8; }
-            double kvb = 0, fl = 0;
-            for (int j = run0; j < run0 + run_n; ++j) { const double nk = (double)(segs[j].s->len + segs[j].rows); kvb += 2.0 * nk * nkv * d * e; fl += 4.0 * segs[j].rows * nk * nh * d; }
-            ProfScope ps(c, MMD_K_ATTN_LLM, kvb + 2.0 * rr * run_n * nh * d * e, fl);
-            { const hipError_t le = launch_attention_decode_multi(a, st); attn_last_form(c->last_form); HIPCHK(c, le); }
-        }
-        for (int j = 0; j < nseg; ++j) {
-            if (multi_attn && j >= run0 && j < run0 + run_n) continue;
-            mmd_stream* sj = segs[j].s;
-            const size_t le = kv_layer_elems(c, sj->cap);
-            const int Sj = segs[j].rows; const int64_t nj = sj->len;
-            AttnArgs a; memset(&a, 0, sizeof(a));
-            a.q = (char*)c->l_q + (size_t)segs[j].row0 * nh * d * e; a.ldq = (int64_t)nh * d;
-            a.K = (char*)sj->K + (size_t)i * le * e; a.V = (char*)sj->V + (size_t)i * le * e;
-            a.k_hs = sj->cap * d; a.k_ts = d; a.v_hs = sj->cap * d; a.v_ts = d;
-            a.out = (char*)c->l_attn + (size_t)segs[j].row0 * nh * d * e; a.ldo = (int64_t)nh * d;
-            a.S = Sj; a.nh = nh; a.nkv = nkv; a.d = d; a.n_ctx = nj; a.causal = 1; a.v_transposed = 1;
-            a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.variant = 0;
-            a.dyn = dyn; a.layer = i; a.dyn_splits = 64;
-            if (rope_fused && splits <= 4) { a.qkv_slabs = c->splitk_ws + (size_t)segs[j].row0 * c->qkv_w; a.slab_rows = S; a.n_slabs = splits; a.qkv_bias = L.bqkv; a.rope_tab = (char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8; }
-            double kvb = 2.0 * (double)(nj + Sj) * nkv * d * e;
-            ProfScope ps(c, MMD_K_ATTN_LLM, kvb + 2.0 * Sj * nh * d * e, 4.0 * Sj * (double)(nj + Sj) * nh * d);
-            { const hipError_t le = launch_attention(dt, a, st); attn_last_form(c->last_form); HIPCHK(c, le); }
-        }
-        const void* next_norm = (i + 1 < g.num_layers) ? c->L[i + 1].ln1 : c->fnorm;
-        void* next_xn = (i + 1 < g.num_layers) ? c->l_xn : c->l_hid;
-        if (sparse_last && i + 1 == g.num_layers) {
-            void* attn_c = c->l_q; void* h_c = c->l_qkv;          // (both dead here: the queries were consumed by the attention above, the fused qkv rows by RoPE + append)
-            { ProfScope ps(c, MMD_K_OTHER, 0, 0);
-              HIPCHK(c, launch_gather_rows2(c->l_attn, (int64_t)nh * d, attn_c, nh * d, c->l_h, H, h_c, H, need_rows, n_need, st)); }
-            int sp = 1;
-            rc = slab_gemm(attn_c, (int64_t)nh * d, L.wo_p, H, nh * d, &sp, L.wo_8, L.so, nullptr, n_need); if (rc) return rc;
-            { ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * n_need * H * e, 0);
-              HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, sp, n_need, H, h_c, h_c, L.ln2, g.rms_norm_eps, c->l_xn, st)); }
-            rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, n_need, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu); if (rc) return rc;
-            rc = slab_gemm(c->l_act, I, L.wdown_p, H, I, &sp, L.wdown_8, L.sdown, nullptr, n_need); if (rc) return rc;
-            { ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * n_need * H * e, 0);
-              HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, sp, n_need, H, h_c, h_c, c->fnorm, g.rms_norm_eps, c->l_hid, st)); }
-            c->hid_compact = n_need;
-            xn_ready = true;          // (the final norm is done)
-            continue;
-        }
-        if (chain) {
-            rc = slab_gemm(c->l_attn, (int64_t)nh * d, L.wo_p, H, nh * d, &splits, L.wo_8, L.so, &ch_fin); if (rc) return rc;
-            ch_xn.xn_gamma = L.ln2;
-            rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, S, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu, &ch_xn); if (rc) return rc;
-            const bool last = i + 1 == g.num_layers;              // the caller wants the final norm's output materialised
-            rc = slab_gemm(c->l_act, I, L.wdown_p, H, I, &splits, L.wdown_8, L.sdown, last ? nullptr : &ch_fin); if (rc) return rc;
-            if (last) {
-                ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e, 0);
-                HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, splits, S, H, c->l_h, c->l_h, next_norm, g.rms_norm_eps, next_xn, st));
-            }
-        } else if (fused) {
-            rc = slab_gemm(c->l_attn, (int64_t)nh * d, L.wo_p, H, nh * d, &splits, L.wo_8, L.so); if (rc) return rc;
-            { ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e, 0);
-              HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, splits, S, H, c->l_h, c->l_h, L.ln2, g.rms_norm_eps, c->l_xn, st)); }
-            rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, S, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu); if (rc) return rc;
-            rc = slab_gemm(c->l_act, I, L.wdown_p, H, I, &splits, L.wdown_8, L.sdown); if (rc) return rc;
-            ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e, 0);
-            HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, splits, S, H, c->l_h, c->l_h, next_norm, g.rms_norm_eps, next_xn, st));
-        } else {
-            rc = gemm(c, c->l_attn, (int64_t)nh * d, L.wo, (int64_t)nh * d, nullptr, c->l_h, H, c->l_h, H, S, H, nh * d, EPI_RESID, 0, GEMM_AUTO, L.wo_p, false, L.wo_8, L.so); if (rc) return rc;
-            { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, L.ln2, c->l_xn, S, H, g.rms_norm_eps, st)); }
-            // (the SwiGLU product has ONE reader, down_proj: piece-major when both run on the ring kernel -- every bf16 chunk of >= 512 rows)
-            const bool pm = !L.sgu && !L.sdown && gemm_pair_pm(c, false, c->l_xn, H, L.wgu_p, nullptr, 2 * I, H, EPI_SWIGLU, c->l_act, I, L.wdown_p, H, c->l_h, H, c->l_h, H, EPI_RESID, S);
-            rc = gemm(c, c->l_xn, H, L.wgu, H, nullptr, nullptr, 0, c->l_act, I, S, 2 * I, H, EPI_SWIGLU, 0, GEMM_AUTO, L.wgu_p, false, L.wgu_8, L.sgu, nullptr, nullptr, pm ? 2 : 0); if (rc) return rc;
-            // a split-K down_proj (long K, under one block wave of tiles: every chunk) leaves its fp32 slabs; ONE pass then sums them, adds the residual stream, and
-            // normalises for the next layer (or the final norm) -- instead of splitk_reduce (+ residual) followed by a separate RMSNorm launch re-reading the row
-            int rs = 0;
-            rc = gemm(c, c->l_act, I, L.wdown, I, nullptr, c->l_h, H, c->l_h, H, S, H, I, EPI_RESID, 0, GEMM_AUTO, L.wdown_p, false, L.wdown_8, L.sdown, nullptr,
-                      (dt == MMD_BF16 && H <= 4096 && (H & 3) == 0 && !c->no_fuse && !c->no_slab_norm) ? &rs : nullptr, pm ? 1 : 0); if (rc) return rc;
-            if (rs > 1) {
-                ProfScope ps(c, MMD_K_NORM_ROPE, 4.0 * S * H * e + 4.0 * rs * S * H, 0);
-                HIPCHK(c, launch_slab_resid_rmsnorm(c->splitk_ws, rs, S, H, c->l_h, c->l_h, next_norm, g.rms_norm_eps, next_xn, st, L.sdown));          // (fp8 matrices: the tile GEMM's slabs are unscaled)
-                xn_ready = true;
-            }
-        }
+        rc = layer_qkv(r, i, &splits); if (rc) return rc;
+        rc = layer_attention(r, i, splits); if (rc) return rc;
+        if (p.sparse_last && i + 1 == g.num_layers) rc = layer_tail_sparse_last(r, i);
+        else rc = p.schedule == STEP_CHAIN ? layer_tail_chain(r, i) : p.schedule == STEP_FUSED ? layer_tail_fused(r, i) : layer_tail_tile(r, i);
+        if (rc) return rc;
     }
-    if (!fused && !xn_ready) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, c->fnorm, c->l_hid, S, H, g.rms_norm_eps, st)); }
+    if (tile && !r.xn_ready) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, c->fnorm, c->l_hid, S, H, g.rms_norm_eps, st)); }
     if (hidden_out) HIPCHK(c, hipMemcpyAsync(hidden_out, c->l_hid, (size_t)S * H * e, hipMemcpyDeviceToDevice, st));
     if (!dyn) for (int j = 0; j < nseg; ++j) segs[j].s->len += segs[j].rows;
     return MMD_OK;
@@ -1501,10 +1500,10 @@ extern "C" int mmd_llm_step_multi(mmd_ctx* c, mmd_stream* const* streams, const 
     return llm_step_segs(c, segs.data(), n_segs, embeds, S, hidden_out, nullptr);
 }
 
-// the rows whose final hidden state a step's caller reads, `a` first and `b` behind it (llm_step_segs may then leave l_hid compact, in this order); more than 64: no list
-static int build_need_list(const int32_t* a, int na, const int32_t* b, int nb, int32_t need[64]) {
+// the rows whose final hidden state a step's caller reads, `a` first and `b` behind it (llm_step_segs may then leave l_hid compact, in this order); more than STEP_NEED_MAX: no list
+static int build_need_list(const int32_t* a, int na, const int32_t* b, int nb, int32_t need[STEP_NEED_MAX]) {
     int n = 0;
-    if (na + nb <= 64) { for (int i = 0; i < na; ++i) need[n++] = a[i]; for (int i = 0; i < nb; ++i) need[n++] = b[i]; }
+    if (na + nb <= STEP_NEED_MAX) { for (int i = 0; i < na; ++i) need[n++] = a[i]; for (int i = 0; i < nb; ++i) need[n++] = b[i]; }
     return n;
 }
 // enqueue the 4 head logits of n rows of l_hid (`compact`: its first n rows) and their copy into heads_host; the caller synchronises and reads heads_host
@@ -1529,7 +1528,7 @@ extern "C" int mmd_frame_step_multi(mmd_ctx* c, mmd_stream* const* streams, cons
     if ((n_head_rows && (!head_rows || !heads_out_host)) || (n_hidden_rows && (!hidden_rows || !hidden_rows_out))) FAIL(c, MMD_EINVAL, "null row/result pointer");
     for (int i = 0; i < n_head_rows; ++i) if (head_rows[i] < 0 || head_rows[i] >= S) FAIL(c, MMD_ERANGE, "head row %d outside the step", head_rows[i]);
     for (int i = 0; i < n_hidden_rows; ++i) if (hidden_rows[i] < 0 || hidden_rows[i] >= S) FAIL(c, MMD_ERANGE, "hidden row %d outside the step", hidden_rows[i]);
-    int32_t need[64]; const int n_need = build_need_list(head_rows, n_head_rows, hidden_rows, n_hidden_rows, need);          // heads first, then the hidden / logit rows
+    int32_t need[STEP_NEED_MAX]; const int n_need = build_need_list(head_rows, n_head_rows, hidden_rows, n_hidden_rows, need);          // heads first, then the hidden / logit rows
     rc = llm_step_segs(c, segs.data(), n_segs, embeds, S, nullptr, nullptr, n_need ? need : nullptr, n_need); if (rc) return rc;
     const bool compact = c->hid_compact > 0;
     hipStream_t st = c->stream; const int H = c->cfg.hidden_size; const size_t e = es(c);
@@ -1691,7 +1690,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         rc = dev_alloc(c, (void**)&c->round_toks_dev, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)); if (rc) return rc;
         HIPCHK(c, hipHostMalloc((void**)&c->round_toks_host, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)));
     }
-    int32_t need[64]; const int n_need = build_need_list(head_rows, n_head_rows, sample_row, n_sample, need);          // the heads' rows first, then the sampling rows
+    int32_t need[STEP_NEED_MAX]; const int n_need = build_need_list(head_rows, n_head_rows, sample_row, n_sample, need);          // the heads' rows first, then the sampling rows
     rc = llm_step_segs(c, segs.data(), n_segs, c->l_h, S, nullptr, nullptr, n_need ? need : nullptr, n_need); if (rc) return rc;
     const bool compact = c->hid_compact > 0;
     if (n_sample) {
@@ -1813,7 +1812,7 @@ extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int
     for (int i = 0; i < n_rows; ++i) if (rows_host[i] < 0 || rows_host[i] >= S) FAIL(c, MMD_ERANGE, "head row %d outside the step", rows_host[i]);
     if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
     StepSeg one{s, 0, S};
-    int32_t need[64]; const int n_need = build_need_list(rows_host, n_rows, nullptr, 0, need);
+    int32_t need[STEP_NEED_MAX]; const int n_need = build_need_list(rows_host, n_rows, nullptr, 0, need);
     int rc = S > 0 ? llm_step_segs(c, &one, 1, embeds, S, nullptr, nullptr, n_need ? need : nullptr, n_need) : MMD_OK; if (rc) return rc;
     if (n_rows == 0) return MMD_OK;
     rc = read_head_rows(c, rows_host, n_rows, c->hid_compact > 0); if (rc) return rc;
@@ -1932,7 +1931,7 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     // (~255 kernels) instead of launching them one by one -- the decode step is made of 5-50 us kernels and is otherwise
     // paced by host launch latency.
     const bool more = !stop && max_new > 1;
-    const bool can_graph = more && !c->no_graph && !c->no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr &&
+    const bool can_graph = more && !c->no_graph && !c->sw.no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr &&
                            g.hidden_size <= 4096 && g.head_dim == 128;     // head_dim 128: the attention kernel that reads *dyn
     if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
     if (can_graph || (samp && more)) {          // the sampled step reads the list length through *step_dev on the eager route too
@@ -2132,6 +2131,7 @@ extern "C" int mmd_op_gemm_last_plan(mmd_ctx* c, int* out4) {
 }
 // the decode steps of the most recent generate call: 0 none or eager, 1 replayed an existing captured step, 2 captured in that call, then replayed
 extern "C" int mmd_op_decode_last_route(mmd_ctx* c) { return c ? c->dec_route : MMD_EINVAL; }
+extern "C" int mmd_op_step_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < STEP_PLAN_FIELDS; ++i) out[i] = c->step_last[i]; return MMD_OK; }
 // times one GEMM shape on the context's stream with HIP events (weights packed once, outside the timed region)
 extern "C" int mmd_op_gemm_bench(mmd_ctx* c, int M, int N, int K, int epi, int variant, int iters, float* avg_ms_out, const void* Xin, const void* Win) {
     if (!c || !avg_ms_out || iters <= 0) return MMD_EINVAL;

@@ -852,6 +852,14 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         1 replayed an existing captured step, 2 captured the step in that call, then replayed it."""
         return int(lib().mmd_op_decode_last_route(self._ctx))
 
+    STEP_PLAN_FIELDS = ('schedule', 'rope_fused', 'chunk_rope', 'sparse_last', 'run0', 'run_n', 'run_all', 'down_slab_norm', 'mlp_pm')
+
+    def step_last_plan(self):
+        """The schedule the most recent LLM step took (mmd_op_step_last_plan): a dict over STEP_PLAN_FIELDS; schedule 0 tile, 1 fused slabs, 2 decode chain."""
+        out = (C.c_int * len(self.STEP_PLAN_FIELDS))()
+        check(lib().mmd_op_step_last_plan(self._ctx, out), self._ctx, 'step_last_plan')
+        return dict(zip(self.STEP_PLAN_FIELDS, out))
+
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, frames=None, past_key_values=None, max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  repetition_penalty=None, eos_token_id=None, seed=None, return_dict_in_generate=False, **kwargs):

@@ -188,6 +188,12 @@ def test_greedy_generate_rejects_an_empty_prompt(graph_model):
         fast_greedy_generate(model=m, inputs_embeds=empty, past_key_values=None, eos_token_id=-1, inplace_output_ids=torch.zeros(1, 4, dtype=torch.long, device='cuda'))
 
 
+def _switches(env):
+    """the schedule switches that are on in a subprocess's extra environment (MMDUET_NO_FUSE=0 is off), sorted"""
+    import step_regimes
+    return tuple(sorted(k for k, v in env.items() if k in step_regimes.SWITCHES and v != '0'))
+
+
 def test_fused_and_unfused_schedules_agree(true_shape, monkeypatch):
     """The fused slab consumers (reduce+RoPE+append, reduce+residual+RMSNorm) keep the unfused rounding points."""
     import subprocess, sys, os, json
@@ -203,21 +209,30 @@ pcfg = VideoHeadLiveLlavaQwenConfig(vocab_size=2048, num_hidden_layers=2, vit_nu
 m = VideoHeadLiveLlavaQwenForCausalLM(pcfg, torch_dtype=torch.bfloat16, max_vit_batch=1, max_step_tokens=int(os.environ.get('MMD_MAX_STEP', 128)), kv_initial_tokens=int(os.environ.get('MMD_KV_TOKENS', 512)))
 m.load_state_dict(w)
 g = torch.Generator().manual_seed(5)
-c = None; res = []
+c = None; res = []; plans = []
 for S in [int(v) for v in os.environ['MMD_SIZES'].split(',')]:
     x = (torch.randn(1, S, 3584, generator=g) * 0.5).to(torch.bfloat16).cuda()
     o = m(inputs_embeds=x, past_key_values=c); c = o.past_key_values
     res.append(o.informative_logits[0, -1].tolist() + o.logits[0, -1, :8].tolist())
+    plans.append(m.step_last_plan())
 print("RES " + json.dumps(res))
+print("PLANS " + json.dumps(plans))
 '''
     from conftest import ROOT
+    plans = {}          # the step_last_plan() of every forward of a run, by (sizes, switches)
     def run(sizes='49,1,30,5,16,1,3', **kw):
         env = dict(os.environ, MMD_ROOT=ROOT, MMD_SIZES=sizes, **kw)
         r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
+        plans[(sizes, _switches(kw))] = json.loads([l for l in r.stdout.splitlines() if l.startswith('PLANS ')][0][6:])
         return json.loads([l for l in r.stdout.splitlines() if l.startswith('RES ')][0][4:])
     # one K slab per decode GEMV: same reduction order, same rounding points -> bit-identical
     assert run('49,1,30', MMDUET_NO_FUSE='0', MMDUET_GEMV_KSPLIT_SHORT='1', MMDUET_NO_CHAIN='1') == run('49,1,30', MMDUET_NO_FUSE='1', MMDUET_GEMV_KSPLIT_SHORT='1')
+    # ... and the two runs really took two schedules: fused slabs (no chain) against tile in every step, nothing else apart
+    fused_run, tile_run = plans[('49,1,30', ('MMDUET_NO_CHAIN',))], plans[('49,1,30', ('MMDUET_NO_FUSE',))]
+    assert [p['schedule'] for p in fused_run] == [1, 1, 1] and [p['schedule'] for p in tile_run] == [0, 0, 0]
+    assert all({f for f in a if a[f] != b[f]} == {'schedule'} for a, b in zip(fused_run, tile_run))
+    paired = {('49,1,30', ('MMDUET_NO_CHAIN',)), ('49,1,30', ('MMDUET_NO_FUSE',))}          # switched runs whose plans were compared with their partner's
     # the shipped schedule sums the decode qkv / o products in two fp32 K slabs and (rows <= 16) takes the RMSNorm statistics from per-n-tile
     # partial sums (GemvChain): different fp32 summation orders, bf16-rounding-level apart -- and deterministic run to run
     a, b, a2 = run(MMDUET_NO_FUSE='0'), run(MMDUET_NO_FUSE='1'), run(MMDUET_NO_FUSE='0')
@@ -258,6 +273,21 @@ print("RES " + json.dumps(res))
     ref = run(long_ctx, MMDUET_NO_FUSE='1', MMD_KV_TOKENS='16384')          # unfused launch schedule throughout
     for ra, rb in zip(got[-5:], ref[-5:]):
         assert ra == pytest.approx(rb, abs=3e-2, rel=3e-2)
+    # every switch really switched: against the run of the same sizes without it, the plan field it governs differs in at least one step and no other field in any
+    # (MMDUET_NO_FUSE=1 takes every fused form away; MMDUET_NO_CHAIN also ends the chain's q / k / v preparation inside the attention kernel)
+    governs = {'MMDUET_NO_FUSE': ('schedule', 'rope_fused', 'chunk_rope', 'down_slab_norm', 'mlp_pm'), 'MMDUET_NO_CHAIN': ('schedule', 'rope_fused'),
+               'MMDUET_NO_ROPE_FUSE': ('rope_fused',), 'MMDUET_NO_SLAB_NORM': ('down_slab_norm',), 'MMDUET_NO_CHUNK_ROPE': ('chunk_rope',)}
+    compared = set()
+    for (sizes, sw), with_switch in plans.items():
+        for name in sw:
+            base = plans.get((sizes, tuple(k for k in sw if k != name)))
+            if base is None:
+                continue          # (`paired` below: a switched run nobody compared fails the test)
+            diff = {f for a, b in zip(base, with_switch) for f in a if a[f] != b[f]}
+            assert governs[name][0] in diff and diff <= set(governs[name]), (sizes, sw, name, diff)
+            compared.add(name); paired.add((sizes, sw))
+    assert compared == set(governs)
+    assert {k for k in plans if k[1]} == paired, {k for k in plans if k[1]} - paired          # every run with a switch had a partner
 
 
 def test_chunk_last_layer_on_read_rows_only(true_shape):
@@ -278,26 +308,32 @@ m = VideoHeadLiveLlavaQwenForCausalLM(pcfg, torch_dtype=torch.bfloat16, max_vit_
 m.load_state_dict(w)
 g = torch.Generator().manual_seed(11)
 def rnd(S): return (torch.randn(S, 3584, generator=g) * 0.5).to(torch.bfloat16).cuda()
-res = []
+res = []; plans = []
 # single stream: 64 frame-end rows of a 640-row chunk, then one row twice + the first row of a 333-row chunk, then 65 rows (all rows computed), then a small step
 c = None
 for S, rows in ((640, list(range(9, 640, 10))), (333, [332, 332, 0]), (130, list(range(0, 130, 2))), (5, [4])):
     h, c = m.frame_step(rnd(S), c, rows)
-    res.append(h.flatten().tolist())
+    res.append(h.flatten().tolist()); plans.append(m.step_last_plan())
 # two streams in one forward: heads on one, last-row logits on the other; then each stream alone on a small step
 a = m.multi_step([dict(x=rnd(300), cache=None, head_rows=[99, 199, 299], hidden='none'), dict(x=rnd(150), cache=None, head_rows=[], hidden='last')], want_logits=True)
-res.append(a[0]['heads'].flatten().tolist() + a[1]['logits'][0, :16].float().cpu().tolist() + a[1]['hidden'].float().cpu().flatten()[:16].tolist())
+res.append(a[0]['heads'].flatten().tolist() + a[1]['logits'][0, :16].float().cpu().tolist() + a[1]['hidden'].float().cpu().flatten()[:16].tolist()); plans.append(m.step_last_plan())
 for k in (0, 1):
-    h, _ = m.frame_step(rnd(3), a[k]['cache'], [2]); res.append(h.flatten().tolist())
+    h, _ = m.frame_step(rnd(3), a[k]['cache'], [2]); res.append(h.flatten().tolist()); plans.append(m.step_last_plan())
 print("RES " + json.dumps(res))
+print("PLANS " + json.dumps(plans))
 '''
     from conftest import ROOT
+    plans = []
     def run(**kw):
         env = dict(os.environ, MMD_ROOT=ROOT, **kw)
         r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
+        plans.append(json.loads([l for l in r.stdout.splitlines() if l.startswith('PLANS ')][0][6:]))
         return json.loads([l for l in r.stdout.splitlines() if l.startswith('RES ')][0][4:])
     a, b, a2 = run(), run(MMDUET_FULL_LAST_LAYER='1'), run()
+    # the switch really switched: the last layer ran on the read rows in the 640-, 333- and 450-row steps without it, in none with it, and nothing else changed
+    assert [p['sparse_last'] for p in plans[0]] == [1, 1, 0, 0, 1, 0, 0] and not any(p['sparse_last'] for p in plans[1])
+    assert all({f for f in x if x[f] != y[f]} <= {'sparse_last'} for x, y in zip(plans[0], plans[1])) and plans[0] == plans[2]
     assert a == a2
     assert len(a[0]) == 64 * 4 and len(a[2]) == 65 * 4
     for ra, rb in zip(a, b):
