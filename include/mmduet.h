@@ -316,6 +316,19 @@ int mmd_op_resid32_layernorm(mmd_ctx* ctx, const void* y16, float* h32, const vo
 /* q [S, nh*d] (rotated in place), k/v [S, nkv*d] appended rotated/unrotated at pos0.. into Kc/Vc [nkv, cap, d] */
 int mmd_op_rope_append(mmd_ctx* ctx, void* qkv, int S, int nh, int nkv, int d, float theta, int64_t pos0, void* q_out,
                        void* Kc, void* Vc, int64_t cap);
+/* the code that writes the KV arena, one `writer` at a time, on caller-owned Kc / Vc [nkv, cap, d] (parity tests of the arena's contents):
+ *   0 rope_append_kernel, row-major V (mmd_op_rope_append)      1 rope_append_kernel, V in transposed 64-token blocks (fp32 contexts, tile steps under 64 rows)
+ *   2 rope_append_chunk_kernel over the step's (cos, sin) table (bf16, d = 128)      3 slab_rope_append_kernel (bf16)
+ *   4 the decode attention's fused q / k / v preparation (bf16, d = 128, S * nh / nkv <= 16, n_slabs <= 4): attention variant 3 over n_ctx = pos0 context tokens already in
+ *     Kc / Vc, result in attn_out [S, nh*d]; q_out is not written (q never leaves the kernel).
+ * src: writers 0-2 the fused qkv rows [S, (nh + 2 nkv) d] in the context dtype; writers 3 / 4 the first row of this step inside fp32 split-K slabs [n_slabs][slab_rows][(nh + 2 nkv) d]
+ * with bias [(nh + 2 nkv) d] (bf16).  inv_freq_host [d / 2]: the RoPE frequencies, used as given.  Transposed V needs cap % 64 == 0.  An unsupported combination is
+ * MMD_EINVAL before anything is launched.  Synchronises the stream. */
+int mmd_op_kv_write(mmd_ctx* ctx, int writer, const void* src, int n_slabs, int slab_rows, const void* bias, const float* inv_freq_host, int S, int nh, int nkv, int d,
+                    int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, void* attn_out);
+/* the first n tokens (n % 64 == 0, n <= mmd_kv_capacity) of one layer of a stream's arena AS STORED: K_out [nkv, n, d] rotated rows, V_out [nkv, n / 64, d, 64] transposed
+ * 64-token blocks (token t, dim e of a head at ((t >> 6) * d + e) * 64 + (t & 63)); device buffers in the context dtype.  Synchronises the stream. */
+int mmd_kv_debug_read(mmd_stream* s, int layer, int64_t n, void* K_out, void* V_out);
 /* causal GQA attention with query offset: q [S, nh*d], Kc/Vc [nkv, cap, d], n_ctx = tokens before this step;
  * out [S, nh*d].  causal = 0 -> full attention over n_ctx + S keys.  variant: 0 auto, 1 simple, 2 mfma, 3 the arena kernels (attn_gqa128_kernel), 4 row-major
  * K / V (the tower's), 5 attn_gqa128_w1_kernel, 6 attn_gqa128_chunk_kernel. */

@@ -1204,6 +1204,23 @@ extern "C" int mmd_kv_debug_set_len(mmd_stream* s, int64_t n) {
     return MMD_OK;
 }
 
+// test aid (tests/test_gpu_kv_arena.py): the first n tokens of one layer as the arena stores them -- K_out [nkv, n, d], V_out [nkv, n / 64, d, 64] (device, context dtype).
+// Nothing is un-transposed and no address beyond token n of a row is touched (the row stride may be virtual).  Synchronises the stream.
+extern "C" int mmd_kv_debug_read(mmd_stream* s, int layer, int64_t n, void* K_out, void* V_out) {
+    if (!s) return MMD_EINVAL;
+    mmd_ctx* c = s->ctx;
+    if (!K_out || !V_out || layer < 0 || layer >= c->cfg.num_layers) FAIL(c, MMD_EINVAL, "kv_debug_read: layer %d of %d, or an output buffer missing", layer, c->cfg.num_layers);
+    if (n < 0 || (n % 64) != 0 || n > s->mapped) FAIL(c, MMD_EINVAL, "kv_debug_read: n = %lld must be a multiple of 64 within the %lld tokens backed by memory", (long long)n, (long long)s->mapped);
+    hipSetDevice(c->device);
+    const size_t e = es(c), tok = (size_t)c->cfg.head_dim * e, le = kv_layer_elems(c, s->cap) * e;
+    const int64_t pitch = (int64_t)((size_t)s->cap * tok / 4), w = (int64_t)((size_t)n * tok / 4);          // in 4-byte units, like the stash copies
+    if (w > 0x7fffffff / c->cfg.num_kv_heads) FAIL(c, MMD_EINVAL, "kv_debug_read: %lld tokens are more than one copy launch takes", (long long)n);
+    HIPCHK(c, launch_copy_rows(MMD_F32, (const char*)s->K + (size_t)layer * le, pitch, K_out, w, c->cfg.num_kv_heads, (int)w, c->stream));
+    HIPCHK(c, launch_copy_rows(MMD_F32, (const char*)s->V + (size_t)layer * le, pitch, V_out, w, c->cfg.num_kv_heads, (int)w, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MMD_OK;
+}
+
 static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need) {
     if (need <= s->mapped) return MMD_OK;
     if (s->vmm) return vmm_map_upto(c, s, need);            // growth = more pages behind the same addresses: no copy, no second arena
@@ -2191,6 +2208,49 @@ extern "C" int mmd_op_resid32_layernorm(mmd_ctx* c, const void* y16, float* h32,
     if (!y16 || !h32 || (w16 && (!b16 || !out16)) || (pos16 && period <= 0)) FAIL(c, MMD_EINVAL, "resid32_layernorm: missing operand");
     if (outbf && w16) FAIL(c, MMD_EINVAL, "resid32_layernorm: outbf (the tower's final bf16 result: h32 is not rewritten) and a LayerNorm output are exclusive");
     HIPCHK(c, launch_resid32_layernorm(y16, h32, pos16, period, w16, b16, out16, outbf, M, H, eps, c->stream)); return MMD_OK;
+}
+// every piece of code that writes the KV arena, on caller-owned buffers (tests/test_gpu_kv_write.py): what is refused here is refused before any launch
+extern "C" int mmd_op_kv_write(mmd_ctx* c, int writer, const void* src, int n_slabs, int slab_rows, const void* bias, const float* inv_freq_host, int S, int nh, int nkv, int d,
+                               int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, void* attn_out) {
+    if (!c) return MMD_EINVAL;
+    if (!src || !inv_freq_host || !Kc || !Vc) FAIL(c, MMD_EINVAL, "kv_write: missing operand");
+    if (writer < 0 || writer > 4) FAIL(c, MMD_EINVAL, "kv_write: writer %d (0 .. 4)", writer);
+    if (S < 1 || nh < 1 || nkv < 1 || (nh % nkv) != 0 || d < 2 || (d & 1) || pos0 < 0 || cap < 1 || pos0 + S > cap) FAIL(c, MMD_EINVAL, "kv_write: shape (S %d, heads %d / %d, d %d, tokens [%lld, %lld) of %lld)", S, nh, nkv, d, (long long)pos0, (long long)pos0 + S, (long long)cap);
+    if (writer >= 1 && (cap % 64) != 0) FAIL(c, MMD_EINVAL, "kv_write: the transposed V layout needs cap %% 64 == 0");
+    if (writer >= 2 && c->cfg.dtype != MMD_BF16) FAIL(c, MMD_EINVAL, "kv_write: writer %d is a bf16 kernel", writer);
+    if ((writer == 2 || writer == 4) && d != 128) FAIL(c, MMD_EINVAL, "kv_write: writer %d needs head_dim 128", writer);
+    if (writer <= 3 && !q_out) FAIL(c, MMD_EINVAL, "kv_write: q_out missing");
+    if (writer >= 3 && (!bias || slab_rows < S)) FAIL(c, MMD_EINVAL, "kv_write: the slab writers need a bias and slab_rows >= S");
+    if (writer == 3 && (n_slabs < 1 || n_slabs > 16)) FAIL(c, MMD_EINVAL, "kv_write: 1 .. 16 slabs");
+    if (writer == 4 && (n_slabs < 1 || n_slabs > 4 || S * (nh / nkv) > 16 || !attn_out)) FAIL(c, MMD_EINVAL, "kv_write: the decode attention takes 1 .. 4 slabs, S x G <= 16 and an output buffer");
+    hipSetDevice(c->device);
+    const int half = d / 2;
+    float* freq = nullptr; void* tab = nullptr;
+    HIPCHK(c, hipMalloc((void**)&freq, sizeof(float) * half));
+    auto done = [&](int rc) { hipStreamSynchronize(c->stream); hipFree(freq); if (tab) hipFree(tab); return rc; };
+    hipError_t e = hipMemcpyAsync(freq, inv_freq_host, sizeof(float) * half, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && (writer == 2 || writer == 4)) {
+        e = hipMalloc(&tab, (size_t)S * half * sizeof(float) * 2);
+        if (e == hipSuccess) e = launch_rope_table(tab, S, half, freq, pos0, c->stream);
+    }
+    // (the split-KV workspace of a context that never ran a step: 128 MiB as in mmd_op_attention, an arbitrary test size that stays with the context -- not the model's own sizing)
+    if (e == hipSuccess && writer == 4 && !c->attn_ws) { c->attn_bytes = (size_t)128 << 20; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return done(rc); }
+    if (e == hipSuccess) {
+        if (writer <= 1) e = launch_rope_append(c->cfg.dtype, src, S, nh, nkv, d, freq, pos0, q_out, Kc, Vc, cap, writer, c->stream);
+        else if (writer == 2) e = launch_rope_append_chunk(src, S, nh, nkv, tab, pos0, q_out, Kc, Vc, cap, c->stream);
+        else if (writer == 3) e = launch_slab_rope_append((const float*)src, n_slabs, bias, S, nh, nkv, d, freq, pos0, q_out, Kc, Vc, cap, c->stream, nullptr, 0, slab_rows);
+        else {
+            AttnArgs a; memset(&a, 0, sizeof(a));
+            a.q = nullptr; a.ldq = (int64_t)nh * d; a.K = Kc; a.V = Vc; a.k_hs = cap * d; a.k_ts = d; a.v_hs = cap * d; a.v_ts = d; a.v_transposed = 1; a.out = attn_out; a.ldo = (int64_t)nh * d;
+            a.S = S; a.nh = nh; a.nkv = nkv; a.d = d; a.n_ctx = pos0; a.causal = 1; a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.variant = 3;
+            a.qkv_slabs = (const float*)src; a.slab_rows = slab_rows; a.n_slabs = n_slabs; a.qkv_bias = bias; a.rope_tab = tab;
+            e = launch_attention(c->cfg.dtype, a, c->stream);
+            attn_last_form(c->last_form);
+        }
+    }
+    const int rc = done(MMD_OK);
+    if (e != hipSuccess) FAIL(c, MMD_EHIP, "kv_write: writer %d failed: %s", writer, hipGetErrorString(e));
+    return rc;
 }
 extern "C" int mmd_op_rope_append(mmd_ctx* c, void* qkv, int S, int nh, int nkv, int d, float theta, int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap) {
     if (!c) return MMD_EINVAL; hipSetDevice(c->device);

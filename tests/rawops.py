@@ -127,6 +127,28 @@ class RawOps:
         check(lib().mmd_op_rope_append(self.ctx, _ptr(qd), S, nh, nkv, d, theta, pos0, _ptr(q), _ptr(Kc), _ptr(Vc), Kc.shape[1]), self.ctx)
         return q
 
+    def kv_write(self, writer, src, inv_freq, nh, nkv, d, pos0, q_out, Kc, Vc, S=None, bias=None, row0=0, attn_out=None):
+        """mmd_op_kv_write on caller-owned device buffers.  Writers 0-2: src = qkv [S, w].  Writers 3 / 4: src = fp32 slabs [n_slabs, slab_rows, w], this step's S rows
+        start at slab row `row0`.  inv_freq: CPU fp32 [d / 2].  -> the return code (nothing raises: refusals are part of what is tested)."""
+        w = (nh + 2 * nkv) * d
+        n_slabs, slab_rows, at = 0, 0, src.data_ptr()
+        if writer >= 3:
+            n_slabs, slab_rows = src.shape[0], src.shape[1]
+            at += row0 * w * 4
+        else:
+            S = src.shape[0]
+        fr = inv_freq.contiguous().float()
+        self.m._bind_stream()
+        rc = lib().mmd_op_kv_write(self.ctx, writer, C.c_void_p(at), n_slabs, slab_rows, _ptr(bias), C.c_void_p(fr.data_ptr()), S, nh, nkv, d, pos0, _ptr(q_out), _ptr(Kc), _ptr(Vc),
+                                   Kc.shape[1], _ptr(attn_out))
+        torch.cuda.synchronize()
+        return rc
+
+    def attention_last_form(self):
+        f = (C.c_int * 2)()
+        check(lib().mmd_op_attention_last_form(self.ctx, f), self.ctx, 'attention_last_form')
+        return tuple(f)
+
     def attention(self, q, Kc, Vc, nh, nkv, d, n_ctx, causal=True, variant=0):
         S = q.shape[0]
         o = torch.empty(S, nh * d, device=self.dev, dtype=self.dtype); self.m._bind_stream()
