@@ -242,6 +242,22 @@ int mmd_sample_generate(mmd_ctx* ctx, mmd_stream* s, const void* prompt_embeds, 
                         float temperature, int top_k, float top_p, uint64_t seed, uint64_t* offset_inout, int64_t* out_ids_host, int max_new, int* n_out);
 int mmd_set_sample_lane(mmd_ctx* ctx, int lane);
 
+/* Log-probabilities of the tokens the two generate calls above return (what HF exposes as output_scores + compute_transition_scores; no reference counterpart: the
+ * reference's loops keep the ids only).  For every returned token t (EOS included), with l the fp32 lm_head logits of its step:
+ *   logprob          = l[t] - logsumexp(l): the model's log-probability, -nll of mmd_lm_nll for label t;
+ *   sampling_logprob = z[t] - logsumexp over the kept set of z: under the distribution t was taken from (z = pen(l) / T and the kept set {z >= tau} of DESIGN.md "Sampling";
+ *                      after an arg-max T = 1 and everything is kept, i.e. log_softmax(pen(l))[t]);
+ *   top_n alternatives = the top_n largest raw logits by (value descending, index ascending), as ids and logprobs; id -1 and -inf where the vocabulary is shorter.
+ * The maximum is subtracted and mass is summed as in the sampling chain (trunc(exp(x - max) 2^40) in 64-bit integers, one writer per partial): a token's numbers do not depend
+ * on the grid.  A row with a NaN gives NaN (mmd_sample_generate still fails with MMD_EDOM).
+ * mmd_set_generate_logprobs: top_n = -1 off (the default: the generate calls enqueue what they enqueue without this feature), 0..8 on with that many alternatives; holds for the
+ * following generate calls of the context; anything else is MMD_ERANGE.  The captured decode step is keyed by the setting too.  The records stay on the device until
+ * mmd_generate_logprobs_read copies those of the most recent generate call (ONE copy, then a stream synchronisation): logprob_host / sampling_logprob_host float[cap_tokens],
+ * top_ids_host int64[cap_tokens, top_n], top_logprob_host float[cap_tokens, top_n] (host; each may be NULL); *n_out = that call's token count, 0 if it did not record;
+ * MMD_ERANGE if cap_tokens is smaller.  mmd_round_multi does not record. */
+int mmd_set_generate_logprobs(mmd_ctx* ctx, int top_n);
+int mmd_generate_logprobs_read(mmd_ctx* ctx, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out);
+
 /* ---- multi-GPU: the one collective of the path ------------------------------------------------------------------ */
 /* The reference shards videos over N manually launched processes (--start_idx/--end_idx, test/inference.py:337) and has no
  * collective; here one process per GPU gathers the per-frame head scores of its streams with ONE RCCL all-gather over xGMI.
@@ -306,6 +322,12 @@ int mmd_op_gemm_bench(mmd_ctx* ctx, int M, int N, int K, int epi, int variant, i
  * info_out float[n,4] = (tau, kept count, kept mass / total mass, NaN flag), scores_out [n,V] or NULL = the scores z = pen(l) / T.  Synchronises the stream. */
 int mmd_op_sample(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
                   uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out);
+/* mmd_op_sample with the rows' log-probability records.  greedy != 0: the arg-max with penalty (first maximal index) stands in the draw's place -- temperature, top_k, top_p and
+ * the random words are ignored, the scores are pen(l), info_out is not written and may be NULL.  Outputs on the HOST: lp_out_host float[n, 2] = (logprob, sampling_logprob),
+ * top_ids_out_host int64[n, top_n], top_lp_out_host float[n, top_n] (0 <= top_n <= 8, else MMD_ERANGE).  Synchronises the stream. */
+int mmd_op_sample_logprobs(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                           uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n, int64_t* tokens_out, float* info_out, float* scores_out,
+                           float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host);
 int mmd_op_rmsnorm(mmd_ctx* ctx, const void* x, const void* w, void* y, int M, int H, float eps);
 int mmd_op_layernorm(mmd_ctx* ctx, const void* x, const void* w, const void* b, void* y, int M, int H, float eps);
 /* the autocast tower's residual step (models/modeling_live.py:28: `hidden (fp32) + sublayer_out (fp16)` promotes, LayerNorm returns fp32, the next linear casts to

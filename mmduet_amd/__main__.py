@@ -35,12 +35,16 @@ def main(argv=None):
     import argparse
     sp = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
     sp.add_argument('--do_sample', nargs='?', const=True, default=False, type=lambda v: str(v).lower() in ('1', 'true', 'yes'))
+    sp.add_argument('--logprobs', nargs='?', const=0, default=None, type=int)          # --logprobs [N]: per-token log-probabilities of every response, N (0..8) alternatives each
     sp.add_argument('--temperature', type=float, default=1.0)
     sp.add_argument('--top_k', type=int, default=0)
     sp.add_argument('--top_p', type=float, default=1.0)
     sp.add_argument('--sampling_seed', type=int, default=0)
     for k, v in vars(sp.parse_known_args(sys.argv[1:] if argv is None else argv)[0]).items():
         setattr(args, k, v)
+    args.output_logprobs, args.top_logprobs = args.logprobs is not None, args.logprobs or 0
+    if args.output_logprobs and args.streams_per_gpu > 1:
+        raise NotImplementedError('--logprobs: the multi-stream rounds (--streams_per_gpu > 1) record no log-probabilities')
     rank, world, local = init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
@@ -177,6 +181,9 @@ def main(argv=None):
                             nxt = pf.take()
                             stage_device(nxt[1])
                         responses = infer.inference()
+                        if args.output_logprobs:          # (this file's own records; the evaluator feed of results.py is not touched)
+                            for turn, lp in zip([t for t in responses if t['role'] == 'assistant'], infer.response_logprobs):
+                                turn['logprobs'] = lp
                         rec = result_record(data[i]['question_id'], responses, duration, infer.debug_data_list, evaluator_format=args.evaluator_format)
                         f_out.write(json.dumps(rec) + '\n')
                         keep_scores(i, infer.debug_data_list, getattr(infer, 'response_token_ids', ()))

@@ -95,7 +95,7 @@ template <typename T> __device__ __forceinline__ float silu_t(float x) {
 static inline size_t dtype_size(int dt) { return dt == MMD_F32 ? 4 : 2; }
 
 // device-resident state of a graph-captured decode step (updated by the last kernel of the graph)
-struct StepState { long long n_ctx; long long cap; void* K; void* V; int n_prev; int pad; };
+struct StepState { long long n_ctx; long long cap; void* K; void* V; int n_prev; int step; };          // step: index of the decode step within its generate call (the slot of its log-probability record)
 
 // ---- the GEMM family (arguments, epilogues, kernel ids and the dispatch decision: gemm_plan.h) ---------------------------
 const GemmTuning& gemm_tuning();          // the process's GemmTuning (MMDUET_GEMV_KSPLIT_SHORT, read once)
@@ -152,9 +152,21 @@ struct SampleRow {
     uint32_t seed_lo, seed_hi, lane, advance;
 };
 constexpr int SMP_MAX_SLICES = 64;
+// log-probability records (sample.hip): one per token.  lp = log-probability under the model (raw logits), slp = under the distribution the token was taken from, then the
+// top_n largest raw logits as ids (-1: the row is shorter) and their lp.  LogprobOut says where row r of a launch records: slot (dyn ? dyn->step : idx0) + r of rec[cap] (a slot
+// beyond cap is not written), for the token toks[r]; rec == null: nothing is recorded.
+constexpr int LP_MAX_TOP = 8;
+struct LogprobRec { float lp, slp; float top_lp[LP_MAX_TOP]; int top_id[LP_MAX_TOP]; };
+struct LogprobOut { LogprobRec* rec; int cap; const StepState* dyn; int idx0; const int64_t* toks; int top_n; };
 size_t sample_topkp_scratch_bytes(int V, int n, bool own_scores);          // n <= MMD_ROUND_MAX_SAMPLERS rows per launch; own_scores: the z rows live in the scratch
 hipError_t launch_sample_batch_topkp(const float* logits /*[n, V]*/, int V, int n, SampleRow* rows_dev, bool any_k, bool any_p, const unsigned long long* r_words_dev /* or null: Philox */,
-                                     int64_t* toks_out_dev, float* info_out_dev /* [n,4] or null */, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st);
+                                     int64_t* toks_out_dev, float* info_out_dev /* [n,4] or null */, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st,
+                                     const LogprobOut* lp = nullptr /* the draw records slp */);
+size_t logprob_scratch_bytes(int n);
+// the chain's scores z = pen(l) / T with nothing filtered (rows with top_k 0, top_p 1): maxima, masses and z stay in `scratch` for launch_logprob_rows(greedy)
+hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, const SampleRow* rows_dev, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st);
+// lp and the top_n of n <= MMD_ROUND_MAX_SAMPLERS rows; greedy: slp too, from what launch_sample_scores_unfiltered left in sample_scratch (same scores_out_dev)
+hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st);
 // streaming cross entropy over lm_head logit chunks (mmd_lm_nll; ops.hip): fold chunk `logits` [m, nc] (row stride ld, ld % 4 == 0; vocabulary columns [c0, c0 + nc)) into
 // state [m, 3] = (max, sum exp, label logit) -- `first`: the state starts empty -- through the one-writer partials part [m, lm_nll_splits(m, nc), 3]; then nll / lse from the state
 constexpr int LM_NLL_BLOCKS = 2048, LM_NLL_MAX_SPLITS = 256;          // blocks one chunk's reduce aims at; m * lm_nll_splits(m, nc) <= max(m, LM_NLL_BLOCKS)

@@ -36,7 +36,7 @@ struct Prof {
 // one captured decode step: the instantiated graph, its source, and the (penalty, EOS, filter selection) it was captured for
 struct DecodeGraph {
     hipGraphExec_t exec = nullptr; hipGraph_t src = nullptr;
-    float pen = 0.f; int64_t eos = 0; int sel = 0;
+    float pen = 0.f; int64_t eos = 0; int sel = 0; int lp = -1;          // lp: log-probability recording of the step (-1 off, else its top_n)
     void drop() {
         if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
         if (src) { hipGraphDestroy(src); src = nullptr; }
@@ -120,6 +120,9 @@ struct mmd_ctx {
     // for MMD_ROUND_MAX_SAMPLERS rows
     SampleRow* samp_rows_dev = nullptr; SampleRow* samp_rows_host = nullptr; void* samp_scratch = nullptr;
     uint32_t sample_lane = 0; uint32_t n_samplers = 0;
+    // log-probabilities of generated tokens (mmd_set_generate_logprobs; allocated at their first use): lp_top = the setting (-1 off), lp_rec [lp_cap] the device records of the
+    // most recent generate call, lp_n of them valid with lp_call_top alternatives each
+    int lp_top = -1, lp_cap = 0, lp_n = 0, lp_call_top = -1; LogprobRec* lp_rec = nullptr; void* lp_scratch = nullptr;
     Prof prof;
 };
 
@@ -1298,7 +1301,7 @@ static int upload_seg_states(StepRun& r) {
     c->seg_slot = (slot + 1) & 7;
     if (!c->seg_event[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->seg_event[slot], hipEventDisableTiming));
     else HIPCHK(c, hipEventSynchronize(c->seg_event[slot]));          // (eight steps old: long done unless the caller queues steps without ever synchronising)
-    for (int j = 0; j < r.p.run_n; ++j) { mmd_stream* sj = r.segs[r.p.run0 + j].s; hs[j].n_ctx = sj->len; hs[j].cap = sj->cap; hs[j].K = sj->K; hs[j].V = sj->V; hs[j].n_prev = 0; hs[j].pad = 0; }
+    for (int j = 0; j < r.p.run_n; ++j) { mmd_stream* sj = r.segs[r.p.run0 + j].s; hs[j].n_ctx = sj->len; hs[j].cap = sj->cap; hs[j].K = sj->K; hs[j].V = sj->V; hs[j].n_prev = 0; hs[j].step = 0; }
     HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(StepState) * r.p.run_n, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->seg_event[slot], st));
     r.seg_states = ds;
@@ -1838,41 +1841,53 @@ extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int
     return MMD_OK;
 }
 
+// log-probabilities behind an arg-max over logits_ws: the chain's scores for row descriptor 0 (T = 1, no filter: the penalty alone), then the record
+static int greedy_logprobs_enqueue(mmd_ctx* c, const LogprobOut& lp) {
+    const int V = c->cfg.vocab_size; hipStream_t st = c->stream;
+    HIPCHK(c, launch_sample_scores_unfiltered(c->logits_ws, V, 1, c->samp_rows_dev, nullptr, c->samp_scratch, st));
+    HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, lp, true, nullptr, c->samp_scratch, c->lp_scratch, st));
+    return MMD_OK;
+}
+
 // one decode step (feed the previously drawn token, draw the next) enqueued on the stream; `dyn` selects the
 // graph-capturable form that reads position / arena / penalty-list length from device state
 // `samp`: the sampling chain over row descriptor 0 takes the arg-max's place; its penalty list always grows on the device
-static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const SampleCall* samp = nullptr) {
+// `lp`: the step records its token's log-probabilities (the kernels stand between the choice of the token and the state's advance)
+static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const SampleCall* samp = nullptr,
+                               const LogprobOut* lp = nullptr) {
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size;
     // the next token's embedding is gathered straight into the residual-stream buffer (llm_step_segs skips its copy when embeds == l_h)
     HIPCHK(c, launch_embed(g.dtype, c->embed, c->tok_dev, 1, H, g.vocab_size, c->l_h, st));
     int rc = llm_step_impl(c, s, c->l_h, 1, nullptr, dyn); if (rc) return rc;
     rc = gemm(c, c->l_hid, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, g.vocab_size, 1, g.vocab_size, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
     if (samp) {
-        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, g.vocab_size, 1, c->samp_rows_dev, samp->any_k, samp->any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st));
+        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, g.vocab_size, 1, c->samp_rows_dev, samp->any_k, samp->any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lp));
+        if (lp) HIPCHK(c, launch_logprob_rows(c->logits_ws, g.vocab_size, 1, *lp, false, nullptr, c->samp_scratch, c->lp_scratch, st));
         HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st));
         return MMD_OK;
     }
     HIPCHK(c, launch_argmax_penalty(c->logits_ws, g.vocab_size, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, dyn, c->argmax_scratch));
+    if (lp) { rc = greedy_logprobs_enqueue(c, *lp); if (rc) return rc; }
     if (dyn) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st));
     return MMD_OK;
 }
 
 // captures one dynamic decode step into dg for the key (key_pen, eos_id, sel).  Capture runs on the context's own stream (the legacy null stream -- torch's default --
 // cannot be captured); the instantiated graph is then launched on whatever stream the caller bound
-static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, bool pen, float rep_penalty, int np, int64_t eos_id, const SampleCall* samp, float key_pen, int sel) {
+static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, bool pen, float rep_penalty, int np, int64_t eos_id, const SampleCall* samp, float key_pen, int sel, const LogprobOut* lp) {
     hipStream_t st = c->stream;
     dg.drop();
     HIPCHK(c, hipStreamSynchronize(st));
     c->stream = c->own_stream;
     hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
     if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
-    int rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, samp);
+    int rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, samp, lp);
     hipError_t ce = hipStreamEndCapture(c->own_stream, &dg.src);
     c->stream = st;
     if (rc) { dg.drop(); return rc; }
     HIPCHK(c, ce);
     HIPCHK(c, hipGraphInstantiate(&dg.exec, dg.src, nullptr, nullptr, 0));
-    dg.pen = key_pen; dg.eos = eos_id; dg.sel = sel;
+    dg.pen = key_pen; dg.eos = eos_id; dg.sel = sel; dg.lp = lp ? lp->top_n : -1;
     return MMD_OK;
 }
 
@@ -1890,14 +1905,34 @@ static int penalty_reserve(mmd_ctx* c, int need) {
     return MMD_OK;
 }
 
+// the records of a call's tokens: like the penalty list the buffer grows by doubling, and the captured steps that hold the old pointer are dropped
+static int logprob_reserve(mmd_ctx* c, int need) {
+    if (!c->lp_scratch) { int rc = dev_alloc(c, &c->lp_scratch, logprob_scratch_bytes(1), false); if (rc) return rc; }
+    if (need <= c->lp_cap) return MMD_OK;
+    int ncap = c->lp_cap > 0 ? c->lp_cap : 1024;
+    while (ncap < need) ncap *= 2;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->dec_greedy.drop(); c->dec_sampled.drop();
+    if (c->lp_rec) dev_free(c, c->lp_rec);
+    c->lp_rec = nullptr; c->lp_cap = 0;
+    int rc = dev_alloc(c, (void**)&c->lp_rec, (size_t)ncap * sizeof(LogprobRec)); if (rc) return rc;
+    c->lp_cap = ncap;
+    return MMD_OK;
+}
+
 // ---- the token loop of a response: prompt step, then one token in, one token out --------------------------------------------------------------------------
 // samp == nullptr: arg-max (+ repetition penalty).  Otherwise the sampling chain of sample.hip stands where the arg-max stood.  Everything the chain needs per step is
 // in row descriptor 0 on the device: the penalty-list length is read through &step_dev->n_prev and grown by advance_state_kernel, the Philox offset is advanced by the
 // draw kernel, so the captured step is replayed as it is for any temperature / top_k / top_p / seed.  Draw i of the call uses offset *offset_inout + i; *offset_inout
 // advances with every token read (EOS included).  *n_out is up to date whenever the call returns.
+// Log-probabilities (mmd_set_generate_logprobs): every step, the prompt's included, records behind its draw into lp_rec[step]; the captured step reads its index from
+// step_dev->step.  After an arg-max the chain's scores run over row descriptor 0 (T = 1, nothing filtered); on the eager route that descriptor is posted again before every
+// step, because there the list length rides in kernel arguments.  Nothing is read back here: mmd_generate_logprobs_read copies the records once.
 static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
                          int64_t* out_ids_host, int max_new, int* n_out, const SampleArgs* samp) {
     c->dec_route = 0; *n_out = 0;
+    const int lp_top = c->lp_top; const bool lp_on = lp_top >= 0;
+    c->lp_n = 0; c->lp_call_top = lp_top;
     if (max_new == 0) return MMD_OK;          // nothing asked for: nothing is enqueued, the stream is not extended
     if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
     if (S < 1) FAIL(c, MMD_EINVAL, "empty prompt");
@@ -1907,7 +1942,11 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     const bool pen = rep_penalty > 0.f;
     int np = (pen && n_prev) ? *n_prev : 0;
     if (pen) { rc = penalty_reserve(c, np + max_new); if (rc) return rc; }
-    if (samp) { rc = sample_reserve(c); if (rc) return rc; }
+    if (samp || lp_on) { rc = sample_reserve(c); if (rc) return rc; }
+    if (lp_on) {
+        if (V > (1 << 18)) FAIL(c, MMD_ERANGE, "log-probabilities handle vocabularies up to 2^18 entries");
+        rc = logprob_reserve(c, max_new); if (rc) return rc;
+    }
     if (np > 0) HIPCHK(c, hipMemcpyAsync(c->prev_dev, prev_ids_host, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
     const SampleCall call = samp ? sample_call(*samp, V) : SampleCall{false, false};
     const SampleCall* callp = samp ? &call : nullptr;
@@ -1917,6 +1956,16 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
         return MMD_OK;
     };
+    uint64_t no_offset = 0;
+    auto post_lp_row = [&](bool dynamic) -> int {          // the arg-max's descriptor for the log-probability scores: the penalty at T = 1, no filter, no draw
+        const SampleArgs plain{1.f, 0, 1.f, 0, &no_offset};
+        fill_sample_row(c->samp_rows_host[0], plain, c->prev_dev, pen, np < c->prev_cap ? np : c->prev_cap, c->prev_cap, rep_penalty, dynamic ? &c->step_dev->n_prev : nullptr,
+                        nullptr, nullptr, 0, 0);
+        HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
+        return MMD_OK;
+    };
+    LogprobOut lpo{c->lp_rec, c->lp_cap, nullptr, 0, c->tok_dev, lp_top};
+    const LogprobOut* lpp = lp_on ? &lpo : nullptr;
     int produced = 0;
     auto read_token = [&](int64_t* tok) -> int {
         HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -1931,13 +1980,18 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         const void* last = (const char*)c->l_hid + (size_t)(S - 1) * H * e;
         rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, V, 1, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
         if (samp) { rc = post_row(false); if (rc) return rc; }
+        else if (lp_on) { rc = post_lp_row(false); if (rc) return rc; }
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        if (samp) HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st));
+        if (samp) {
+            HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lpp));
+            if (lp_on) HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, lpo, false, nullptr, c->samp_scratch, c->lp_scratch, st));
+        }
         else HIPCHK(c, launch_argmax_penalty(c->logits_ws, V, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, nullptr, c->argmax_scratch));
+        if (lp_on && !samp) { rc = greedy_logprobs_enqueue(c, lpo); if (rc) return rc; }
     }
     int64_t tok = 0;
     rc = read_token(&tok); if (rc) return rc;
-    out_ids_host[produced++] = tok; *n_out = produced;
+    out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
     const bool stop = tok == eos_id;
     if (!stop && pen) {
         if (np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -1953,26 +2007,32 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
     if (can_graph || (samp && more)) {          // the sampled step reads the list length through *step_dev on the eager route too
         StepState* hs = c->step_host;
-        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->pad = 0;
+        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->step = 1;
         HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
     }
     if (samp && more) { rc = post_row(true); if (rc) return rc; }
+    if (lp_on && !samp && can_graph) { rc = post_lp_row(true); if (rc) return rc; }
+    if (can_graph) lpo.dyn = c->step_dev;
     DecodeGraph& dg = samp ? c->dec_sampled : c->dec_greedy;
     if (can_graph) {
         // arg-max: the penalty value rides in a kernel argument.  sampled: the value is in the row descriptor, the step holds penalty on / off and which filters run
         const float key_pen = pen ? (samp ? 1.f : rep_penalty) : 0.f;
         const int sel = (call.any_k ? 1 : 0) | (call.any_p ? 2 : 0);
         c->dec_route = 1;
-        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != sel) {
-            rc = capture_decode_step(c, s, dg, pen, rep_penalty, np, eos_id, callp, key_pen, sel); if (rc) { c->dec_route = 0; return rc; }
+        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != sel || dg.lp != lp_top) {
+            rc = capture_decode_step(c, s, dg, pen, rep_penalty, np, eos_id, callp, key_pen, sel, lpp); if (rc) { c->dec_route = 0; return rc; }
             c->dec_route = 2;
         }
     }
     for (int i = 1; i < max_new && !stop; ++i) {
         if (can_graph) { HIPCHK(c, hipGraphLaunch(dg.exec, st)); s->len += 1; }
-        else { rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, callp); if (rc) return rc; }
+        else {
+            if (lp_on && !samp) { rc = post_lp_row(false); if (rc) return rc; }
+            lpo.idx0 = i;
+            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, callp, lpp); if (rc) return rc;
+        }
         rc = read_token(&tok); if (rc) return rc;
-        out_ids_host[produced++] = tok; *n_out = produced;
+        out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
         if (tok == eos_id) break;
         if (pen) {          // (arg-max, eager: the list grows by a copy here; every other route grows it in advance_state_kernel)
             if (!samp && !can_graph && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
@@ -2001,12 +2061,46 @@ extern "C" int mmd_sample_generate(mmd_ctx* c, mmd_stream* s, const void* prompt
     return generate_impl(c, s, prompt_embeds, S, eos_id, rep_penalty, prev_ids_host, n_prev, prev_cap, out_ids_host, max_new, n_out, &samp);
 }
 
-// raw operator: n rows of logits through the sampling chain, one set of parameters, row i on lane i (MMD_ROUND_MAX_SAMPLERS rows per launch)
-extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
-                             uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out) {
+extern "C" int mmd_set_generate_logprobs(mmd_ctx* c, int top_n) {
+    if (!c) return MMD_EINVAL;
+    if (top_n < -1 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "log-probability alternatives: -1 (off) or 0..%d, got %d", LP_MAX_TOP, top_n);
+    c->lp_top = top_n;
+    return MMD_OK;
+}
+
+static void unpack_logprobs(const LogprobRec* h, int n, int top_n, float* lp, float* slp, int64_t* top_ids, float* top_lp) {
+    for (int i = 0; i < n; ++i) {
+        if (lp) lp[i] = h[i].lp;
+        if (slp) slp[i] = h[i].slp;
+        for (int j = 0; j < top_n; ++j) { if (top_ids) top_ids[(size_t)i * top_n + j] = h[i].top_id[j]; if (top_lp) top_lp[(size_t)i * top_n + j] = h[i].top_lp[j]; }
+    }
+}
+
+extern "C" int mmd_generate_logprobs_read(mmd_ctx* c, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out) {
     if (!c) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (!logits || !tokens_out || !info_out || n < 1 || n > 4096 || V < 1 || V > (1 << 18) || n_prev < 0 || (n_prev > 0 && !prev_ids_dev)) FAIL(c, MMD_EINVAL, "bad mmd_op_sample arguments");
+    if (!n_out || cap_tokens < 0) FAIL(c, MMD_EINVAL, "bad mmd_generate_logprobs_read arguments");
+    *n_out = 0;
+    const int n = c->lp_n;
+    if (n == 0) return MMD_OK;
+    if (cap_tokens < n) FAIL(c, MMD_ERANGE, "%d records, room for %d", n, cap_tokens);
+    std::vector<LogprobRec> h((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(h.data(), c->lp_rec, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unpack_logprobs(h.data(), n, c->lp_call_top, logprob_host, sampling_logprob_host, top_ids_host, top_logprob_host);
+    *n_out = n;
+    return MMD_OK;
+}
+
+// raw operator: n rows of logits through the sampling chain, one set of parameters, row i on lane i (MMD_ROUND_MAX_SAMPLERS rows per launch)
+// lp_host != null (mmd_op_sample_logprobs): the rows' log-probability records too; greedy: the multi-row arg-max with penalty stands in the draw's place
+static int op_sample_impl(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                          uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out,
+                          bool greedy, int top_n, float* lp_host, int64_t* top_ids_host, float* top_lp_host) {
+    if (!c) return MMD_EINVAL;
+    hipSetDevice(c->device);
+    if (greedy) { temperature = 1.f; top_k = 0; top_p = 1.f; }
+    if (!logits || !tokens_out || (!info_out && !greedy) || n < 1 || n > 4096 || V < 1 || V > (1 << 18) || n_prev < 0 || (n_prev > 0 && !prev_ids_dev)) FAIL(c, MMD_EINVAL, "bad mmd_op_sample arguments");
     if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1");
     hipStream_t st = c->stream;
     const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS;
@@ -2014,24 +2108,64 @@ extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, cons
     const SampleArgs a{temperature, top_k, top_p, seed, &offset};
     for (int i = 0; i < n; ++i) fill_sample_row(rows[i], a, prev_ids_dev, rep_penalty > 0.f && n_prev > 0, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
     SampleRow* rows_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
+    LogprobRec* rec_dev = nullptr; void* lp_scratch = nullptr; void* am_scratch = nullptr;
     int rc = MMD_OK;
-    auto release = [&]() { hipStreamSynchronize(st); if (rows_dev) hipFree(rows_dev); if (r_dev) hipFree(r_dev); if (scratch) hipFree(scratch); };
+    auto release = [&]() {
+        hipStreamSynchronize(st);
+        if (rows_dev) hipFree(rows_dev); if (r_dev) hipFree(r_dev); if (scratch) hipFree(scratch);
+        if (rec_dev) hipFree(rec_dev); if (lp_scratch) hipFree(lp_scratch); if (am_scratch) hipFree(am_scratch);
+    };
 #define OPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { release(); FAIL(c, MMD_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
     OPCHK(hipMalloc((void**)&rows_dev, sizeof(SampleRow) * n));
     OPCHK(hipMalloc(&scratch, sample_topkp_scratch_bytes(V, chunk, scores_out == nullptr)));
     OPCHK(hipMemcpyAsync(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice, st));
     if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpyAsync(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st)); }
+    if (lp_host) { OPCHK(hipMalloc((void**)&rec_dev, sizeof(LogprobRec) * n)); OPCHK(hipMalloc(&lp_scratch, logprob_scratch_bytes(chunk))); }
+    if (greedy) OPCHK(hipMalloc(&am_scratch, sample_batch_scratch_bytes()));
     const SampleCall call = sample_call(a, V);
+    const bool pen_on = rep_penalty > 0.f && n_prev > 0;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = n - i0 < chunk ? n - i0 : chunk;
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        OPCHK(launch_sample_batch_topkp(logits + (size_t)i0 * V, V, m, rows_dev + i0, call.any_k, call.any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4,
-                                        scores_out ? scores_out + (size_t)i0 * V : nullptr, scratch, st));
+        const float* lg = logits + (size_t)i0 * V; float* sc = scores_out ? scores_out + (size_t)i0 * V : nullptr;
+        const LogprobOut lpo{rec_dev, n, nullptr, i0, tokens_out + i0, top_n};
+        if (greedy) {
+            SampleBatch b{};
+            for (int r = 0; r < m; ++r) { b.prev[r] = prev_ids_dev; b.tok[r] = tokens_out + i0 + r; b.append[r] = nullptr; b.n_prev[r] = pen_on ? n_prev : 0; b.penalty[r] = pen_on ? rep_penalty : 1.f; }
+            OPCHK(launch_sample_batch(lg, V, b, m, tokens_out + i0, am_scratch, st));
+            OPCHK(launch_sample_scores_unfiltered(lg, V, m, rows_dev + i0, sc, scratch, st));
+        } else {
+            OPCHK(launch_sample_batch_topkp(lg, V, m, rows_dev + i0, call.any_k, call.any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4, sc, scratch, st,
+                                            lp_host ? &lpo : nullptr));
+        }
+        if (lp_host) OPCHK(launch_logprob_rows(lg, V, m, lpo, greedy, sc, scratch, lp_scratch, st));
     }
     OPCHK(hipStreamSynchronize(st));
+    if (lp_host) {
+        std::vector<LogprobRec> h((size_t)n);
+        OPCHK(hipMemcpy(h.data(), rec_dev, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost));
+        std::vector<float> l1((size_t)n), l2((size_t)n);
+        unpack_logprobs(h.data(), n, top_n, l1.data(), l2.data(), top_ids_host, top_lp_host);
+        for (int i = 0; i < n; ++i) { lp_host[2 * i] = l1[i]; lp_host[2 * i + 1] = l2[i]; }
+    }
 #undef OPCHK
     release();
     return rc;
+}
+
+extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                             uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out) {
+    return op_sample_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, false, 0, nullptr, nullptr, nullptr);
+}
+
+extern "C" int mmd_op_sample_logprobs(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                                      uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n, int64_t* tokens_out, float* info_out, float* scores_out,
+                                      float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host) {
+    if (!c) return MMD_EINVAL;
+    if (top_n < 0 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "top_n 0..%d, got %d", LP_MAX_TOP, top_n);
+    if (!lp_out_host || (top_n > 0 && (!top_ids_out_host || !top_lp_out_host))) FAIL(c, MMD_EINVAL, "bad mmd_op_sample_logprobs arguments");
+    return op_sample_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, greedy != 0, top_n,
+                          lp_out_host, top_ids_out_host, top_lp_out_host);
 }
 
 // ---- measurement -------------------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@
 //                          5 resolve the last level, fix tau / kept count / kept mass, write the slice's kept mass.  Rows with both filters off only run phase 5.
 //   sample_draw_kernel     one block per row: Philox word (or the explicit one), target = mulhi64(r, Z_kept), the slice from the per-slice masses, the token from a scan
 //                          inside the slice; writes token / info, appends to the sampler's slots, advances the row's offset.
+// Log-probabilities of the token a row ended with (DESIGN.md "Log-probabilities"; the kernels are at the end of the file): the draw kernel emits z[tok] - zmax - log(Z_kept 2^-40)
+// through LogprobOut; three more kernels give the same over the RAW logits plus the top_n largest of them.
 #include "common.h"
 
 constexpr int SMP_L12 = 2048, SMP_L3 = 1024;                                 // bins of radix levels 1, 2 and of level 3
@@ -248,7 +250,7 @@ __global__ __launch_bounds__(256) void sample_select_kernel(int V, const SampleR
 }
 
 __global__ __launch_bounds__(256) void sample_draw_kernel(int V, int nblk, SampleRow* __restrict__ rows, SampleWs w, const unsigned long long* __restrict__ r_words,
-                                                          int64_t* __restrict__ toks_out, float* __restrict__ info_out) {
+                                                          int64_t* __restrict__ toks_out, float* __restrict__ info_out, LogprobOut lp) {
     __shared__ unsigned long long sm[256];
     __shared__ int s_slice; __shared__ unsigned long long s_base, s_target, s_Z; __shared__ int s_tok;
     const int r = blockIdx.x, t = threadIdx.x; const SampleRow row = rows[r];
@@ -305,6 +307,10 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(int V, int nblk, Sampl
             info_out[r * 4 + 2] = tot ? (float)((double)s_Z / (double)tot) : 0.f;
             info_out[r * 4 + 3] = nan ? 1.f : 0.f;
         }
+        if (lp.rec) {          // log-probability of the token under the distribution it was drawn from: the kept set's masses are exactly the ones the draw searched
+            const int ri = (lp.dyn ? lp.dyn->step : lp.idx0) + r;
+            if (ri < lp.cap) lp.rec[ri].slp = tok < 0 ? NAN : (float)((double)z[tok] - (double)zmax - log((double)s_Z * 0x1p-40));
+        }
         if (row.advance) rows[r].offset = row.offset + 1;
     }
 }
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(int V, int nblk, Sampl
 int sample_topkp_slices(int V) { const int s = cdiv(V, 256); return s < 1 ? 1 : (s > SMP_MAX_SLICES ? SMP_MAX_SLICES : s); }
 
 hipError_t launch_sample_batch_topkp(const float* logits, int V, int n, SampleRow* rows_dev, bool any_k, bool any_p, const unsigned long long* r_words_dev, int64_t* toks_out_dev,
-                                     float* info_out_dev, float* scores_out_dev, void* scratch, hipStream_t st) {
+                                     float* info_out_dev, float* scores_out_dev, void* scratch, hipStream_t st, const LogprobOut* lp) {
     if (n <= 0) return hipSuccess;
     if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18)) return hipErrorInvalidValue;
     const SampleWs w = carve(scratch, V, n, scores_out_dev);
@@ -323,6 +329,165 @@ hipError_t launch_sample_batch_topkp(const float* logits, int V, int n, SampleRo
     if (any_k) { hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 1); hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 2); }
     if (any_p) { hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 3); hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 4); }
     hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 5);
-    hipLaunchKernelGGL(sample_draw_kernel, dim3(n), blk, 0, st, V, nblk, rows_dev, w, r_words_dev, toks_out_dev, info_out_dev);
+    hipLaunchKernelGGL(sample_draw_kernel, dim3(n), blk, 0, st, V, nblk, rows_dev, w, r_words_dev, toks_out_dev, info_out_dev, lp ? *lp : LogprobOut{});
+    return hipGetLastError();
+}
+
+// ---- log-probabilities ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Per row, for the token `t` the row ended with:  lp = l[t] - logsumexp(l) over the RAW logits,  slp = z[t] - logsumexp_{kept} z  (the draw kernel writes it; after an arg-max
+// the chain's scores + phase 5 run with T = 1 and nothing filtered, and logprob_final_kernel reads their partials),  and the top_n largest raw logits by (value descending, index
+// ascending) with their lp.  The sums are the chain's: the maximum subtracted, mass_fx in 64-bit integers, one writer per (row, slice) partial over the chain's slices -- a row's
+// numbers are the same bits whatever the grid and the other rows of the launch.  The last step (two differences and one log per number) runs in double on one thread.
+//   logprob_max_top_kernel   grid (slices, rows): the slice's maximum key and NaN flag, then top_n rounds of a block arg-max that each take the best element after the last taken
+//   logprob_mass_kernel      grid (slices, rows): the slice's mass against the row maximum
+//   logprob_final_kernel     one block per row: Z, the top_n of the slices' candidates (the same rounds over <= 64 * 8 entries in LDS), the record
+struct LogprobWs { uint32_t* part_max; uint32_t* part_nan; unsigned long long* part_mass; float* cand_v; int* cand_i; };
+constexpr int LP_NONE = 0x7fffffff;          // candidate slot without an element (the slice / row is shorter than top_n)
+
+size_t logprob_scratch_bytes(int n) { return (size_t)n * SMP_MAX_SLICES * (4 + 4 + 8 + LP_MAX_TOP * 8) + 256; }
+static LogprobWs carve_lp(void* scratch, int n) {
+    LogprobWs w; char* p = (char*)scratch;
+    w.part_mass = (unsigned long long*)p; p += (size_t)n * SMP_MAX_SLICES * 8;
+    w.part_max = (uint32_t*)p; p += (size_t)n * SMP_MAX_SLICES * 4;
+    w.part_nan = (uint32_t*)p; p += (size_t)n * SMP_MAX_SLICES * 4;
+    w.cand_v = (float*)p; p += (size_t)n * SMP_MAX_SLICES * LP_MAX_TOP * 4;
+    w.cand_i = (int*)p;
+    return w;
+}
+
+// (value descending, index ascending); NaN is never better than anything
+__device__ __forceinline__ bool lp_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+// the best of one (value, index) per thread; all 256 threads get it
+__device__ __forceinline__ void block_best(float& v, int& i, float* s_v, int* s_i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64);
+        if (lp_better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    __syncthreads();          // (the round before may still be reading s_v / s_i)
+    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = v; s_i[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    v = s_v[0]; i = s_i[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (lp_better(s_v[k], s_i[k], v, i)) { v = s_v[k]; i = s_i[k]; }
+}
+
+__global__ __launch_bounds__(256) void logprob_max_top_kernel(const float* __restrict__ logits, int V, LogprobWs w, int top_n) {
+    __shared__ uint32_t s_max[4], s_nan[4];
+    __shared__ float s_v[4]; __shared__ int s_i[4];
+    const int r = blockIdx.y;
+    const float* lg = logits + (long long)r * V;
+    int beg, end; slice_of(V, blockIdx.x, gridDim.x, &beg, &end);
+    uint32_t mk = 0, nn = 0;
+    for (int i = beg + threadIdx.x; i < end; i += 256) { const float v = lg[i]; if (v != v) nn = 1; else mk = max(mk, f2key(v)); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mk = max(mk, (uint32_t)__shfl_xor((int)mk, o, 64)); nn |= (uint32_t)__shfl_xor((int)nn, o, 64); }
+    if ((threadIdx.x & 63) == 0) { s_max[threadIdx.x >> 6] = mk; s_nan[threadIdx.x >> 6] = nn; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) { mk = max(mk, s_max[k]); nn |= s_nan[k]; }
+        w.part_max[r * SMP_MAX_SLICES + blockIdx.x] = mk; w.part_nan[r * SMP_MAX_SLICES + blockIdx.x] = nn;
+    }
+    float last_v = INFINITY; int last_i = -1;          // the element taken last: the next one is the best of those it beats
+    for (int j = 0; j < top_n; ++j) {
+        float bv = -INFINITY; int bi = LP_NONE;
+        for (int i = beg + threadIdx.x; i < end; i += 256) { const float v = lg[i]; if (lp_better(last_v, last_i, v, i) && lp_better(v, i, bv, bi)) { bv = v; bi = i; } }
+        block_best(bv, bi, s_v, s_i);
+        if (threadIdx.x == 0) { const int c = (r * SMP_MAX_SLICES + blockIdx.x) * LP_MAX_TOP + j; w.cand_v[c] = bv; w.cand_i[c] = bi; }
+        last_v = bv; last_i = bi;
+    }
+}
+
+// row maximum and NaN flag of the raw logits from the per-slice partials
+__device__ __forceinline__ float lp_row_max(const LogprobWs& w, int r, int nblk, bool* nan) {
+    uint32_t mk = 0, nn = 0;
+    for (int b = 0; b < nblk; ++b) { mk = max(mk, w.part_max[r * SMP_MAX_SLICES + b]); nn |= w.part_nan[r * SMP_MAX_SLICES + b]; }
+    *nan = nn != 0;
+    return key2f(mk);
+}
+
+__global__ __launch_bounds__(256) void logprob_mass_kernel(const float* __restrict__ logits, int V, LogprobWs w) {
+    __shared__ unsigned long long s_m[256];
+    const int r = blockIdx.y;
+    bool nan; const float lmax = lp_row_max(w, r, gridDim.x, &nan);
+    if (nan) return;
+    const float* lg = logits + (long long)r * V;
+    int beg, end; slice_of(V, blockIdx.x, gridDim.x, &beg, &end);
+    unsigned long long m = 0;
+    for (int i = beg + threadIdx.x; i < end; i += 256) m += mass_fx(lg[i], lmax);
+    s_m[threadIdx.x] = m;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) { if (threadIdx.x < off) s_m[threadIdx.x] += s_m[threadIdx.x + off]; __syncthreads(); }
+    if (threadIdx.x == 0) w.part_mass[r * SMP_MAX_SLICES + blockIdx.x] = s_m[0];
+}
+
+// `greedy`: the row's token came from the arg-max; sw holds the chain's scores pen(l) (T = 1) with their per-slice maxima and (unfiltered) masses
+__global__ __launch_bounds__(256) void logprob_final_kernel(const float* __restrict__ logits, int V, int nblk, LogprobWs w, LogprobOut o, int greedy, SampleWs sw) {
+    __shared__ float s_cv[SMP_MAX_SLICES * LP_MAX_TOP]; __shared__ int s_ci[SMP_MAX_SLICES * LP_MAX_TOP];
+    __shared__ float s_v[4]; __shared__ int s_i[4];
+    __shared__ double s_logZ;
+    const int r = blockIdx.x, t = threadIdx.x;
+    const int ri = (o.dyn ? o.dyn->step : o.idx0) + r;
+    if (ri >= o.cap) return;
+    LogprobRec* rec = o.rec + ri;
+    const float* lg = logits + (long long)r * V;
+    bool nan; const float lmax = lp_row_max(w, r, nblk, &nan);
+    if (t == 0) {
+        unsigned long long Z = 0;
+        if (!nan) for (int b = 0; b < nblk; ++b) Z += w.part_mass[r * SMP_MAX_SLICES + b];
+        s_logZ = log((double)Z * 0x1p-40);
+    }
+    const int nc = nblk * o.top_n;
+    for (int c = t; c < nc; c += 256) { const int g = (r * SMP_MAX_SLICES + c / o.top_n) * LP_MAX_TOP + c % o.top_n; s_cv[c] = w.cand_v[g]; s_ci[c] = w.cand_i[g]; }
+    __syncthreads();
+    const double logZ = s_logZ;
+    float last_v = INFINITY; int last_i = -1;
+    for (int j = 0; j < o.top_n; ++j) {
+        float bv = -INFINITY; int bi = LP_NONE;
+        for (int c = t; c < nc; c += 256) { const float v = s_cv[c]; const int i = s_ci[c]; if (i != LP_NONE && lp_better(last_v, last_i, v, i) && lp_better(v, i, bv, bi)) { bv = v; bi = i; } }
+        block_best(bv, bi, s_v, s_i);
+        if (t == 0) {
+            rec->top_id[j] = bi == LP_NONE ? -1 : bi;
+            rec->top_lp[j] = bi == LP_NONE ? -INFINITY : (nan ? NAN : (float)((double)bv - (double)lmax - logZ));
+        }
+        last_v = bv; last_i = bi;
+    }
+    if (t == 0) {
+        const long long tok = o.toks[r];
+        const bool ok = !nan && tok >= 0 && tok < V;          // (the arg-max of a row of NaNs names no index)
+        rec->lp = ok ? (float)((double)lg[tok] - (double)lmax - logZ) : NAN;
+        if (greedy) {
+            bool znan; const float zmax = row_max(sw, r, nblk, &znan);
+            float slp = NAN;
+            if (ok && !znan) {
+                unsigned long long Z = 0;
+                for (int b = 0; b < nblk; ++b) Z += sw.part_mass[r * SMP_MAX_SLICES + b];
+                slp = (float)((double)sw.z[(long long)r * sw.ldz + tok] - (double)zmax - log((double)Z * 0x1p-40));
+            }
+            rec->slp = slp;
+        }
+    }
+}
+
+hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, const SampleRow* rows_dev, float* scores_out_dev, void* scratch, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18)) return hipErrorInvalidValue;
+    const SampleWs w = carve(scratch, V, n, scores_out_dev);
+    const dim3 grid(sample_topkp_slices(V), n), blk(256);
+    hipLaunchKernelGGL(sample_scores_kernel, grid, blk, 0, st, logits, V, rows_dev, w);
+    hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, rows_dev, w, 5);
+    return hipGetLastError();
+}
+
+hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18) || o.top_n < 0 || o.top_n > LP_MAX_TOP || !o.rec || !o.toks) return hipErrorInvalidValue;
+    const LogprobWs w = carve_lp(lp_scratch, n);
+    const SampleWs sw = greedy ? carve(sample_scratch, V, n, scores_out_dev) : SampleWs{};
+    const int nblk = sample_topkp_slices(V);
+    const dim3 grid(nblk, n), blk(256);
+    hipLaunchKernelGGL(logprob_max_top_kernel, grid, blk, 0, st, logits, V, w, o.top_n);
+    hipLaunchKernelGGL(logprob_mass_kernel, grid, blk, 0, st, logits, V, w);
+    hipLaunchKernelGGL(logprob_final_kernel, dim3(n), blk, 0, st, logits, V, nblk, w, o, greedy ? 1 : 0, sw);
     return hipGetLastError();
 }

@@ -98,6 +98,9 @@ class LiveInferForBenchmark:
         self.top_k = int(getattr(args, 'top_k', 0) or 0)
         self.top_p = float(getattr(args, 'top_p', 1.0))
         self.sampling_seed = int(getattr(args, 'sampling_seed', 0) or 0)
+        # per-token log-probabilities of the responses (off by default; DESIGN.md "Log-probabilities"): response_logprobs grows beside response_token_ids
+        self.output_logprobs = bool(getattr(args, 'output_logprobs', False))
+        self.top_logprobs = int(getattr(args, 'top_logprobs', 0) or 0)
         self.frames_per_forward = max(1, int(getattr(args, 'frames_per_forward', 1)))
         self.overlap_vision = bool(getattr(args, 'overlap_vision', True))
         self.record_head_logits = False          # diagnostics (parity tests, bench.py's self-check): debug_data entries also carry the 4 raw head logits of the frame
@@ -382,10 +385,8 @@ class LiveInferForBenchmark:
         self.last_ids = self._no_ids()
         self.last_role = 'user'
 
-    def _generate_response(self):
-        """test/inference.py:257-274."""
-        self.last_ids = self._added_stream_generation_ids
-        self._issue_vit_burst()
+    def _native_response(self):
+        """The response's token loop on the device, arg-max or sampled: -> (output ids, cache)."""
         if self.do_sample:
             output_ids, past_key_values, self.generated_token_ids, self._sample_offset = fast_sample_generate(
                 model=self.model, inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values,
@@ -397,6 +398,26 @@ class LiveInferForBenchmark:
                 model=self.model, inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values,
                 eos_token_id=self.eos_token_id, inplace_output_ids=self.inplace_output_ids,
                 repetition_penalty=self.repetition_penalty, generated_token_ids=self.generated_token_ids)
+        return output_ids, past_key_values
+
+    def _generate_response(self):
+        """test/inference.py:257-274."""
+        self.last_ids = self._added_stream_generation_ids
+        self._issue_vit_burst()
+        if not self.output_logprobs:
+            output_ids, past_key_values = self._native_response()
+        else:
+            from .multistream import _ModelProxy
+            if isinstance(self.model, _ModelProxy):
+                raise NotImplementedError('output_logprobs: the multi-stream rounds (_ModelProxy, streams_per_gpu > 1) record no log-probabilities')
+            self.model.set_generate_logprobs(self.top_logprobs)
+            try:
+                output_ids, past_key_values = self._native_response()
+                rec = self.model.last_generate_logprobs()
+            finally:
+                self.model.set_generate_logprobs(-1)
+            self.last_generated_logprobs = dict(logprobs=rec['logprobs'].tolist(), sampling_logprobs=rec['sampling_logprobs'].tolist(),
+                                                top=[[[int(i), float(v)] for i, v in zip(ids, lps)] for ids, lps in zip(rec['top_logprob_ids'].tolist(), rec['top_logprobs'].tolist())])
         self.last_generated_ids = output_ids[0].tolist()
         n_tok = len(self.last_generated_ids)
         self._resp_tokens_mean = n_tok if self._resp_tokens_mean is None else 0.7 * self._resp_tokens_mean + 0.3 * n_tok
@@ -449,6 +470,7 @@ class LiveInferForBenchmark:
     def inference(self):
         model_response_list = [{'time': q[0], 'content': q[1], 'role': 'user'} for q in self.query_queue]
         self.response_token_ids = []
+        self.response_logprobs = []          # one dict per response when output_logprobs is on
         while self.frame_embeds_queue:
             # 1. a user query due at the current time goes in first
             if self.query_queue and self.video_time >= self.query_queue[0][0]:
@@ -482,6 +504,8 @@ class LiveInferForBenchmark:
                         self.replayed_frames += k - 1 - j
                     response = self._generate_response()
                     self.response_token_ids.append(self.last_generated_ids)
+                    if self.output_logprobs:
+                        self.response_logprobs.append(self.last_generated_logprobs)
                     model_response_list.append({'time': self.video_time, 'content': response, 'role': 'assistant'})
                     self.num_frames_no_reply = 0
                     self.consecutive_n_frames = 0

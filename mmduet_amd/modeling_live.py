@@ -112,10 +112,12 @@ _GENERATE_IGNORED = ('attention_mask', 'position_ids', 'use_cache', 'return_dict
 
 
 class GenerateOutput:
-    """What generate(return_dict_in_generate=True) returns."""
+    """What generate(return_dict_in_generate=True) returns.  The four log-probability fields are None unless output_logprobs was asked for: logprobs and
+    sampling_logprobs [1, n] fp32, top_logprobs [1, n, top_n] fp32, top_logprob_ids [1, n, top_n] int64 (n = the new tokens)."""
 
-    def __init__(self, sequences, past_key_values):
+    def __init__(self, sequences, past_key_values, logprobs=None, sampling_logprobs=None, top_logprobs=None, top_logprob_ids=None):
         self.sequences, self.past_key_values = sequences, past_key_values
+        self.logprobs, self.sampling_logprobs, self.top_logprobs, self.top_logprob_ids = logprobs, sampling_logprobs, top_logprobs, top_logprob_ids
 
 
 class SamplerHandle:
@@ -336,6 +338,7 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         check(L.mmd_create(C.byref(c), self.device.index or 0, C.byref(h)), None, 'mmd_create')
         self._ctx = h
         self._lock = threading.RLock()      # the Gradio demo calls the model from two threads (demo/app.py:84-85)
+        self._logprobs_top, self._last_logprobs = -1, None          # set_generate_logprobs / last_generate_logprobs
         self._embed = _Embedding(self)
         self._tower = _VisionTower(self)
         self._finalized = False
@@ -828,10 +831,34 @@ class VideoHeadLiveLlavaQwenForCausalLM:
                 check(lib().mmd_sample_generate(self._ctx, arena.h, _ptr(x), S, eos, pen, prev_arr, C.byref(n_prev), cap, float(temperature), int(top_k or 0), float(top_p),
                                                 int(seed) & _U64, C.byref(off), out_ids, max_new_tokens, C.byref(n_out)), self._ctx, 'mmd_sample_generate')
             cache = KVCacheHandle(arena, arena.length())
+            self._last_logprobs = self._read_generate_logprobs(n_out.value) if self._logprobs_top >= 0 else None
         ids = [int(out_ids[i]) for i in range(n_out.value)]
         if grow:
             generated_token_ids[:] = [int(prev_arr[i]) for i in range(n_prev.value)]
         return ids, cache, int(off.value)
+
+    def set_generate_logprobs(self, top_n=-1):
+        """mmd_set_generate_logprobs: the following greedy_generate / sample_generate calls record per-token log-probabilities with `top_n` (0..8) alternatives
+        (DESIGN.md "Log-probabilities"); -1 or None switches the recording off (the default)."""
+        top_n = -1 if top_n is None else int(top_n)
+        with self._lock:
+            check(lib().mmd_set_generate_logprobs(self._ctx, top_n), self._ctx, 'mmd_set_generate_logprobs')
+            self._logprobs_top = top_n
+
+    def _read_generate_logprobs(self, n_tokens):
+        top = self._logprobs_top
+        lp, slp = torch.empty(n_tokens, dtype=torch.float32), torch.empty(n_tokens, dtype=torch.float32)
+        top_lp, top_ids = torch.empty(n_tokens, top, dtype=torch.float32), torch.empty(n_tokens, top, dtype=torch.long)
+        n = C.c_int(0)
+        check(lib().mmd_generate_logprobs_read(self._ctx, _ptr(lp), _ptr(slp), _ptr(top_ids), _ptr(top_lp), int(n_tokens), C.byref(n)), self._ctx, 'mmd_generate_logprobs_read')
+        if n.value != n_tokens:
+            raise RuntimeError(f'{n.value} log-probability records for {n_tokens} tokens')
+        return dict(logprobs=lp, sampling_logprobs=slp, top_logprobs=top_lp, top_logprob_ids=top_ids)
+
+    def last_generate_logprobs(self):
+        """The records of the most recent native generate call of this model as CPU tensors -- logprobs [n], sampling_logprobs [n], top_logprobs [n, top_n],
+        top_logprob_ids [n, top_n] -- or None if that call did not record (set_generate_logprobs)."""
+        return self._last_logprobs
 
     def greedy_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None,
                         generated_token_ids=None):
@@ -862,11 +889,19 @@ class VideoHeadLiveLlavaQwenForCausalLM:
 
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, frames=None, past_key_values=None, max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
-                 repetition_penalty=None, eos_token_id=None, seed=None, return_dict_in_generate=False, **kwargs):
+                 repetition_penalty=None, eos_token_id=None, seed=None, return_dict_in_generate=False, output_logprobs=False, top_logprobs=0, **kwargs):
         """models/live_llava/video_head_live_llava_qwen.py:210-242 (HF `generate` for batch 1).  do_sample=False is the greedy path; do_sample=True draws with temperature,
         top-k and top-p on the device (DESIGN.md "Sampling"), seeded by `seed` (None: one draw from torch.initial_seed() per call).  Returns a LongTensor [1, n]: with
         `input_ids` the prompt followed by the new tokens, with `inputs_embeds` only the new tokens; with return_dict_in_generate an object with .sequences and
-        .past_key_values.  Arguments that ask for what is not built (beam search, min_p, typical_p, ...) raise NotImplementedError."""
+        .past_key_values.  output_logprobs=True (dict form only) adds the per-token log-probabilities recorded by the native loop, with `top_logprobs` (0..8) alternatives per
+        token (GenerateOutput).  Arguments that ask for what is not built (beam search, min_p, typical_p, ...) raise NotImplementedError."""
+        top_logprobs = int(top_logprobs or 0)
+        if output_logprobs and not return_dict_in_generate:
+            raise ValueError('generate: output_logprobs needs return_dict_in_generate=True (a plain id tensor has no place for them)')
+        if top_logprobs and not output_logprobs:
+            raise ValueError('generate: top_logprobs needs output_logprobs=True')
+        if not 0 <= top_logprobs <= 8:
+            raise ValueError('generate: top_logprobs is 0..8')
         if 'max_length' in kwargs and kwargs['max_length'] is not None:
             raise NotImplementedError('generate: max_length is not supported, pass max_new_tokens')
         kwargs.pop('max_length', None)
@@ -896,18 +931,32 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             eos_token_id = eos_token_id[0] if eos_token_id else None
         pen = float(repetition_penalty) if repetition_penalty not in (None, 1.0) else None
         max_new_tokens = int(max_new_tokens)
-        if max_new_tokens <= 0:
-            ids, cache = [], past_key_values
-        elif not do_sample:
-            ids, cache = self.greedy_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, pen, [] if pen else None)
-        else:
-            if seed is None:
-                seed = torch.initial_seed()
-            ids, cache, _ = self.sample_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, pen, [] if pen else None,
-                                                 temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        was = self._logprobs_top
+        if output_logprobs or was >= 0:          # (this call's own setting; a recording switched on for the bare loops is put back afterwards)
+            self.set_generate_logprobs(top_logprobs if output_logprobs else -1)
+        try:
+            if max_new_tokens <= 0:
+                ids, cache = [], past_key_values
+                rec = dict(logprobs=torch.empty(0), sampling_logprobs=torch.empty(0), top_logprobs=torch.empty(0, top_logprobs), top_logprob_ids=torch.empty(0, top_logprobs, dtype=torch.long))
+            elif not do_sample:
+                ids, cache = self.greedy_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, pen, [] if pen else None)
+                rec = self._last_logprobs
+            else:
+                if seed is None:
+                    seed = torch.initial_seed()
+                ids, cache, _ = self.sample_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, pen, [] if pen else None,
+                                                     temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+                rec = self._last_logprobs
+        finally:
+            if self._logprobs_top != was:
+                self.set_generate_logprobs(was)
         new = torch.tensor([ids], dtype=torch.long, device=self.device).view(1, -1)
         seq = new if prompt is None else torch.cat([prompt.reshape(1, -1).to(device=self.device, dtype=torch.long), new], dim=1)
-        return GenerateOutput(seq, cache) if return_dict_in_generate else seq
+        if not return_dict_in_generate:
+            return seq
+        if not output_logprobs:
+            return GenerateOutput(seq, cache)
+        return GenerateOutput(seq, cache, **{k: v[None] for k, v in rec.items()})
 
     def generate_after_embed(self, input_ids, frames, **kwargs):
         """models/live_llava/video_head_live_llava_qwen.py:207-208: generate over joint_embed(input_ids, frames); like HF with inputs_embeds only, the new tokens are returned."""
@@ -934,6 +983,33 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             check(lib().mmd_op_sample(self._ctx, _ptr(lg), n, V, _ptr(prev), 0 if prev is None else prev.numel(), float(repetition_penalty or 0.0), float(temperature),
                                       int(top_k or 0), float(top_p), int(seed) & _U64, int(offset) & _U64, r_arr, _ptr(toks), _ptr(info), _ptr(scores)), self._ctx, 'mmd_op_sample')
         return toks, info, scores
+
+    def sample_logprob_op(self, logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, r=None, prev_ids=None, repetition_penalty=None, greedy=False, top_n=0,
+                          return_scores=False):
+        """`sample_op` with the rows' log-probability records (mmd_op_sample_logprobs).  greedy: the arg-max with penalty stands in the draw's place (info is None then).
+        -> (tokens [n], info [n, 4] or None, scores [n, V] or None) on the device and, as CPU tensors, lp fp32 [n, 2] = (logprob, sampling_logprob), top ids int64 [n, top_n],
+        top logprobs fp32 [n, top_n]."""
+        lg = logits.to(device=self.device, dtype=torch.float32).contiguous()
+        if lg.ndim == 1:
+            lg = lg[None]
+        n, V = lg.shape
+        top_n = int(top_n)
+        toks = torch.empty(n, dtype=torch.long, device=self.device)
+        info = None if greedy else torch.empty(n, 4, dtype=torch.float32, device=self.device)
+        scores = torch.empty(n, V, dtype=torch.float32, device=self.device) if return_scores else None
+        prev = torch.as_tensor(prev_ids, dtype=torch.long).to(self.device).contiguous() if prev_ids is not None and len(prev_ids) else None
+        lp, top_ids, top_lp = torch.empty(n, 2, dtype=torch.float32), torch.empty(n, max(top_n, 0), dtype=torch.long), torch.empty(n, max(top_n, 0), dtype=torch.float32)
+        r_arr = None
+        if r is not None:
+            if len(r) != n:
+                raise ValueError('one random word per row')
+            r_arr = (C.c_uint64 * n)(*[int(v) & _U64 for v in r])
+        with self._lock:
+            self._bind_stream()
+            check(lib().mmd_op_sample_logprobs(self._ctx, _ptr(lg), n, V, _ptr(prev), 0 if prev is None else prev.numel(), float(repetition_penalty or 0.0), float(temperature),
+                                               int(top_k or 0), float(top_p), int(seed) & _U64, int(offset) & _U64, r_arr, int(bool(greedy)), top_n, _ptr(toks), _ptr(info),
+                                               _ptr(scores), _ptr(lp), _ptr(top_ids), _ptr(top_lp)), self._ctx, 'mmd_op_sample_logprobs')
+        return toks, info, scores, lp, top_ids, top_lp
 
     # ---- measurement --------------------------------------------------------------------------------------------------
     def prof_enable(self, classes=True):
