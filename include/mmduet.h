@@ -348,6 +348,26 @@ int mmd_op_rope_append(mmd_ctx* ctx, void* qkv, int S, int nh, int nkv, int d, f
  * MMD_EINVAL before anything is launched.  Synchronises the stream. */
 int mmd_op_kv_write(mmd_ctx* ctx, int writer, const void* src, int n_slabs, int slab_rows, const void* bias, const float* inv_freq_host, int S, int nh, int nkv, int d,
                     int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, void* attn_out);
+/* The code that writes the residual stream h between two GEMMs of a decoder layer, and its RMSNorm image, on caller-owned device buffers (tests/test_gpu_residual_stream.py).
+ * Both entries are bf16 kernels, refuse with MMD_EINVAL before anything is launched, synchronise the stream, and leave what they launched to mmd_op_gemm_last_plan.
+ *
+ * mmd_op_slab_resid_rmsnorm: slab_resid_rmsnorm_kernel alone.  slabs fp32 [splits][M][H] are summed in slab order (x wscale [H] fp32, if given), rounded to bf16, added to
+ * resid [M,H] and rounded: h_out [M,H] (may be resid itself); xn_out [M,H] = rnd(norm_w * rnd(h_out / rms)).  last_plan: {32, instantiation 4 / 8 / 16, splits, M}.
+ * Refused: a context that is not bf16, a missing operand (wscale alone may be NULL), M < 1, H > 4096, H % 4 != 0, splits outside 1 .. 16.
+ *
+ * mmd_op_gemv_chain: one GEMV of the decode chain, W [N,K] bf16 row-major (packed as mmd_op_gemm does; with q8 [N,K] and scale [N] of mmd_op_quantize_fp8 the fp8 copy as in
+ * mmd_op_gemm_w8, W then being bf16(q)).  ssq is [rows >= M][256] fp32: per row, the sums of squares of h per 16-column tile.
+ *   role 2, producer: h [M,N] <- rnd(rnd((X [M,K] . W^T) * scale) + h) in place, ssq[m][t] for t < N / 16 written.  gamma, Y NULL, epi 0.
+ *   role 1, consumer: x = rnd(gamma [K] * rnd(h [M,K] * rsqrt(sum(ssq[m][0 .. 255]) / K + eps))) is built inside the kernel; X is passed on as the step passes it and never read.
+ *     epi 0: Y receives fp32 slabs [splits][M][N] (room for max_splits; the planner chooses a count that fits), *splits_out the count.   epi 4: Y = SwiGLU product bf16 [M,N/2]
+ *     (gate / up rows of W interleaved in blocks of 16).
+ * Refused: a context that is not bf16; a role other than 1 / 2, operands that do not belong to the role (above), q8 without scale or the reverse; M outside 1 .. 16, N % 16 != 0,
+ * K % 32 != 0 (fp8: K % 64), epi 4 with N % 32 != 0; and whatever the planner refuses or plans in another chain form: a consumer with M > 4 or with more than 1024 k per wave
+ * (K / (4 x splits), in whole k-tiles rounded up), a producer with N > 4096. */
+int mmd_op_slab_resid_rmsnorm(mmd_ctx* ctx, const float* slabs, int splits, int M, int H, const void* resid, void* h_out, const void* norm_w, float eps, void* xn_out,
+                              const float* wscale);
+int mmd_op_gemv_chain(mmd_ctx* ctx, int role, const void* X, const void* W, const uint8_t* q8, const float* scale, void* h, const void* gamma, float* ssq, float eps,
+                      void* Y, int M, int N, int K, int epi, int max_splits, int* splits_out);
 /* the first n tokens (n % 64 == 0, n <= mmd_kv_capacity) of one layer of a stream's arena AS STORED: K_out [nkv, n, d] rotated rows, V_out [nkv, n / 64, d, 64] transposed
  * 64-token blocks (token t, dim e of a head at ((t >> 6) * d + e) * 64 + (t & 63)); device buffers in the context dtype.  Synchronises the stream. */
 int mmd_kv_debug_read(mmd_stream* s, int layer, int64_t n, void* K_out, void* V_out);

@@ -119,6 +119,8 @@ _SIGS = {
     'mmd_op_resid32_layernorm': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _F]),
     'mmd_op_rope_append': (_I, [_VP, _VP, _I, _I, _I, _I, _F, _I64, _VP, _VP, _VP, _I64]),
     'mmd_op_kv_write': (_I, [_VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I64, _VP, _VP, _VP, _I64, _VP]),
+    'mmd_op_slab_resid_rmsnorm': (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _VP]),
+    'mmd_op_gemv_chain': (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     'mmd_kv_debug_read': (_I, [_VP, _I, _I64, _VP, _VP]),
     'mmd_op_attention': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I64, _I64, _I, _I]),
     'mmd_op_attention_bench': (_I, [_VP, _I, _I, _I, _I, _I64, _I, _I, C.POINTER(_F)]),

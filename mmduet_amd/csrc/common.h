@@ -117,6 +117,8 @@ hipError_t launch_resid32_layernorm(const void* y16, float* h32, const void* pos
 // fused consumers of skinny-GEMM slabs (ops.hip)
 hipError_t launch_slab_resid_rmsnorm(const float* slabs, int splits, int M, int H, const void* resid_in, void* h_out, const void* norm_w, float eps,
                                      void* xn_out, hipStream_t st, const float* wscale = nullptr);
+int slab_resid_maxs(int splits);          // the instantiation (slabs a thread loads before its first add: 4, 8 or 16) that launch_slab_resid_rmsnorm runs for `splits`
+constexpr int OP_PLAN_SLAB_RESID = 32;    // mmd_op_gemm_last_plan after mmd_op_slab_resid_rmsnorm: {this, instantiation, splits, blocks = M} (no GEMM_K_* value)
 hipError_t launch_slab_rope_append(const float* slabs, int splits, const void* bias, int S, int nh, int nkv, int d, const float* inv_freq_dev,
                                    int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st, const StepState* dyn = nullptr, int layer = 0,
                                    int slab_rows = 0);          // slab_rows: rows of one slab when the projection ran over more rows than this stream's S (0 = S); `slabs` points at the stream's first row

@@ -25,7 +25,7 @@ enum { GEMM_AUTO = 0, GEMM_GENERIC = 1, GEMM_SKINNY = 2, GEMM_LARGE = 3, GEMM_BI
 //   * the CONSUMER (qkv / gate_up) never reads a normalised activation: every lane builds its X fragment as rnd(gamma * rnd(h * inv)),
 //     inv = rsqrt(sum(ssq[m][:]) / K + eps) summed in a fixed order (deterministic; same rounding points as slab_resid_rmsnorm_kernel).
 constexpr int GEMV_SSQ_STRIDE = 256;   // floats per row in ssq (n-tiles of 16 columns: N <= 4096)
-constexpr int GEMV_CHAIN_ROWS = 4;     // rows a consumer keeps in LDS; K <= 4096
+constexpr int GEMV_CHAIN_ROWS = 4;     // rows a consumer keeps in LDS, 1024 k per wave (plan_gemv16 refuses the rest)
 struct GemvChain {
     const void* xn_h = nullptr; const void* xn_gamma = nullptr; const float* xn_ssq = nullptr; float xn_eps = 0.f;     // consumer side
     void* fin_h = nullptr; float* fin_ssq = nullptr;                                                                     // producer side
@@ -175,6 +175,15 @@ static inline GemmPlan plan_gemv16(const GemmArgs& a, const GemmTuning& tune) {
     }
     const bool two = a.epi == EPI_SWIGLU || (ntiles % 2 == 0 && ntiles >= 2048);
     const bool chain = a.chain && (a.chain->xn_h || a.chain->fin_h);          // (GemmArgs::chain is a host struct of the arguments: the one pointer the planner looks behind)
+    // what the chain forms of the kernel cannot take (step_plan keeps the model inside; any other caller is refused here, before a launch):
+    //   * producer: ssq has GEMV_SSQ_STRIDE n-tile entries per row;
+    //   * consumer: a wave keeps GEMV_CHAIN_ROWS rows x 1024 k of ITS K range in LDS and normalises them in two passes of 512 (the kernel's ranges: K tiles -- fp8: pairs of
+    //     tiles -- over the splits, then over the 4 waves, both rounded up).
+    if (chain && a.chain->fin_h && a.N > 16 * GEMV_SSQ_STRIDE) return GemmPlan();
+    if (chain && !a.chain->fin_h) {
+        const int kg = a.Wp8 ? 2 : 1, k_wave = cdiv(cdiv(KT / kg, ksplit), 4) * 32 * kg;
+        if (a.M > GEMV_CHAIN_ROWS || k_wave > 1024) return GemmPlan();
+    }
     GemmPlan pl;
     pl.kernel = GEMM_K_GEMV16; pl.tiles = ntiles; pl.w_from = a.Wp8 ? GEMM_W_PACKED8 : GEMM_W_PACKED;
     if (chain && a.chain->fin_h) {

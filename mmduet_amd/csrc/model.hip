@@ -2386,6 +2386,64 @@ extern "C" int mmd_op_kv_write(mmd_ctx* c, int writer, const void* src, int n_sl
     if (e != hipSuccess) FAIL(c, MMD_EHIP, "kv_write: writer %d failed: %s", writer, hipGetErrorString(e));
     return rc;
 }
+// the fused slab consumer (reduce + residual + RMSNorm) on caller-owned buffers (tests/test_gpu_residual_stream.py): launch_slab_resid_rmsnorm and nothing else
+extern "C" int mmd_op_slab_resid_rmsnorm(mmd_ctx* c, const float* slabs, int splits, int M, int H, const void* resid, void* h_out, const void* norm_w, float eps, void* xn_out,
+                                         const float* wscale) {
+    if (!c) return MMD_EINVAL;
+    if (!slabs || !resid || !h_out || !norm_w || !xn_out) FAIL(c, MMD_EINVAL, "slab_resid_rmsnorm: missing operand");
+    if (c->cfg.dtype != MMD_BF16) FAIL(c, MMD_EINVAL, "slab_resid_rmsnorm: a bf16 kernel");
+    if (M < 1 || H < 4 || H > 4096 || (H % 4) != 0 || splits < 1 || splits > 16) FAIL(c, MMD_EINVAL, "slab_resid_rmsnorm: M %d >= 1, H %d <= 4096 and %% 4 == 0, splits %d in 1 .. 16", M, H, splits);
+    hipSetDevice(c->device);
+    c->last_plan[0] = OP_PLAN_SLAB_RESID; c->last_plan[1] = slab_resid_maxs(splits); c->last_plan[2] = splits; c->last_plan[3] = M;
+    const hipError_t e = launch_slab_resid_rmsnorm(slabs, splits, M, H, resid, h_out, norm_w, eps, xn_out, c->stream, wscale);
+    hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) FAIL(c, MMD_EHIP, "slab_resid_rmsnorm failed: %s", hipGetErrorString(e));
+    return MMD_OK;
+}
+// one GEMV of the decode chain on explicit operands, with the GemmArgs the step builds for it: role GEMV_PRODUCER as layer_tail_chain's o_proj / down_proj (slab_gemm with
+// ch_fin), role GEMV_CONSUMER with epi EPI_NONE as layer_qkv (slab_gemm with ch_xn) and with EPI_SWIGLU as layer_tail_chain's gate_up (gemm with ch_xn).  The planner is asked
+// first: what it refuses, and a plan of another chain form than `role`, is MMD_EINVAL before anything is packed or launched.
+extern "C" int mmd_op_gemv_chain(mmd_ctx* c, int role, const void* X, const void* W, const uint8_t* q8, const float* scale, void* h, const void* gamma, float* ssq, float eps,
+                                 void* Y, int M, int N, int K, int epi, int max_splits, int* splits_out) {
+    if (!c) return MMD_EINVAL;
+    if (role != GEMV_CONSUMER && role != GEMV_PRODUCER) FAIL(c, MMD_EINVAL, "gemv_chain: role %d (1 consumer, 2 producer)", role);
+    if (!X || !W || !h || !ssq || (q8 != nullptr) != (scale != nullptr)) FAIL(c, MMD_EINVAL, "gemv_chain: missing operand");
+    if (role == GEMV_PRODUCER && (gamma || Y || epi != EPI_NONE)) FAIL(c, MMD_EINVAL, "gemv_chain: the producer takes no gamma, no output and no epilogue (h is updated in place)");
+    if (role == GEMV_CONSUMER && (!gamma || !Y || (epi != EPI_NONE && epi != EPI_SWIGLU) || (epi == EPI_NONE && (max_splits < 1 || !splits_out))))
+        FAIL(c, MMD_EINVAL, "gemv_chain: the consumer takes gamma and an output; epi 0 (fp32 slabs: max_splits >= 1, splits_out) or 4 (SwiGLU)");
+    if (c->cfg.dtype != MMD_BF16) FAIL(c, MMD_EINVAL, "gemv_chain: a bf16 kernel");
+    if (M < 1 || M > 16 || N < 16 || (N % 16) != 0 || K < 32 || (K % (q8 ? 64 : 32)) != 0 || (epi == EPI_SWIGLU && (N % 32) != 0))
+        FAIL(c, MMD_EINVAL, "gemv_chain: 1 <= M <= 16, N %% 16 == 0 (SwiGLU: %% 32), K %% 32 == 0 (fp8: %% 64); got %d x %d x %d", M, N, K);
+    hipSetDevice(c->device);
+    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    GemvChain ch;
+    if (role == GEMV_PRODUCER) { ch.fin_h = h; ch.fin_ssq = ssq; }
+    else { ch.xn_h = h; ch.xn_gamma = gamma; ch.xn_ssq = ssq; ch.xn_eps = eps; }
+    int splits = 0;
+    // the planner looks at null / non-null / alignment of the weight pointers only: W stands in for its packed copies until the plan is known
+    GemmArgs a;
+    if (role == GEMV_CONSUMER && epi == EPI_SWIGLU) a = gemm_args(c, X, K, W, K, nullptr, nullptr, 0, Y, N / 2, M, N, K, EPI_SWIGLU, 0, GEMM_AUTO, W, false, q8, scale);
+    else {
+        a = slab_args(c, X, K, W, M, N, K);
+        a.Wp8 = q8; a.wscale = scale; a.slabs_out = &splits;
+        if (role == GEMV_CONSUMER) { a.splitk_ws = (float*)Y; a.splitk_ws_bytes = (size_t)max_splits * M * N * sizeof(float); }
+    }
+    a.chain = &ch; a.plan_out = c->last_plan;
+    const GemmPlan pl = gemm_plan_for(c->cfg.dtype, a);
+    if (!pl.valid() || pl.kernel != GEMM_K_GEMV16 || pl.chain != role) FAIL(c, MMD_EINVAL, "gemv_chain: the planner gives role %d no chain GEMV at %d x %d x %d", role, M, N, K);
+    void *Wp = nullptr, *Wp8 = nullptr;
+    int rc = make_packed(c, W, N, K, &Wp); if (rc) return rc;
+    if (q8) { rc = dev_alloc(c, &Wp8, (size_t)N * K, false); if (rc) { dev_free(c, Wp); return rc; } }
+    hipError_t e = q8 ? launch_pack_w8(q8, N, K, Wp8, c->stream) : hipSuccess;
+    a.Wp = Wp; a.Wp8 = Wp8;
+    if (role == GEMV_PRODUCER || epi == EPI_NONE) a.W = nullptr;          // (slab_gemm knows the packed copies only)
+    if (e == hipSuccess) e = launch_gemm(c->cfg.dtype, a, c->stream, &pl);
+    hipStreamSynchronize(c->stream);
+    dev_free(c, Wp); if (Wp8) dev_free(c, Wp8);
+    if (e != hipSuccess) FAIL(c, MMD_EHIP, "gemv_chain: launch failed: %s", hipGetErrorString(e));
+    if (splits_out) *splits_out = role == GEMV_CONSUMER && epi == EPI_NONE ? splits : 0;
+    return MMD_OK;
+}
 extern "C" int mmd_op_rope_append(mmd_ctx* c, void* qkv, int S, int nh, int nkv, int d, float theta, int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap) {
     if (!c) return MMD_EINVAL; hipSetDevice(c->device);
     std::vector<float> t(d / 2);

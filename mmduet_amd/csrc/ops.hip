@@ -287,12 +287,14 @@ __global__ __launch_bounds__(256) void slab_resid_rmsnorm_kernel(const float* __
         }
     }
 }
+int slab_resid_maxs(int splits) { return splits <= 4 ? 4 : (splits <= 8 ? 8 : 16); }
 hipError_t launch_slab_resid_rmsnorm(const float* slabs, int splits, int M, int H, const void* resid_in, void* h_out, const void* norm_w, float eps,
                                      void* xn_out, hipStream_t st, const float* wscale) {
     if (M <= 0) return hipSuccess;
     if (H > 4096 || (H & 3) || splits > 16) return hipErrorInvalidValue;
-    if (splits <= 4) hipLaunchKernelGGL(slab_resid_rmsnorm_kernel<4>, dim3(M), dim3(256), 0, st, slabs, splits, M, H, (const bf16_t*)resid_in, (bf16_t*)h_out, (const bf16_t*)norm_w, eps, (bf16_t*)xn_out, wscale);
-    else if (splits <= 8) hipLaunchKernelGGL(slab_resid_rmsnorm_kernel<8>, dim3(M), dim3(256), 0, st, slabs, splits, M, H, (const bf16_t*)resid_in, (bf16_t*)h_out, (const bf16_t*)norm_w, eps, (bf16_t*)xn_out, wscale);
+    const int maxs = slab_resid_maxs(splits);
+    if (maxs == 4) hipLaunchKernelGGL(slab_resid_rmsnorm_kernel<4>, dim3(M), dim3(256), 0, st, slabs, splits, M, H, (const bf16_t*)resid_in, (bf16_t*)h_out, (const bf16_t*)norm_w, eps, (bf16_t*)xn_out, wscale);
+    else if (maxs == 8) hipLaunchKernelGGL(slab_resid_rmsnorm_kernel<8>, dim3(M), dim3(256), 0, st, slabs, splits, M, H, (const bf16_t*)resid_in, (bf16_t*)h_out, (const bf16_t*)norm_w, eps, (bf16_t*)xn_out, wscale);
     else hipLaunchKernelGGL(slab_resid_rmsnorm_kernel<16>, dim3(M), dim3(256), 0, st, slabs, splits, M, H, (const bf16_t*)resid_in, (bf16_t*)h_out, (const bf16_t*)norm_w, eps, (bf16_t*)xn_out, wscale);
     return hipGetLastError();
 }

@@ -144,6 +144,25 @@ class RawOps:
         torch.cuda.synchronize()
         return rc
 
+    def slab_resid_rmsnorm(self, slabs, resid, h_out, norm_w, eps, xn_out, wscale=None, splits=None, M=None, H=None):
+        """mmd_op_slab_resid_rmsnorm on caller-owned device buffers (slabs fp32 [splits, M, H]; h_out may be resid).  -> the return code: refusals are part of what is tested"""
+        splits = slabs.shape[0] if splits is None else splits
+        M = slabs.shape[1] if M is None else M
+        H = slabs.shape[2] if H is None else H
+        self.m._bind_stream()
+        rc = lib().mmd_op_slab_resid_rmsnorm(self.ctx, _ptr(slabs), splits, M, H, _ptr(resid), _ptr(h_out), _ptr(norm_w), eps, _ptr(xn_out), _ptr(wscale))
+        torch.cuda.synchronize()
+        return rc
+
+    def gemv_chain(self, role, X, W, h, ssq, M, N, K, gamma=None, eps=0.0, Y=None, q8=None, scale=None, epi='none', max_splits=0):
+        """mmd_op_gemv_chain on caller-owned device buffers: role 2 the producer (h [M, N] in place, ssq written), role 1 the consumer (h [M, K], gamma, ssq read; Y fp32 slabs
+        with room for max_splits, or the SwiGLU product).  -> (return code, slabs written)"""
+        n = C.c_int(0)
+        self.m._bind_stream()
+        rc = lib().mmd_op_gemv_chain(self.ctx, role, _ptr(X), _ptr(W), _ptr(q8), _ptr(scale), _ptr(h), _ptr(gamma), _ptr(ssq), eps, _ptr(Y), M, N, K, EPI[epi], max_splits, C.byref(n))
+        torch.cuda.synchronize()
+        return rc, n.value
+
     def attention_last_form(self):
         f = (C.c_int * 2)()
         check(lib().mmd_op_attention_last_form(self.ctx, f), self.ctx, 'attention_last_form')

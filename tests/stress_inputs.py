@@ -14,10 +14,11 @@ owns every row's softmax (None where no single key does).  With c = d ** -0.5 an
   first_row_only  sink with n_ctx = 0: row 0 sees exactly one key
 
 GEMM builders: outlier_x (six channels of X at 10^3 .. 10^4), weights (randn / sqrt(K)), saturating (pre-activations of standard deviation amp / 3), and
-the element-wise bound the stress GEMM tests use (acc_floor / rounding_tol)."""
+the element-wise bound the stress GEMM tests use (acc_floor / rounding_tol / epilogue_bound)."""
 import math
 from collections import namedtuple
 import torch
+import torch.nn.functional as F
 
 AttnCase = namedtuple('AttnCase', 'q K V n_ctx hot')
 BF = torch.bfloat16
@@ -150,6 +151,34 @@ def rounding_tol(points, a):
     for p in points:
         t = t + U_BF16 * (p.abs() + a)
     return t
+
+
+def swiglu_split(t):
+    """[M, N] in the interleaved SwiGLU column order -> (gate [M, N/2], up [M, N/2])"""
+    v = t.reshape(t.shape[0], -1, 2, 16)
+    return v[:, :, 0].reshape(t.shape[0], -1), v[:, :, 1].reshape(t.shape[0], -1)
+
+
+def epilogue_bound(epi, lin, a, R=None, r=1):
+    """-> (ref, tol) for a kernel output; lin = X W^T (+ bias) in float64, a = acc_floor, r = 1 bf16 output / 0 fp32"""
+    u = U_BF16 * r
+    act = 2.0 ** -20
+    if epi == 'swiglu':
+        g, up = swiglu_split(lin); ag, au = swiglu_split(a)
+        eg = u * (g.abs() + ag) + ag; eu = u * (up.abs() + au) + au
+        s = F.silu(g)
+        es = 1.1 * eg + u * (s.abs() + 1.1 * eg) + act * s.abs() + 1e-6
+        ref = s * up
+        t = up.abs() * es + s.abs() * eu + es * eu
+        return ref, t + u * (ref.abs() + t)
+    if epi == 'resid':
+        ref = lin + R.double()
+        return ref, u * (lin.abs() + a) + u * (ref.abs() + a + u * lin.abs()) + a
+    if epi in ('gelu_tanh', 'gelu_erf'):
+        ref = F.gelu(lin, approximate='tanh' if epi == 'gelu_tanh' else 'none')
+        e = u * (lin.abs() + a) + a
+        return ref, 1.13 * e + u * (ref.abs() + 1.13 * e) + act * ref.abs() + 1e-6
+    return lin, u * (lin.abs() + a) + a
 
 
 def old_max_norm_err(Y, ref):

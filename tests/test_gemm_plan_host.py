@@ -99,10 +99,12 @@ def test_rejections(plan):
     qkv16, qkv17 = _row('gemm_qkv_16'), _row('gemm_qkv_17')
     assert plan(**dict(qkv16, variant=STREAM_V))['kernel'] == INVALID            # GEMM_STREAM on a shape stream_ok refuses (M <= 32)
     assert plan(**dict(_row('gemm_lm_head_65'), variant=STREAM_V))['kernel'] == INVALID          # ... (fp32 output)
-    assert plan(**qkv16, chain=1)['kernel'] == T.GEMV16 and plan(**qkv16, chain=1)['chain'] == 1
-    assert plan(**qkv16, chain=2)['chain'] == 2 and plan(**qkv16, chain=2)['blocks'] == 288
+    qkv2, o2 = _row('gemm_qkv_2'), _row('gemm_o_2')
+    assert plan(**qkv2, chain=1)['kernel'] == T.GEMV16 and plan(**qkv2, chain=1)['chain'] == 1
+    assert plan(**o2, chain=2)['chain'] == 2 and plan(**o2, chain=2)['blocks'] == 224
     assert plan(**qkv17, chain=1)['kernel'] == INVALID                           # the decode chain exists in the GEMV kernel only
-    assert plan(**qkv16, chain=1, no_gemv=1)['kernel'] == INVALID
+    assert plan(**qkv2, chain=1, no_gemv=1)['kernel'] == INVALID
+    assert plan(**qkv16, chain=1)['kernel'] == INVALID and plan(**qkv16, chain=2)['kernel'] == INVALID          # ... and there within its LDS rows / ssq entries (below)
     slab = _row('slabs_qkv_256')
     assert plan(**dict(slab, M=257, ws_bytes=16 * 257 * 4608 * 4))['kernel'] == INVALID          # slabs_out on a shape no slab kernel takes
     assert plan(**dict(slab, K=3600))['kernel'] == INVALID                       # ... K is not a whole number of steps
@@ -116,6 +118,42 @@ def test_rejections(plan):
     assert plan(**dict(_row('gemm_lm_head_65'), variant=BIG_V))['kernel'] == INVALID
     assert plan(**dict(_row('gemm_gate_up_513'), ring_flags=24))['kernel'] == INVALID            # a ring instantiation that is not in the library
     assert plan(**dict(qkv16, M=0))['kernel'] == -2                              # nothing to launch
+
+
+def test_chain_forms_are_refused_outside_the_kernels_limits(plan):
+    """A consumer keeps GEMV_CHAIN_ROWS = 4 rows x 1024 k per wave in LDS, a producer's ssq has GEMV_SSQ_STRIDE = 256 n-tile entries per row: both sides of each bound.  The
+    plain GEMV at the same shapes is untouched."""
+    def consumer(M, N, K, room, **kw):          # layer_qkv's form: fp32 slabs into a workspace with room for `room` of them
+        return plan(M=M, N=N, K=K, epi=EPI['none'], variant=SKINNY_V, X=X_, ldx=K, Wp=WP_, ws=WS_, ws_bytes=room * M * N * 4, slabs_out=1, chain=1, **kw)
+
+    def gate_up(M, N, K, **kw):                 # layer_tail_chain's form: SwiGLU in place, never split
+        return plan(M=M, N=N, K=K, epi=EPI['swiglu'], variant=AUTO, X=X_, ldx=K, W=W_, ldw=K, Wp=WP_, Y=Y_, ldy=N // 2, ws=WS_, ws_bytes=64 << 20, chain=1, **kw)
+
+    def producer(M, N, K, **kw):
+        return plan(M=M, N=N, K=K, epi=EPI['none'], variant=SKINNY_V, X=X_, ldx=K, Wp=WP_, ws=WS_, ws_bytes=64 << 20, slabs_out=1, chain=2, **kw)
+    # rows: 4 | 5
+    p = consumer(4, 4608, 3584, 4)
+    assert (p['kernel'], p['chain'], p['splits'], p['blocks']) == (T.GEMV16, 1, 2, 576), p
+    assert consumer(5, 4608, 3584, 4)['kernel'] == INVALID and gate_up(5, 37888, 3584)['kernel'] == INVALID
+    assert gate_up(4, 37888, 3584)['chain'] == 1
+    # K per wave at one split: 4096 / 4 = 1024 | 4128 -> 33 k-tiles = 1056
+    p = consumer(1, 512, 4096, 1)
+    assert (p['kernel'], p['chain'], p['splits']) == (T.GEMV16, 1, 1), p
+    assert consumer(1, 512, 4128, 1)['kernel'] == INVALID
+    assert gate_up(1, 64, 4096)['splits'] == 1 and gate_up(1, 64, 4096)['chain'] == 1 and gate_up(1, 64, 4128)['kernel'] == INVALID
+    # ... the bound is on the wave's range, not on K: two splits halve it (4128 -> 17 k-tiles per wave = 544; 8192 -> 1024; 8224 -> 1056)
+    assert consumer(1, 512, 4128, 4)['splits'] == 2 and consumer(1, 512, 4128, 4)['kernel'] == T.GEMV16
+    assert consumer(1, 512, 8192, 1)['kernel'] == INVALID
+    # ... fp8 weights: ranges in pairs of k-tiles (4096 -> 16 pairs = 1024 | 4160 -> 17 pairs = 1088)
+    assert consumer(1, 512, 4096, 1, Wp8=WP8_, wscale=SC_)['kernel'] == T.GEMV16 and consumer(1, 512, 4160, 1, Wp8=WP8_, wscale=SC_)['kernel'] == INVALID
+    # producer: N = 16 x 256 | one tile more
+    p = producer(4, 4096, 3584)
+    assert (p['kernel'], p['chain'], p['splits'], p['blocks']) == (T.GEMV16, 2, 1, 256), p
+    assert producer(4, 4112, 3584)['kernel'] == INVALID
+    assert producer(16, 4096, 18944)['chain'] == 2          # (a producer keeps nothing per row: any M of the GEMV)
+    # the plain GEMV has no such limits
+    for M, N, K in ((5, 4608, 3584), (1, 512, 4128), (1, 4112, 3584), (16, 512, 8192)):
+        assert plan(M=M, N=N, K=K, epi=EPI['none'], variant=SKINNY_V, X=X_, ldx=K, Wp=WP_, ws=WS_, ws_bytes=M * N * 4, slabs_out=1)['kernel'] == T.GEMV16
 
 
 def test_fp32_contexts_take_the_generic_kernels(plan):

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 import gemm_regimes as T
 import stress_inputs as SI
+import residual_stream as RS
 
 C_ACC = SI.C_ACC
 U = SI.U_BF16
@@ -47,32 +48,7 @@ def _ops(env, dtype=torch.bfloat16, mst=1024):
     return env[(dtype, mst)]
 
 
-def _split(t):
-    """[M, N] in the interleaved SwiGLU column order -> (gate [M, N/2], up [M, N/2])"""
-    v = t.reshape(t.shape[0], -1, 2, 16)
-    return v[:, :, 0].reshape(t.shape[0], -1), v[:, :, 1].reshape(t.shape[0], -1)
-
-
-def _bound(epi, lin, a, R=None, r=1):
-    """-> (ref, tol) for a kernel output; lin = X W^T (+ bias) in float64, a = acc_floor, r = 1 bf16 output / 0 fp32"""
-    u = U * r
-    act = 2.0 ** -20
-    if epi == 'swiglu':
-        g, up = _split(lin); ag, au = _split(a)
-        eg = u * (g.abs() + ag) + ag; eu = u * (up.abs() + au) + au
-        s = F.silu(g)
-        es = 1.1 * eg + u * (s.abs() + 1.1 * eg) + act * s.abs() + 1e-6
-        ref = s * up
-        t = up.abs() * es + s.abs() * eu + es * eu
-        return ref, t + u * (ref.abs() + t)
-    if epi == 'resid':
-        ref = lin + R.double()
-        return ref, u * (lin.abs() + a) + u * (ref.abs() + a + u * lin.abs()) + a
-    if epi in ('gelu_tanh', 'gelu_erf'):
-        ref = F.gelu(lin, approximate='tanh' if epi == 'gelu_tanh' else 'none')
-        e = u * (lin.abs() + a) + a
-        return ref, 1.13 * e + u * (ref.abs() + 1.13 * e) + act * ref.abs() + 1e-6
-    return lin, u * (lin.abs() + a) + a
+_split, _bound = SI.swiglu_split, SI.epilogue_bound          # (shared with tests/test_gpu_residual_stream.py)
 
 
 def _check(name, Y, ref, tol):
@@ -256,9 +232,7 @@ def test_norms_with_an_element_at_1e4(env, dtype, H):
     rel = U if bf else 1e-5
     # RMSNorm
     y = ops.rmsnorm(x, w, 1e-6).double()
-    xn = xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + 1e-6)
-    cands = [wd * ((xn * (1 + s * 2.0 ** -20)).to(torch.bfloat16).double() if bf else xn) for s in (-1, 0, 1)]
-    err = torch.stack([(y - c).abs() - (rel * c.abs() + floor) for c in cands]).amin(0)
+    err = RS.rms_excess(y, RS.rms_candidates(x, w, 1e-6, rounded=bf), rel, floor)          # (the rule lives in tests/residual_stream.py: the slab and chain tests apply it too)
     assert torch.isfinite(y).all() and err.max().item() <= 0, ('rmsnorm', H, err.max().item())
     assert bool((y[5] == 0).all())
     # LayerNorm
