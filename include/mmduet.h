@@ -29,7 +29,7 @@ extern "C" {
 #define MMD_ENOENT (-2)
 #define MMD_ERANGE (-34)
 #define MMD_EHIP (-5)
-#define MMD_EDOM (-33)         /* a NaN among the logits a token was to be drawn from */
+#define MMD_EDOM (-33)         /* a NaN among the logits a token was to be drawn from, or -- under constraints -- no score above -inf */
 
 typedef enum { MMD_F32 = 0, MMD_BF16 = 1 } mmd_dtype;
 /* storage of the decoder's linear-layer weights (q/k/v/o/gate/up/down): MMD_W_FP8_E4M3 = OCP e4m3fn with one fp32 scale per output
@@ -258,6 +258,24 @@ int mmd_set_sample_lane(mmd_ctx* ctx, int lane);
 int mmd_set_generate_logprobs(mmd_ctx* ctx, int top_n);
 int mmd_generate_logprobs_read(mmd_ctx* ctx, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out);
 
+/* Constrained decoding (DESIGN.md "Constraints"; what HF generate gives the reference class through eos_token_id lists, min_new_tokens, suppress_tokens, single-token
+ * bad_words_ids and sequence_bias, models/live_llava/video_head_live_llava_qwen.py:231).  For the fp32 lm_head logits l of a step the chain's score becomes
+ *   z_i = mask_i(pen(l_i + b_i)) / T
+ * b_i: the bias of id i in the table (0 when absent; -inf = suppressed); pen: the repetition penalty, once per id, on l_i + b_i; mask_i = -inf when i is suppressed or when i is
+ * one of the EOS ids and fewer than min_new tokens have been returned so far in this response.  Everything behind z is the chain as it was (DESIGN.md "Sampling"); the arg-max
+ * is the first maximal index of z at T = 1.  A token equal to ANY of the EOS ids ends the response: returned, not fed back, not appended to the penalty list.  With recording
+ * on, logprob and the top_n alternatives stay over the raw logits; sampling_logprob is over z.
+ * mmd_set_generate_constraints holds for the following mmd_greedy_generate / mmd_sample_generate calls (host arrays, copied before it returns): eos_ids [n_eos <= 8] -- with a
+ * set given the calls' own eos_id is ignored, with none it stays the one EOS id --, min_new >= 0, the table ids [n <= 256] (unique, in [0, vocab)) with bias [n] (finite or
+ * -inf).  n_eos = min_new = n = 0 is off, the default: the calls then enqueue what they enqueue without this feature.  MMD_EINVAL: a limit above is broken, a bias is NaN or
+ * +inf, or the suppressed ids together with the EOS ids cover the vocabulary.  Switching on or off gives another captured decode step; new values of a set that stays on are
+ * re-uploaded into the context's buffers and the captured step is replayed as it is.  Per token: a row whose every z is -inf (the raw logits may hold -inf themselves) fails the
+ * call with MMD_EDOM like a NaN row, on the arg-max and on the draw route.
+ * mmd_sampler_set_constraints: the same per sampler (the table lives in a sampler-owned device buffer, uploaded synchronously); a round of mmd_round_multi may mix constrained
+ * and unconstrained samplers, arg-max and sampled. */
+int mmd_set_generate_constraints(mmd_ctx* ctx, const int64_t* eos_ids_host, int n_eos, int min_new, const int32_t* ids_host, const float* bias_host, int n);
+int mmd_sampler_set_constraints(mmd_sampler* sp, const int64_t* eos_ids_host, int n_eos, int min_new, const int32_t* ids_host, const float* bias_host, int n);
+
 /* ---- multi-GPU: the one collective of the path ------------------------------------------------------------------ */
 /* The reference shards videos over N manually launched processes (--start_idx/--end_idx, test/inference.py:337) and has no
  * collective; here one process per GPU gathers the per-frame head scores of its streams with ONE RCCL all-gather over xGMI.
@@ -328,6 +346,14 @@ int mmd_op_sample(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t
 int mmd_op_sample_logprobs(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
                            uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n, int64_t* tokens_out, float* info_out, float* scores_out,
                            float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host);
+/* mmd_op_sample_logprobs with one constraint set per row (the limits of mmd_set_generate_constraints, checked per row): row i's table is entries [tab_off_host[i],
+ * tab_off_host[i + 1]) of tab_ids_host / tab_bias_host, its EOS ids eos_host[i * 8 ..] (n_eos_host[i] of them), min_new_host[i], and step_host[i] = tokens returned so far.
+ * greedy != 0: the constrained arg-max.  lp_out_host may be NULL (nothing recorded, top_n ignored).  MMD_EDOM when a row has a NaN or nothing above -inf (its token is -1). */
+int mmd_op_sample_constrained(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                              uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n,
+                              const int32_t* tab_off_host, const int32_t* tab_ids_host, const float* tab_bias_host, const int64_t* eos_host, const int32_t* n_eos_host,
+                              const int32_t* min_new_host, const int32_t* step_host,
+                              int64_t* tokens_out, float* info_out, float* scores_out, float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host);
 int mmd_op_rmsnorm(mmd_ctx* ctx, const void* x, const void* w, void* y, int M, int H, float eps);
 int mmd_op_layernorm(mmd_ctx* ctx, const void* x, const void* w, const void* b, void* y, int M, int H, float eps);
 /* the autocast tower's residual step (models/modeling_live.py:28: `hidden (fp32) + sublayer_out (fp16)` promotes, LayerNorm returns fp32, the next linear casts to

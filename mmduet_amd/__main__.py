@@ -40,6 +40,10 @@ def main(argv=None):
     sp.add_argument('--top_k', type=int, default=0)
     sp.add_argument('--top_p', type=float, default=1.0)
     sp.add_argument('--sampling_seed', type=int, default=0)
+    # constrained decoding (DESIGN.md "Constraints"): an EOS set of up to 8 ids (default: the config's one), the fewest tokens of a response, ids no response may contain
+    sp.add_argument('--eos_token_ids', type=int, nargs='+', default=None)
+    sp.add_argument('--min_new_tokens', type=int, default=0)
+    sp.add_argument('--suppress_tokens', type=int, nargs='*', default=[])
     for k, v in vars(sp.parse_known_args(sys.argv[1:] if argv is None else argv)[0]).items():
         setattr(args, k, v)
     args.output_logprobs, args.top_logprobs = args.logprobs is not None, args.logprobs or 0

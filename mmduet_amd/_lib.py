@@ -99,6 +99,8 @@ _SIGS = {
     'mmd_sample_generate': (_I, [_VP, _VP, _VP, _I, _I64, _F, _VP, C.POINTER(_I), _I, _F, _I, _F, C.c_uint64, C.POINTER(C.c_uint64), _VP, _I, C.POINTER(_I)]),
     'mmd_set_sample_lane': (_I, [_VP, _I]),
     'mmd_set_generate_logprobs': (_I, [_VP, _I]),
+    'mmd_set_generate_constraints': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I]),
+    'mmd_sampler_set_constraints': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I]),
     'mmd_generate_logprobs_read': (_I, [_VP, _VP, _VP, _VP, _VP, _I, C.POINTER(_I)]),
     'mmd_prof_enable': (_I, [_VP, _I]),
     'mmd_prof_set_stride': (_I, [_VP, _I]),
@@ -114,6 +116,7 @@ _SIGS = {
     'mmd_op_gemm_w8': (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I]),
     'mmd_op_sample': (_I, [_VP, _VP, _I, _I, _VP, _I, _F, _F, _I, _F, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
     'mmd_op_sample_logprobs': (_I, [_VP, _VP, _I, _I, _VP, _I, _F, _F, _I, _F, C.c_uint64, C.c_uint64, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'mmd_op_sample_constrained': (_I, [_VP, _VP, _I, _I, _VP, _I, _F, _F, _I, _F, C.c_uint64, C.c_uint64, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     'mmd_op_rmsnorm': (_I, [_VP, _VP, _VP, _VP, _I, _I, _F]),
     'mmd_op_layernorm': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _F]),
     'mmd_op_resid32_layernorm': (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _I, _I, _F]),

@@ -123,7 +123,9 @@ hipError_t launch_slab_rope_append(const float* slabs, int splits, const void* b
                                    int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st, const StepState* dyn = nullptr, int layer = 0,
                                    int slab_rows = 0);          // slab_rows: rows of one slab when the projection ran over more rows than this stream's S (0 = S); `slabs` points at the stream's first row
 hipError_t launch_rope_table(void* tab, int S, int half, const float* inv_freq_dev, int64_t pos0, hipStream_t st, const StepState* dyn = nullptr);   // float2 [S][half], bf16-rounded
-hipError_t launch_advance_state(StepState* st_dev, const int64_t* tok_dev, int64_t* prev_dev, int prev_cap, int64_t eos, int use_penalty, hipStream_t st);
+struct ConstraintRow;
+hipError_t launch_advance_state(StepState* st_dev, const int64_t* tok_dev, int64_t* prev_dev, int prev_cap, int64_t eos, int use_penalty, hipStream_t st,
+                                const ConstraintRow* cons_dev = nullptr);          // cons_dev: EOS is membership of its set (read on the device), `eos` is ignored
 hipError_t launch_add_rows(int dtype, void* x, const void* add, int M, int H, int period, hipStream_t st);   // x[m,:] += add[m % period,:]
 hipError_t launch_rope_append_chunk(const void* qkv, int S, int nh, int nkv, const void* tab, int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st);   // bf16, d = 128, transposed V, table from launch_rope_table
 hipError_t launch_rope_append(int dtype, const void* qkv, int S, int nh, int nkv, int d, const float* inv_freq_dev, int64_t pos0, void* q_out,
@@ -154,6 +156,16 @@ struct SampleRow {
     uint32_t seed_lo, seed_hi, lane, advance;
 };
 constexpr int SMP_MAX_SLICES = 64;
+// constrained decoding (DESIGN.md "Constraints"): one ConstraintRow per logits row, in DEVICE memory beside its SampleRow.  The table is (id, bias) sorted by id, ids unique,
+// bias finite or -inf (= suppressed);  z_i = mask_i(pen(l_i + b_i)) / T, mask = -inf for a suppressed id and -- while fewer than min_new tokens have been returned -- for the
+// EOS ids.  step = tokens returned so far in this response; step_ptr (the captured step: &StepState::step) overrides it.  A row with n = 0, n_eos = 0 is unconstrained.
+constexpr int CONS_MAX_TABLE = 256, CONS_MAX_EOS = 8;
+struct ConstraintRow {
+    const int32_t* ids; const float* bias; const int* step_ptr;
+    long long eos[CONS_MAX_EOS];
+    int n, n_eos, min_new, step;
+};
+__host__ __device__ inline bool cons_is_eos(const ConstraintRow& c, long long t) { for (int k = 0; k < c.n_eos; ++k) if (c.eos[k] == t) return true; return false; }
 // log-probability records (sample.hip): one per token.  lp = log-probability under the model (raw logits), slp = under the distribution the token was taken from, then the
 // top_n largest raw logits as ids (-1: the row is shorter) and their lp.  LogprobOut says where row r of a launch records: slot (dyn ? dyn->step : idx0) + r of rec[cap] (a slot
 // beyond cap is not written), for the token toks[r]; rec == null: nothing is recorded.
@@ -163,10 +175,13 @@ struct LogprobOut { LogprobRec* rec; int cap; const StepState* dyn; int idx0; co
 size_t sample_topkp_scratch_bytes(int V, int n, bool own_scores);          // n <= MMD_ROUND_MAX_SAMPLERS rows per launch; own_scores: the z rows live in the scratch
 hipError_t launch_sample_batch_topkp(const float* logits /*[n, V]*/, int V, int n, SampleRow* rows_dev, bool any_k, bool any_p, const unsigned long long* r_words_dev /* or null: Philox */,
                                      int64_t* toks_out_dev, float* info_out_dev /* [n,4] or null */, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st,
-                                     const LogprobOut* lp = nullptr /* the draw records slp */);
+                                     const LogprobOut* lp = nullptr /* the draw records slp */, const ConstraintRow* cons_dev = nullptr /* [n] or null: no row is constrained */);
 size_t logprob_scratch_bytes(int n);
 // the chain's scores z = pen(l) / T with nothing filtered (rows with top_k 0, top_p 1): maxima, masses and z stay in `scratch` for launch_logprob_rows(greedy)
-hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, const SampleRow* rows_dev, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st);
+hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, const SampleRow* rows_dev, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st,
+                                           const ConstraintRow* cons_dev = nullptr);
+// the constrained arg-max: first maximal index of the z that launch_sample_scores_unfiltered left in `scratch` (-1: a NaN, or every z is -inf) -> rows[r].tok / .append, toks_out[r]
+hipError_t launch_argmax_scores(int V, int n, const SampleRow* rows_dev, float* scores_out_dev, void* scratch, int64_t* toks_out_dev /* or null */, hipStream_t st);
 // lp and the top_n of n <= MMD_ROUND_MAX_SAMPLERS rows; greedy: slp too, from what launch_sample_scores_unfiltered left in sample_scratch (same scores_out_dev)
 hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st);
 // streaming cross entropy over lm_head logit chunks (mmd_lm_nll; ops.hip): fold chunk `logits` [m, nc] (row stride ld, ld % 4 == 0; vocabulary columns [c0, c0 + nc)) into

@@ -33,10 +33,14 @@ struct Prof {
     double ms[MMD_K_COUNT] = {0}; int64_t n[MMD_K_COUNT] = {0}; double bytes[MMD_K_COUNT] = {0}; double flops[MMD_K_COUNT] = {0};
 };
 
+// a validated constraint set on the host (DESIGN.md "Constraints"): the table sorted by id, ids unique
+struct ConsSet { bool on = false; int n = 0, n_eos = 0, min_new = 0; int64_t eos[CONS_MAX_EOS] = {}; int32_t ids[CONS_MAX_TABLE] = {}; float bias[CONS_MAX_TABLE] = {}; };
+
 // one captured decode step: the instantiated graph, its source, and the (penalty, EOS, filter selection) it was captured for
 struct DecodeGraph {
     hipGraphExec_t exec = nullptr; hipGraph_t src = nullptr;
     float pen = 0.f; int64_t eos = 0; int sel = 0; int lp = -1;          // lp: log-probability recording of the step (-1 off, else its top_n)
+    uint32_t cons = 0;          // constraints: 0 the step was captured without, 1 with (its sets are read from device memory)
     void drop() {
         if (exec) { hipGraphExecDestroy(exec); exec = nullptr; }
         if (src) { hipGraphDestroy(src); src = nullptr; }
@@ -123,6 +127,10 @@ struct mmd_ctx {
     // log-probabilities of generated tokens (mmd_set_generate_logprobs; allocated at their first use): lp_top = the setting (-1 off), lp_rec [lp_cap] the device records of the
     // most recent generate call, lp_n of them valid with lp_call_top alternatives each
     int lp_top = -1, lp_cap = 0, lp_n = 0, lp_call_top = -1; LogprobRec* lp_rec = nullptr; void* lp_scratch = nullptr;
+    // constrained decoding (mmd_set_generate_constraints; allocated at its first use): the validated set, the key the captured steps carry for it (0 off, 1 on: a call that
+    // sets, generates and clears finds its step again), row descriptors on the device ([0] the generate calls', [1..] a round's) with their pinned staging, and descriptor 0's table
+    ConsSet cons; uint32_t cons_gen = 0;
+    ConstraintRow* cons_rows_dev = nullptr; ConstraintRow* cons_rows_host = nullptr; int32_t* cons_ids_dev = nullptr; float* cons_bias_dev = nullptr;
     Prof prof;
 };
 
@@ -294,6 +302,7 @@ extern "C" void mmd_destroy(mmd_ctx* c) {
     if (c->seg_host) hipHostFree(c->seg_host);
     if (c->round_toks_host) hipHostFree(c->round_toks_host);
     if (c->samp_rows_host) hipHostFree(c->samp_rows_host);
+    if (c->cons_rows_host) hipHostFree(c->cons_rows_host);
     for (auto& ev : c->seg_event) if (ev) hipEventDestroy(ev);
     c->dec_greedy.drop(); c->dec_sampled.drop();
     hipStreamDestroy(c->own_stream);
@@ -1573,7 +1582,68 @@ struct mmd_sampler {
     int64_t eos = -1; float penalty = 0.f;
     // sampling (mmd_sampler_set_sampling): off = arg-max.  `offset` counts the tokens drawn since the seed was set; `lane` is the sampler's id within its context
     bool sampling = false, seeded = false; float temperature = 1.f, top_p = 1.f; int top_k = 0; uint64_t seed = 0, offset = 0; uint32_t lane = 0;
+    // constraints (mmd_sampler_set_constraints): the set, its table on the device (sampler-owned, uploaded synchronously), tokens returned so far in this response
+    ConsSet cons; int32_t* cons_ids_dev = nullptr; float* cons_bias_dev = nullptr; int step = 0;
 };
+
+// ---- constraints: validation and the device descriptors ------------------------------------------------------------------------------------------------------------------
+// limits checked when a set is given, not per token (include/mmduet.h): <= 8 EOS ids and <= 256 unique table ids, all in [0, V); bias finite or -inf; min_new >= 0; the
+// suppressed ids and the EOS ids together must leave a token.  n_eos = min_new = n = 0 is "off".  The table is sorted by id for the kernel's binary search.
+static int cons_validate(mmd_ctx* c, int V, const int64_t* eos_ids, int n_eos, int min_new, const int32_t* ids, const float* bias, int n, ConsSet& out) {
+    if (n_eos < 0 || n < 0 || (n_eos > 0 && !eos_ids) || (n > 0 && (!ids || !bias))) FAIL(c, MMD_EINVAL, "bad constraint arguments");
+    if (n_eos > CONS_MAX_EOS) FAIL(c, MMD_EINVAL, "at most %d EOS ids, got %d", CONS_MAX_EOS, n_eos);
+    if (n > CONS_MAX_TABLE) FAIL(c, MMD_EINVAL, "at most %d biased / suppressed ids, got %d", CONS_MAX_TABLE, n);
+    if (min_new < 0) FAIL(c, MMD_EINVAL, "min_new_tokens %d is negative", min_new);
+    ConsSet s;
+    for (int k = 0; k < n_eos; ++k) {
+        if (eos_ids[k] < 0 || eos_ids[k] >= V) FAIL(c, MMD_EINVAL, "EOS id %lld outside the vocabulary of %d", (long long)eos_ids[k], V);
+        s.eos[k] = eos_ids[k];
+    }
+    std::vector<std::pair<int32_t, float>> t((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= V) FAIL(c, MMD_EINVAL, "table id %d outside the vocabulary of %d", ids[k], V);
+        if (bias[k] != bias[k] || bias[k] == INFINITY) FAIL(c, MMD_EINVAL, "the bias of id %d is %s: finite or -inf only", ids[k], bias[k] != bias[k] ? "NaN" : "+inf");
+        t[k] = {ids[k], bias[k]};
+    }
+    std::sort(t.begin(), t.end(), [](const std::pair<int32_t, float>& a, const std::pair<int32_t, float>& b) { return a.first < b.first; });
+    for (int k = 1; k < n; ++k) if (t[k].first == t[k - 1].first) FAIL(c, MMD_EINVAL, "table id %d is listed twice", t[k].first);
+    long long covered = 0;
+    for (int k = 0; k < n; ++k) { s.ids[k] = t[k].first; s.bias[k] = t[k].second; if (t[k].second == -INFINITY) ++covered; }
+    for (int k = 0; k < n_eos; ++k) {
+        bool dup = false;
+        for (int j = 0; j < k; ++j) dup |= s.eos[j] == s.eos[k];
+        for (int j = 0; j < n; ++j) dup |= s.ids[j] == s.eos[k] && s.bias[j] == -INFINITY;
+        if (!dup) ++covered;
+    }
+    if ((n > 0 || n_eos > 0) && covered >= V) FAIL(c, MMD_EINVAL, "the suppressed ids and the EOS ids cover the whole vocabulary of %d: no token could be returned", V);
+    s.n = n; s.n_eos = n_eos; s.min_new = min_new; s.on = n > 0 || n_eos > 0 || min_new > 0;
+    out = s;
+    return MMD_OK;
+}
+// the device descriptor of a set: an empty EOS set falls back to the call's / sampler's own eos id
+static void cons_fill_row(ConstraintRow& r, const ConsSet& s, const int32_t* ids_dev, const float* bias_dev, int64_t eos_id, int V, int step, const int* step_ptr) {
+    r.ids = ids_dev; r.bias = bias_dev; r.step_ptr = step_ptr; r.n = s.n; r.min_new = s.min_new; r.step = step;
+    for (int k = 0; k < CONS_MAX_EOS; ++k) r.eos[k] = -1;
+    if (s.n_eos > 0) { r.n_eos = s.n_eos; for (int k = 0; k < s.n_eos; ++k) r.eos[k] = s.eos[k]; }
+    else if (eos_id >= 0 && eos_id < V) { r.n_eos = 1; r.eos[0] = eos_id; }
+    else r.n_eos = 0;
+}
+static int cons_reserve(mmd_ctx* c) {
+    if (c->cons_bias_dev) return MMD_OK;
+    int rc = dev_alloc(c, (void**)&c->cons_rows_dev, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)); if (rc) return rc;
+    HIPCHK(c, hipHostMalloc((void**)&c->cons_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)));
+    rc = dev_alloc(c, (void**)&c->cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t)); if (rc) return rc;
+    return dev_alloc(c, (void**)&c->cons_bias_dev, CONS_MAX_TABLE * sizeof(float));
+}
+// the table of a set into its device buffers: the stream is drained first (a step in flight may read the old values), then the copy is synchronous -- no staging of
+// pageable memory behind the caller's back
+static int cons_upload_table(mmd_ctx* c, const ConsSet& s, int32_t* ids_dev, float* bias_dev) {
+    if (s.n <= 0) return MMD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(ids_dev, s.ids, sizeof(int32_t) * s.n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(bias_dev, s.bias, sizeof(float) * s.n, hipMemcpyHostToDevice));
+    return MMD_OK;
+}
 
 // one draw's parameters; SampleCall: which of the chain's filter kernels a launch over such rows needs
 struct SampleArgs { float temperature; int top_k; float top_p; uint64_t seed; uint64_t* offset_inout; };
@@ -1615,13 +1685,15 @@ extern "C" void mmd_sampler_destroy(mmd_sampler* sp) {
     hipStreamSynchronize(sp->ctx->stream);
     if (sp->tok_dev) hipFree(sp->tok_dev);
     if (sp->prev_dev) hipFree(sp->prev_dev);
+    if (sp->cons_ids_dev) hipFree(sp->cons_ids_dev);
+    if (sp->cons_bias_dev) hipFree(sp->cons_bias_dev);
     delete sp;
 }
 extern "C" int mmd_sampler_begin(mmd_sampler* sp, int64_t eos_id, float rep_penalty, const int64_t* prev_ids_host, int n_prev, int max_new) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
     if (n_prev < 0 || max_new < 0 || (n_prev > 0 && !prev_ids_host)) FAIL(c, MMD_EINVAL, "bad sampler arguments");
-    sp->eos = eos_id; sp->penalty = rep_penalty > 0.f ? rep_penalty : 0.f; sp->n_prev = 0;
+    sp->eos = eos_id; sp->penalty = rep_penalty > 0.f ? rep_penalty : 0.f; sp->n_prev = 0; sp->step = 0;
     if (sp->penalty <= 0.f) return MMD_OK;
     const int need = n_prev + max_new + 1;          // (the slot behind the list receives every drawn token; it counts only when the token is not EOS)
     if (need > sp->prev_cap) {
@@ -1647,6 +1719,22 @@ extern "C" int mmd_sampler_set_sampling(mmd_sampler* sp, float temperature, int 
     sp->sampling = true; sp->temperature = temperature; sp->top_k = top_k; sp->top_p = top_p;
     return MMD_OK;
 }
+extern "C" int mmd_sampler_set_constraints(mmd_sampler* sp, const int64_t* eos_ids_host, int n_eos, int min_new, const int32_t* ids_host, const float* bias_host, int n) {
+    if (!sp) return MMD_EINVAL;
+    mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
+    ConsSet s; int rc = cons_validate(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
+    if (s.on) {
+        if (c->cfg.vocab_size > (1 << 18)) FAIL(c, MMD_ERANGE, "constraints handle vocabularies up to 2^18 entries");
+        rc = cons_reserve(c); if (rc) return rc;
+        if (!sp->cons_bias_dev) {
+            if (hipMalloc((void**)&sp->cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&sp->cons_bias_dev, CONS_MAX_TABLE * sizeof(float)) != hipSuccess)
+                FAIL(c, MMD_ENOMEM, "hipMalloc of a sampler's constraint table failed");
+        }
+        rc = cons_upload_table(c, s, sp->cons_ids_dev, sp->cons_bias_dev); if (rc) return rc;
+    }
+    sp->cons = s;
+    return MMD_OK;
+}
 extern "C" int mmd_sampler_lane(const mmd_sampler* sp) { return sp ? (int)sp->lane : MMD_EINVAL; }
 extern "C" int64_t mmd_sampler_offset(const mmd_sampler* sp) { return sp ? (int64_t)sp->offset : MMD_EINVAL; }
 
@@ -1664,23 +1752,34 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
     FeedBatch feed; int n_feed = 0;
     // sampling rows: the arg-max ones first, the ones whose sampler has sampling on behind them (two passes over the segments), so each kind is one block of logits rows
     SampleBatch sb; int n_sample = 0; int32_t sample_row[MMD_ROUND_MAX_SAMPLERS]; int sample_seg[MMD_ROUND_MAX_SAMPLERS];
-    int n_greedy = 0; bool any_k = false, any_p = false;
-    for (int pass = 0; pass < 2; ++pass)
+    // with constraints (mmd_sampler_set_constraints) three blocks: plain arg-max | constrained arg-max | sampled.  The last two have row descriptors (and constraint
+    // descriptors, empty for an unconstrained sampled row) in slots 1.. of the context's arrays, in the order of their logits rows
+    int n_plain = 0, n_greedy = 0; bool any_k = false, any_p = false, any_cons_sampled = false; uint64_t no_offset = 0;
+    for (int pass = 0; pass < 3; ++pass)
     for (int j = 0; j < n_segs; ++j) {
         const int fl = seg_flags ? seg_flags[j] : 0;
         mmd_sampler* sp = samplers ? samplers[j] : nullptr;
         if ((fl & (MMD_SEG_FEED | MMD_SEG_SAMPLE)) && (!sp || sp->ctx != c)) FAIL(c, MMD_EINVAL, "segment %d feeds / samples without a sampler of this context", j);
-        if (pass == 1) {
-            if (!(fl & MMD_SEG_SAMPLE) || !sp->sampling) continue;
+        if (pass == 0 && n_greedy < n_plain) n_greedy = n_plain;
+        if (pass > 0) {
+            if (!(fl & MMD_SEG_SAMPLE)) continue;
+            if (pass == 1 ? (sp->sampling || !sp->cons.on) : !sp->sampling) continue;
             if (n_sample >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d sampling segments", MMD_ROUND_MAX_SAMPLERS);
             for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
-            if (n_sample == n_greedy) { rc = sample_reserve(c); if (rc) return rc; }
+            if (n_sample == n_plain) { rc = sample_reserve(c); if (rc) return rc; }
+            if (sp->cons.on) { rc = cons_reserve(c); if (rc) return rc; }
             const bool pen = sp->penalty > 0.f;
-            const SampleArgs a{sp->temperature, sp->top_k, sp->top_p, sp->seed, &sp->offset};
-            fill_sample_row(c->samp_rows_host[1 + n_sample - n_greedy], a, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr, sp->tok_dev,
-                            (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr, sp->lane, 0);
-            any_k |= sample_call(a, V).any_k; any_p |= sample_call(a, V).any_p;
+            const SampleArgs a = pass == 1 ? SampleArgs{1.f, 0, 1.f, 0, &no_offset} : SampleArgs{sp->temperature, sp->top_k, sp->top_p, sp->seed, &sp->offset};
+            const int slot = 1 + n_sample - n_plain;
+            fill_sample_row(c->samp_rows_host[slot], a, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr, sp->tok_dev,
+                            (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr, pass == 1 ? 0 : sp->lane, 0);
+            if (c->cons_rows_host) {
+                if (sp->cons.on) cons_fill_row(c->cons_rows_host[slot], sp->cons, sp->cons_ids_dev, sp->cons_bias_dev, sp->eos, V, sp->step, nullptr);
+                else c->cons_rows_host[slot] = ConstraintRow{};
+            }
+            if (pass == 2) { any_k |= sample_call(a, V).any_k; any_p |= sample_call(a, V).any_p; any_cons_sampled |= sp->cons.on; }
             sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample;
+            if (pass == 1) n_greedy = n_sample;
             continue;
         }
         if (fl & MMD_SEG_FEED) {
@@ -1692,13 +1791,13 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             void* dst = (char*)c->l_h + (size_t)segs[j].row0 * H * e;
             if (seg_embeds[j] != dst) HIPCHK(c, hipMemcpyAsync(dst, seg_embeds[j], (size_t)segs[j].rows * H * e, hipMemcpyDeviceToDevice, st));
         }
-        if ((fl & MMD_SEG_SAMPLE) && !sp->sampling) {
+        if ((fl & MMD_SEG_SAMPLE) && !sp->sampling && !sp->cons.on) {
             if (n_sample >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d sampling segments", MMD_ROUND_MAX_SAMPLERS);
             for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
             const bool pen = sp->penalty > 0.f;
             sb.prev[n_sample] = sp->prev_dev; sb.n_prev[n_sample] = pen ? sp->n_prev : 0; sb.penalty[n_sample] = pen ? sp->penalty : 1.f;
             sb.tok[n_sample] = sp->tok_dev; sb.append[n_sample] = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
-            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample; n_greedy = n_sample;
+            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample; n_plain = n_greedy = n_sample;
         }
     }
     if (n_sample && !tokens_out_host) FAIL(c, MMD_EINVAL, "sampling segments need tokens_out_host");
@@ -1723,13 +1822,18 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             rows = c->round_hidden;
         }
         rc = gemm(c, rows, H, c->lm_head, H, nullptr, nullptr, 0, c->round_logits, V, n_sample, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-        if (n_greedy) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_sample_batch(c->round_logits, V, sb, n_greedy, c->round_toks_dev, c->round_scratch, st)); }
-        if (n_sample > n_greedy) {
-            const int ns = n_sample - n_greedy;
-            HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev + 1, c->samp_rows_host + 1, sizeof(SampleRow) * ns, hipMemcpyHostToDevice, st));          // (the round's synchronisation frees the staging)
+        if (n_plain) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_sample_batch(c->round_logits, V, sb, n_plain, c->round_toks_dev, c->round_scratch, st)); }
+        if (n_sample > n_plain) {
+            const int nd = n_sample - n_plain, nc = n_greedy - n_plain, ns = n_sample - n_greedy;
+            HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev + 1, c->samp_rows_host + 1, sizeof(SampleRow) * nd, hipMemcpyHostToDevice, st));          // (the round's synchronisation frees the staging)
+            if (nc || any_cons_sampled) HIPCHK(c, hipMemcpyAsync(c->cons_rows_dev + 1, c->cons_rows_host + 1, sizeof(ConstraintRow) * nd, hipMemcpyHostToDevice, st));
             ProfScope ps(c, MMD_K_OTHER, 0, 0);
-            HIPCHK(c, launch_sample_batch_topkp(c->round_logits + (size_t)n_greedy * V, V, ns, c->samp_rows_dev + 1, any_k, any_p, nullptr, c->round_toks_dev + n_greedy, nullptr, nullptr,
-                                                c->samp_scratch, st));
+            if (nc) {          // constrained arg-max: the chain's scores with nothing filtered, then the first maximal index of z.  (The sampled rows below reuse the scratch: same stream.)
+                HIPCHK(c, launch_sample_scores_unfiltered(c->round_logits + (size_t)n_plain * V, V, nc, c->samp_rows_dev + 1, nullptr, c->samp_scratch, st, c->cons_rows_dev + 1));
+                HIPCHK(c, launch_argmax_scores(V, nc, c->samp_rows_dev + 1, nullptr, c->samp_scratch, c->round_toks_dev + n_plain, st));
+            }
+            if (ns) HIPCHK(c, launch_sample_batch_topkp(c->round_logits + (size_t)n_greedy * V, V, ns, c->samp_rows_dev + 1 + nc, any_k, any_p, nullptr, c->round_toks_dev + n_greedy, nullptr, nullptr,
+                                                        c->samp_scratch, st, nullptr, any_cons_sampled ? c->cons_rows_dev + 1 + nc : nullptr));
         }
         HIPCHK(c, hipMemcpyAsync(c->round_toks_host, c->round_toks_dev, sizeof(int64_t) * n_sample, hipMemcpyDeviceToHost, st));
     }
@@ -1741,8 +1845,11 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         const int64_t tok = c->round_toks_host[i];
         mmd_sampler* sp = samplers[sample_seg[i]];
         tokens_out_host[sample_seg[i]] = tok;
-        if (i >= n_greedy) { sp->offset += 1; if (tok < 0) FAIL(c, MMD_EDOM, "NaN in the logits of segment %d: no token drawn", sample_seg[i]); }
-        if (sp->penalty > 0.f && tok != sp->eos && sp->n_prev < sp->prev_cap) sp->n_prev += 1;          // (EOS is neither fed back nor penalised: models/modeling_live.py:66-72)
+        if (i >= n_greedy) sp->offset += 1;
+        if (i >= n_plain && tok < 0) FAIL(c, MMD_EDOM, "segment %d: a NaN among the logits, or every score is -inf: no token drawn", sample_seg[i]);
+        sp->step += 1;
+        const bool is_eos = (sp->cons.on && sp->cons.n_eos > 0) ? std::find(sp->cons.eos, sp->cons.eos + sp->cons.n_eos, tok) != sp->cons.eos + sp->cons.n_eos : tok == sp->eos;
+        if (sp->penalty > 0.f && !is_eos && sp->n_prev < sp->prev_cap) sp->n_prev += 1;          // (EOS is neither fed back nor penalised: models/modeling_live.py:66-72)
     }
     return MMD_OK;
 }
@@ -1849,45 +1956,61 @@ static int greedy_logprobs_enqueue(mmd_ctx* c, const LogprobOut& lp) {
     return MMD_OK;
 }
 
+// the constrained arg-max over logits_ws: the chain's scores for row descriptor 0 under constraint descriptor 0 (T = 1, no filter), the first maximal index of them into
+// tok_dev, and -- recording on -- the record from the same scores
+static int constrained_argmax_enqueue(mmd_ctx* c, const ConstraintRow* cons, const LogprobOut* lp) {
+    const int V = c->cfg.vocab_size; hipStream_t st = c->stream;
+    HIPCHK(c, launch_sample_scores_unfiltered(c->logits_ws, V, 1, c->samp_rows_dev, nullptr, c->samp_scratch, st, cons));
+    HIPCHK(c, launch_argmax_scores(V, 1, c->samp_rows_dev, nullptr, c->samp_scratch, c->tok_dev, st));
+    if (lp) HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, *lp, true, nullptr, c->samp_scratch, c->lp_scratch, st));
+    return MMD_OK;
+}
+
 // one decode step (feed the previously drawn token, draw the next) enqueued on the stream; `dyn` selects the
 // graph-capturable form that reads position / arena / penalty-list length from device state
 // `samp`: the sampling chain over row descriptor 0 takes the arg-max's place; its penalty list always grows on the device
 // `lp`: the step records its token's log-probabilities (the kernels stand between the choice of the token and the state's advance)
+// `cons`: constraint descriptor 0 on the device (DESIGN.md "Constraints"): the chain's scores take it; the arg-max becomes the first maximal index of those scores (row
+// descriptor 0 is then posted for every arg-max step, as for the log-probabilities); the state's advance tests the EOS set
 static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const SampleCall* samp = nullptr,
-                               const LogprobOut* lp = nullptr) {
+                               const LogprobOut* lp = nullptr, const ConstraintRow* cons = nullptr) {
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size;
     // the next token's embedding is gathered straight into the residual-stream buffer (llm_step_segs skips its copy when embeds == l_h)
     HIPCHK(c, launch_embed(g.dtype, c->embed, c->tok_dev, 1, H, g.vocab_size, c->l_h, st));
     int rc = llm_step_impl(c, s, c->l_h, 1, nullptr, dyn); if (rc) return rc;
     rc = gemm(c, c->l_hid, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, g.vocab_size, 1, g.vocab_size, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
     if (samp) {
-        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, g.vocab_size, 1, c->samp_rows_dev, samp->any_k, samp->any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lp));
+        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, g.vocab_size, 1, c->samp_rows_dev, samp->any_k, samp->any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lp, cons));
         if (lp) HIPCHK(c, launch_logprob_rows(c->logits_ws, g.vocab_size, 1, *lp, false, nullptr, c->samp_scratch, c->lp_scratch, st));
-        HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st));
+        HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st, cons));
         return MMD_OK;
     }
-    HIPCHK(c, launch_argmax_penalty(c->logits_ws, g.vocab_size, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, dyn, c->argmax_scratch));
-    if (lp) { rc = greedy_logprobs_enqueue(c, *lp); if (rc) return rc; }
-    if (dyn) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st));
+    if (cons) { rc = constrained_argmax_enqueue(c, cons, lp); if (rc) return rc; }
+    else {
+        HIPCHK(c, launch_argmax_penalty(c->logits_ws, g.vocab_size, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, dyn, c->argmax_scratch));
+        if (lp) { rc = greedy_logprobs_enqueue(c, *lp); if (rc) return rc; }
+    }
+    if (dyn) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st, cons));
     return MMD_OK;
 }
 
 // captures one dynamic decode step into dg for the key (key_pen, eos_id, sel).  Capture runs on the context's own stream (the legacy null stream -- torch's default --
 // cannot be captured); the instantiated graph is then launched on whatever stream the caller bound
-static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, bool pen, float rep_penalty, int np, int64_t eos_id, const SampleCall* samp, float key_pen, int sel, const LogprobOut* lp) {
+static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, bool pen, float rep_penalty, int np, int64_t eos_id, const SampleCall* samp, float key_pen, int sel, const LogprobOut* lp,
+                               const ConstraintRow* cons, uint32_t cons_gen) {
     hipStream_t st = c->stream;
     dg.drop();
     HIPCHK(c, hipStreamSynchronize(st));
     c->stream = c->own_stream;
     hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
     if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
-    int rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, samp, lp);
+    int rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, samp, lp, cons);
     hipError_t ce = hipStreamEndCapture(c->own_stream, &dg.src);
     c->stream = st;
     if (rc) { dg.drop(); return rc; }
     HIPCHK(c, ce);
     HIPCHK(c, hipGraphInstantiate(&dg.exec, dg.src, nullptr, nullptr, 0));
-    dg.pen = key_pen; dg.eos = eos_id; dg.sel = sel; dg.lp = lp ? lp->top_n : -1;
+    dg.pen = key_pen; dg.eos = eos_id; dg.sel = sel; dg.lp = lp ? lp->top_n : -1; dg.cons = cons_gen;
     return MMD_OK;
 }
 
@@ -1942,7 +2065,21 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     const bool pen = rep_penalty > 0.f;
     int np = (pen && n_prev) ? *n_prev : 0;
     if (pen) { rc = penalty_reserve(c, np + max_new); if (rc) return rc; }
-    if (samp || lp_on) { rc = sample_reserve(c); if (rc) return rc; }
+    const bool cons_on = c->cons.on;
+    if (cons_on && V > (1 << 18)) FAIL(c, MMD_ERANGE, "constraints handle vocabularies up to 2^18 entries");
+    if (samp || lp_on || cons_on) { rc = sample_reserve(c); if (rc) return rc; }
+    // constraints on: descriptor 0 on the device carries the EOS set (the call's own eos_id when the set is empty), min_new and the table; the captured step reads the response
+    // step through &step_dev->step, an eager arg-max step gets it posted.  EOS below is membership of that set.
+    ConstraintRow crow{};
+    if (cons_on) cons_fill_row(crow, c->cons, c->cons_ids_dev, c->cons_bias_dev, eos_id, V, 0, nullptr);
+    const ConstraintRow* consp = cons_on ? c->cons_rows_dev : nullptr;
+    auto post_cons = [&](bool dynamic, int step) -> int {
+        crow.step = step; crow.step_ptr = dynamic ? &c->step_dev->step : nullptr;
+        c->cons_rows_host[0] = crow;
+        HIPCHK(c, hipMemcpyAsync(c->cons_rows_dev, c->cons_rows_host, sizeof(ConstraintRow), hipMemcpyHostToDevice, st));
+        return MMD_OK;
+    };
+    auto is_eos = [&](int64_t t) -> bool { return cons_on ? cons_is_eos(crow, t) : t == eos_id; };
     if (lp_on) {
         if (V > (1 << 18)) FAIL(c, MMD_ERANGE, "log-probabilities handle vocabularies up to 2^18 entries");
         rc = logprob_reserve(c, max_new); if (rc) return rc;
@@ -1971,7 +2108,8 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         *tok = c->tok_host[0];
-        if (samp) { ++*samp->offset_inout; if (*tok < 0) FAIL(c, MMD_EDOM, "NaN in the logits: no token drawn"); }
+        if (samp) ++*samp->offset_inout;
+        if ((samp || cons_on) && *tok < 0) FAIL(c, MMD_EDOM, cons_on ? "NaN in the logits, or every score is -inf under the constraints: no token drawn" : "NaN in the logits: no token drawn");
         return MMD_OK;
     };
     // step 0: the prompt (eager)
@@ -1980,19 +2118,21 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         const void* last = (const char*)c->l_hid + (size_t)(S - 1) * H * e;
         rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, V, 1, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
         if (samp) { rc = post_row(false); if (rc) return rc; }
-        else if (lp_on) { rc = post_lp_row(false); if (rc) return rc; }
+        else if (lp_on || cons_on) { rc = post_lp_row(false); if (rc) return rc; }
+        if (cons_on) { rc = post_cons(false, 0); if (rc) return rc; }
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
         if (samp) {
-            HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lpp));
+            HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lpp, consp));
             if (lp_on) HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, lpo, false, nullptr, c->samp_scratch, c->lp_scratch, st));
         }
+        else if (cons_on) { rc = constrained_argmax_enqueue(c, consp, lpp); if (rc) return rc; }
         else HIPCHK(c, launch_argmax_penalty(c->logits_ws, V, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, nullptr, c->argmax_scratch));
-        if (lp_on && !samp) { rc = greedy_logprobs_enqueue(c, lpo); if (rc) return rc; }
+        if (lp_on && !samp && !cons_on) { rc = greedy_logprobs_enqueue(c, lpo); if (rc) return rc; }
     }
     int64_t tok = 0;
     rc = read_token(&tok); if (rc) return rc;
     out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
-    const bool stop = tok == eos_id;
+    const bool stop = is_eos(tok);
     if (!stop && pen) {
         if (np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
@@ -2011,7 +2151,8 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
     }
     if (samp && more) { rc = post_row(true); if (rc) return rc; }
-    if (lp_on && !samp && can_graph) { rc = post_lp_row(true); if (rc) return rc; }
+    if ((lp_on || cons_on) && !samp && can_graph) { rc = post_lp_row(true); if (rc) return rc; }
+    if (cons_on && (can_graph || (samp && more))) { rc = post_cons(true, 1); if (rc) return rc; }
     if (can_graph) lpo.dyn = c->step_dev;
     DecodeGraph& dg = samp ? c->dec_sampled : c->dec_greedy;
     if (can_graph) {
@@ -2019,21 +2160,23 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         const float key_pen = pen ? (samp ? 1.f : rep_penalty) : 0.f;
         const int sel = (call.any_k ? 1 : 0) | (call.any_p ? 2 : 0);
         c->dec_route = 1;
-        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != sel || dg.lp != lp_top) {
-            rc = capture_decode_step(c, s, dg, pen, rep_penalty, np, eos_id, callp, key_pen, sel, lpp); if (rc) { c->dec_route = 0; return rc; }
+        const uint32_t cons_gen = cons_on ? c->cons_gen : 0;
+        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != sel || dg.lp != lp_top || dg.cons != cons_gen) {
+            rc = capture_decode_step(c, s, dg, pen, rep_penalty, np, eos_id, callp, key_pen, sel, lpp, consp, cons_gen); if (rc) { c->dec_route = 0; return rc; }
             c->dec_route = 2;
         }
     }
     for (int i = 1; i < max_new && !stop; ++i) {
         if (can_graph) { HIPCHK(c, hipGraphLaunch(dg.exec, st)); s->len += 1; }
         else {
-            if (lp_on && !samp) { rc = post_lp_row(false); if (rc) return rc; }
+            if ((lp_on || cons_on) && !samp) { rc = post_lp_row(false); if (rc) return rc; }
+            if (cons_on && !samp) { rc = post_cons(false, i); if (rc) return rc; }
             lpo.idx0 = i;
-            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, callp, lpp); if (rc) return rc;
+            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, callp, lpp, consp); if (rc) return rc;
         }
         rc = read_token(&tok); if (rc) return rc;
         out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
-        if (tok == eos_id) break;
+        if (is_eos(tok)) break;
         if (pen) {          // (arg-max, eager: the list grows by a copy here; every other route grows it in advance_state_kernel)
             if (!samp && !can_graph && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
             if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
@@ -2059,6 +2202,18 @@ extern "C" int mmd_sample_generate(mmd_ctx* c, mmd_stream* s, const void* prompt
     if (!n_out || max_new < 0 || (max_new > 0 && !out_ids_host) || !offset_inout) FAIL(c, MMD_EINVAL, "bad generate arguments");
     const SampleArgs samp{temperature, top_k, top_p, seed, offset_inout};
     return generate_impl(c, s, prompt_embeds, S, eos_id, rep_penalty, prev_ids_host, n_prev, prev_cap, out_ids_host, max_new, n_out, &samp);
+}
+
+extern "C" int mmd_set_generate_constraints(mmd_ctx* c, const int64_t* eos_ids_host, int n_eos, int min_new, const int32_t* ids_host, const float* bias_host, int n) {
+    NEED_FINAL(c);
+    ConsSet s; int rc = cons_validate(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
+    if (s.on) {
+        rc = cons_reserve(c); if (rc) return rc;
+        rc = cons_upload_table(c, s, c->cons_ids_dev, c->cons_bias_dev); if (rc) return rc;
+    }
+    c->cons_gen = s.on ? 1 : 0;          // on <-> off: another captured step.  Everything else about a set -- EOS ids, min_new, the table -- is read from descriptor 0 on the device
+    c->cons = s;
+    return MMD_OK;
 }
 
 extern "C" int mmd_set_generate_logprobs(mmd_ctx* c, int top_n) {
@@ -2166,6 +2321,92 @@ extern "C" int mmd_op_sample_logprobs(mmd_ctx* c, const float* logits, int n, in
     if (!lp_out_host || (top_n > 0 && (!top_ids_out_host || !top_lp_out_host))) FAIL(c, MMD_EINVAL, "bad mmd_op_sample_logprobs arguments");
     return op_sample_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, greedy != 0, top_n,
                           lp_out_host, top_ids_out_host, top_lp_out_host);
+}
+
+// raw operator of the constrained chain: mmd_op_sample_logprobs with one constraint set per row.  Row i's table is entries [tab_off[i], tab_off[i + 1]) of tab_ids / tab_bias;
+// every set goes through cons_validate (the limits of mmd_set_generate_constraints).  greedy: the constrained arg-max (scores with nothing filtered, first maximal index).
+extern "C" int mmd_op_sample_constrained(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                                         uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n,
+                                         const int32_t* tab_off_host, const int32_t* tab_ids_host, const float* tab_bias_host, const int64_t* eos_host, const int32_t* n_eos_host,
+                                         const int32_t* min_new_host, const int32_t* step_host,
+                                         int64_t* tokens_out, float* info_out, float* scores_out, float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host) {
+    if (!c) return MMD_EINVAL;
+    hipSetDevice(c->device);
+    if (greedy) { temperature = 1.f; top_k = 0; top_p = 1.f; }
+    if (!logits || !tokens_out || (!info_out && !greedy) || n < 1 || n > 4096 || V < 1 || V > (1 << 18) || n_prev < 0 || (n_prev > 0 && !prev_ids_dev) || !tab_off_host || !n_eos_host ||
+        !min_new_host || !step_host)
+        FAIL(c, MMD_EINVAL, "bad mmd_op_sample_constrained arguments");
+    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1");
+    if (lp_out_host && (top_n < 0 || top_n > LP_MAX_TOP)) FAIL(c, MMD_ERANGE, "top_n 0..%d, got %d", LP_MAX_TOP, top_n);
+    if (lp_out_host && top_n > 0 && (!top_ids_out_host || !top_lp_out_host)) FAIL(c, MMD_EINVAL, "bad mmd_op_sample_constrained arguments");
+    if (tab_off_host[0] != 0) FAIL(c, MMD_EINVAL, "table offsets start at 0");
+    std::vector<ConsSet> sets((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int o = tab_off_host[i], m = tab_off_host[i + 1] - o;
+        if (m < 0 || step_host[i] < 0) FAIL(c, MMD_EINVAL, "row %d: bad table offsets or step", i);
+        int rc = cons_validate(c, V, eos_host ? eos_host + (size_t)i * CONS_MAX_EOS : nullptr, n_eos_host[i], min_new_host[i], tab_ids_host ? tab_ids_host + o : nullptr,
+                               tab_bias_host ? tab_bias_host + o : nullptr, m, sets[i]);
+        if (rc) return rc;
+    }
+    hipStream_t st = c->stream;
+    const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS, total = tab_off_host[n];
+    SampleRow* rows_dev = nullptr; ConstraintRow* cons_dev = nullptr; int32_t* ids_dev = nullptr; float* bias_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
+    LogprobRec* rec_dev = nullptr; void* lp_scratch = nullptr;
+    auto release = [&]() {
+        hipStreamSynchronize(st);
+        if (rows_dev) hipFree(rows_dev); if (cons_dev) hipFree(cons_dev); if (ids_dev) hipFree(ids_dev); if (bias_dev) hipFree(bias_dev); if (r_dev) hipFree(r_dev);
+        if (scratch) hipFree(scratch); if (rec_dev) hipFree(rec_dev); if (lp_scratch) hipFree(lp_scratch);
+    };
+#define OPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { release(); FAIL(c, MMD_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
+    OPCHK(hipMalloc((void**)&rows_dev, sizeof(SampleRow) * n));
+    OPCHK(hipMalloc((void**)&cons_dev, sizeof(ConstraintRow) * n));
+    OPCHK(hipMalloc((void**)&ids_dev, sizeof(int32_t) * (total > 0 ? total : 1)));
+    OPCHK(hipMalloc((void**)&bias_dev, sizeof(float) * (total > 0 ? total : 1)));
+    OPCHK(hipMalloc(&scratch, sample_topkp_scratch_bytes(V, chunk, scores_out == nullptr)));
+    std::vector<SampleRow> rows((size_t)n); std::vector<ConstraintRow> crows((size_t)n); std::vector<int32_t> ids((size_t)(total > 0 ? total : 1)); std::vector<float> bias(ids.size());
+    const SampleArgs a{temperature, top_k, top_p, seed, &offset};
+    for (int i = 0; i < n; ++i) {
+        fill_sample_row(rows[i], a, prev_ids_dev, rep_penalty > 0.f && n_prev > 0, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
+        const int o = tab_off_host[i];
+        for (int k = 0; k < sets[i].n; ++k) { ids[o + k] = sets[i].ids[k]; bias[o + k] = sets[i].bias[k]; }          // (sorted by cons_validate)
+        cons_fill_row(crows[i], sets[i], ids_dev + o, bias_dev + o, -1, V, step_host[i], nullptr);
+    }
+    // (synchronous copies: the vectors above are pageable)
+    OPCHK(hipMemcpy(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice));
+    OPCHK(hipMemcpy(cons_dev, crows.data(), sizeof(ConstraintRow) * n, hipMemcpyHostToDevice));
+    OPCHK(hipMemcpy(ids_dev, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
+    OPCHK(hipMemcpy(bias_dev, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice));
+    if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpy(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice)); }
+    if (lp_out_host) { OPCHK(hipMalloc((void**)&rec_dev, sizeof(LogprobRec) * n)); OPCHK(hipMalloc(&lp_scratch, logprob_scratch_bytes(chunk))); }
+    const SampleCall call = sample_call(a, V);
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = n - i0 < chunk ? n - i0 : chunk;
+        ProfScope ps(c, MMD_K_OTHER, 0, 0);
+        const float* lg = logits + (size_t)i0 * V; float* sc = scores_out ? scores_out + (size_t)i0 * V : nullptr;
+        const LogprobOut lpo{rec_dev, n, nullptr, i0, tokens_out + i0, top_n};
+        if (greedy) {
+            OPCHK(launch_sample_scores_unfiltered(lg, V, m, rows_dev + i0, sc, scratch, st, cons_dev + i0));
+            OPCHK(launch_argmax_scores(V, m, rows_dev + i0, sc, scratch, tokens_out + i0, st));
+        } else {
+            OPCHK(launch_sample_batch_topkp(lg, V, m, rows_dev + i0, call.any_k, call.any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4, sc, scratch, st,
+                                            lp_out_host ? &lpo : nullptr, cons_dev + i0));
+        }
+        if (lp_out_host) OPCHK(launch_logprob_rows(lg, V, m, lpo, greedy != 0, sc, scratch, lp_scratch, st));
+    }
+    OPCHK(hipStreamSynchronize(st));
+    std::vector<int64_t> toks((size_t)n);
+    OPCHK(hipMemcpy(toks.data(), tokens_out, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    if (lp_out_host) {
+        std::vector<LogprobRec> h((size_t)n);
+        OPCHK(hipMemcpy(h.data(), rec_dev, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost));
+        std::vector<float> l1((size_t)n), l2((size_t)n);
+        unpack_logprobs(h.data(), n, top_n, l1.data(), l2.data(), top_ids_out_host, top_lp_out_host);
+        for (int i = 0; i < n; ++i) { lp_out_host[2 * i] = l1[i]; lp_out_host[2 * i + 1] = l2[i]; }
+    }
+#undef OPCHK
+    release();
+    for (int i = 0; i < n; ++i) if (toks[i] < 0) FAIL(c, MMD_EDOM, "row %d: a NaN among the logits, or every score is -inf under the constraints: no token drawn", i);
+    return MMD_OK;
 }
 
 // ---- measurement -------------------------------------------------------------------------------------------------------

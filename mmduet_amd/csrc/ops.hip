@@ -932,14 +932,16 @@ hipError_t launch_embed_feed(int dtype, const void* table, const FeedBatch& f, i
 }
 
 // last node of the captured decode step: append the sampled token to the penalty list (unless EOS), advance the position and the step index
-__global__ void advance_state_kernel(StepState* st, const int64_t* __restrict__ tok, int64_t* __restrict__ prev, int prev_cap, long long eos, int use_penalty) {
+__global__ void advance_state_kernel(StepState* st, const int64_t* __restrict__ tok, int64_t* __restrict__ prev, int prev_cap, long long eos, int use_penalty,
+                                     const ConstraintRow* __restrict__ cons) {
     if (threadIdx.x != 0) return;
     const long long t = *tok;
-    if (use_penalty && t != eos && st->n_prev < prev_cap) { prev[st->n_prev] = t; st->n_prev += 1; }
+    const bool is_eos = cons ? cons_is_eos(*cons, t) : t == eos;          // constraints on: membership of the EOS set in the context's descriptor
+    if (use_penalty && !is_eos && st->n_prev < prev_cap) { prev[st->n_prev] = t; st->n_prev += 1; }
     st->n_ctx += 1; st->step += 1;
 }
-hipError_t launch_advance_state(StepState* st_dev, const int64_t* tok_dev, int64_t* prev_dev, int prev_cap, int64_t eos, int use_penalty, hipStream_t st) {
-    hipLaunchKernelGGL(advance_state_kernel, dim3(1), dim3(64), 0, st, st_dev, tok_dev, prev_dev, prev_cap, (long long)eos, use_penalty);
+hipError_t launch_advance_state(StepState* st_dev, const int64_t* tok_dev, int64_t* prev_dev, int prev_cap, int64_t eos, int use_penalty, hipStream_t st, const ConstraintRow* cons_dev) {
+    hipLaunchKernelGGL(advance_state_kernel, dim3(1), dim3(64), 0, st, st_dev, tok_dev, prev_dev, prev_cap, (long long)eos, use_penalty, cons_dev);
     return hipGetLastError();
 }
 

@@ -76,16 +76,23 @@ __device__ __forceinline__ void slice_of(int V, int blk, int nblk, int* beg, int
     const int per = (V + nblk - 1) / nblk;
     *beg = min(V, blk * per); *end = min(V, *beg + per);
 }
-// row maximum and NaN flag from the per-slice partials (every block folds the <= 64 partials itself)
+// row maximum and NaN flag from the per-slice partials (every block folds the <= 64 partials itself).  Flag bit 0: a NaN in the slice.  Bit 1, written for constrained rows
+// only: no score of the slice is above -inf -- set in EVERY slice, nothing is left to draw from, and the row is treated like a NaN row (no token, MMD_EDOM).
 __device__ __forceinline__ float row_max(const SampleWs& w, int r, int nblk, bool* nan) {
-    uint32_t mk = 0, nn = 0;
-    for (int b = 0; b < nblk; ++b) { mk = max(mk, w.part_max[r * SMP_MAX_SLICES + b]); nn |= w.part_nan[r * SMP_MAX_SLICES + b]; }
-    *nan = nn != 0;
+    uint32_t mk = 0, nn = 0, empty = 2u;
+    for (int b = 0; b < nblk; ++b) { const uint32_t f = w.part_nan[r * SMP_MAX_SLICES + b]; mk = max(mk, w.part_max[r * SMP_MAX_SLICES + b]); nn |= f & 1u; empty &= f; }
+    *nan = (nn | empty) != 0;
     return key2f(mk);
 }
 
-__global__ __launch_bounds__(256) void sample_scores_kernel(const float* __restrict__ logits, int V, const SampleRow* __restrict__ rows, SampleWs w) {
+// CONS (DESIGN.md "Constraints"): the row's (id, bias) table, sorted by id, is staged in LDS; inside the block's slice the kernel writes, each pass behind a barrier,
+//   (l + b) / T for the biased ids  ->  pen(l + b) / T for the ids on the penalty list (b looked up in LDS, 0 when absent: every duplicate writes the same value)  ->
+//   -inf for the suppressed ids and, while fewer than min_new tokens have been returned, for the EOS ids.
+// Only the block that owns a column writes it.  Without CONS the kernel is the code it was.
+template <bool CONS>
+__global__ __launch_bounds__(256) void sample_scores_kernel(const float* __restrict__ logits, int V, const SampleRow* __restrict__ rows, SampleWs w, const ConstraintRow* __restrict__ cons) {
     __shared__ uint32_t s_max[4], s_nan[4];
+    __shared__ int s_id[CONS ? CONS_MAX_TABLE : 1]; __shared__ float s_b[CONS ? CONS_MAX_TABLE : 1];
     const int r = blockIdx.y; const SampleRow row = rows[r];
     const float* lg = logits + (long long)r * V; float* z = w.z + (long long)r * w.ldz;
     int beg, end; slice_of(V, blockIdx.x, gridDim.x, &beg, &end);
@@ -96,15 +103,45 @@ __global__ __launch_bounds__(256) void sample_scores_kernel(const float* __restr
         for (int i = blockIdx.x * 256 + threadIdx.x; i < SMP_HIST_BINS; i += gridDim.x * 256) { hc[i] = 0; hm[i] = 0; }
     }
     const float pen = row.penalty;
+    int nt = 0, n_eos = 0; bool on = false, eos_masked = false;
+    if constexpr (CONS) {
+        nt = min(cons[r].n, CONS_MAX_TABLE); n_eos = min(cons[r].n_eos, CONS_MAX_EOS); on = nt > 0 || n_eos > 0;
+        if (on) {
+            const int step = cons[r].step_ptr ? *cons[r].step_ptr : cons[r].step;
+            eos_masked = step < cons[r].min_new;
+            if ((int)threadIdx.x < nt) { s_id[threadIdx.x] = cons[r].ids[threadIdx.x]; s_b[threadIdx.x] = cons[r].bias[threadIdx.x]; }
+            __syncthreads();
+            if ((int)threadIdx.x < nt) {
+                const int id = s_id[threadIdx.x]; const float b = s_b[threadIdx.x];
+                if (id >= beg && id < end && b != -INFINITY) { float v = (lg[id] + b) / T; if (v == 0.f) v = 0.f; z[id] = v; }
+            }
+        }
+    }
     if (pen > 0.f && pen != 1.f) {
         __syncthreads();
         int np = row.n_prev_ptr ? *row.n_prev_ptr : row.n_prev;
         if (np > row.prev_cap) np = row.prev_cap;
         for (int j = threadIdx.x; j < np; j += 256) {
             const long long id = row.prev[j];
-            if (id >= beg && id < end) { const float l = lg[id]; float v = (l > 0.f ? l / pen : l * pen) / T; if (v == 0.f) v = 0.f; z[id] = v; }          // same value from every duplicate
+            if (id >= beg && id < end) {
+                float l = lg[id];
+                if constexpr (CONS) {          // the bias of this id, if the table holds it (binary search over the sorted ids)
+                    int lo = 0, hi = nt;
+                    while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_id[mid] < (int)id) lo = mid + 1; else hi = mid; }
+                    if (lo < nt && s_id[lo] == (int)id) l = l + s_b[lo];
+                }
+                float v = (l > 0.f ? l / pen : l * pen) / T; if (v == 0.f) v = 0.f; z[id] = v;          // same value from every duplicate
+            }
         }
         __syncthreads();
+    }
+    if constexpr (CONS) {
+        if (on) {
+            __syncthreads();
+            if ((int)threadIdx.x < nt) { const int id = s_id[threadIdx.x]; if (id >= beg && id < end && s_b[threadIdx.x] == -INFINITY) z[id] = -INFINITY; }
+            if (eos_masked && (int)threadIdx.x < n_eos) { const long long id = cons[r].eos[threadIdx.x]; if (id >= beg && id < end) z[id] = -INFINITY; }
+            __syncthreads();
+        }
     }
     uint32_t mk = 0, nn = 0;
     for (int i = beg + threadIdx.x; i < end; i += 256) { const float v = z[i]; if (v != v) nn = 1; else mk = max(mk, f2key(v)); }
@@ -114,6 +151,7 @@ __global__ __launch_bounds__(256) void sample_scores_kernel(const float* __restr
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int k = 1; k < 4; ++k) { mk = max(mk, s_max[k]); nn |= s_nan[k]; }
+        if constexpr (CONS) { if (on && mk <= 0x007fffffu) nn |= 2u; }          // a constrained row's slice without a score above -inf (0x007fffff = f2key(-inf)): row_max folds the bit
         w.part_max[r * SMP_MAX_SLICES + blockIdx.x] = mk; w.part_nan[r * SMP_MAX_SLICES + blockIdx.x] = nn;
     }
 }
@@ -318,13 +356,14 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(int V, int nblk, Sampl
 int sample_topkp_slices(int V) { const int s = cdiv(V, 256); return s < 1 ? 1 : (s > SMP_MAX_SLICES ? SMP_MAX_SLICES : s); }
 
 hipError_t launch_sample_batch_topkp(const float* logits, int V, int n, SampleRow* rows_dev, bool any_k, bool any_p, const unsigned long long* r_words_dev, int64_t* toks_out_dev,
-                                     float* info_out_dev, float* scores_out_dev, void* scratch, hipStream_t st, const LogprobOut* lp) {
+                                     float* info_out_dev, float* scores_out_dev, void* scratch, hipStream_t st, const LogprobOut* lp, const ConstraintRow* cons_dev) {
     if (n <= 0) return hipSuccess;
     if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18)) return hipErrorInvalidValue;
     const SampleWs w = carve(scratch, V, n, scores_out_dev);
     const int nblk = sample_topkp_slices(V);
     const dim3 grid(nblk, n), blk(256);
-    hipLaunchKernelGGL(sample_scores_kernel, grid, blk, 0, st, logits, V, (const SampleRow*)rows_dev, w);
+    if (cons_dev) hipLaunchKernelGGL(sample_scores_kernel<true>, grid, blk, 0, st, logits, V, (const SampleRow*)rows_dev, w, cons_dev);
+    else hipLaunchKernelGGL(sample_scores_kernel<false>, grid, blk, 0, st, logits, V, (const SampleRow*)rows_dev, w, cons_dev);
     if (any_k || any_p) hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 0);
     if (any_k) { hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 1); hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 2); }
     if (any_p) { hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 3); hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, (const SampleRow*)rows_dev, w, 4); }
@@ -469,13 +508,47 @@ __global__ __launch_bounds__(256) void logprob_final_kernel(const float* __restr
     }
 }
 
-hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, const SampleRow* rows_dev, float* scores_out_dev, void* scratch, hipStream_t st) {
+hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, const SampleRow* rows_dev, float* scores_out_dev, void* scratch, hipStream_t st, const ConstraintRow* cons_dev) {
     if (n <= 0) return hipSuccess;
     if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18)) return hipErrorInvalidValue;
     const SampleWs w = carve(scratch, V, n, scores_out_dev);
     const dim3 grid(sample_topkp_slices(V), n), blk(256);
-    hipLaunchKernelGGL(sample_scores_kernel, grid, blk, 0, st, logits, V, rows_dev, w);
+    if (cons_dev) hipLaunchKernelGGL(sample_scores_kernel<true>, grid, blk, 0, st, logits, V, rows_dev, w, cons_dev);
+    else hipLaunchKernelGGL(sample_scores_kernel<false>, grid, blk, 0, st, logits, V, rows_dev, w, cons_dev);
     hipLaunchKernelGGL(sample_select_kernel, grid, blk, 0, st, V, rows_dev, w, 5);
+    return hipGetLastError();
+}
+
+// The constrained arg-max (DESIGN.md "Constraints"): one block per row over the scores and per-slice maxima the two kernels above left.  The first slice whose maximum is the
+// row's holds the first maximal index; the block scans that slice alone.  -1 when the row has a NaN or nothing above -inf.
+__global__ __launch_bounds__(256) void argmax_scores_kernel(int V, int nblk, const SampleRow* __restrict__ rows, SampleWs w, int64_t* __restrict__ toks_out) {
+    __shared__ int s_i[4];
+    const int r = blockIdx.x; const SampleRow row = rows[r];
+    bool nan; const float zmax = row_max(w, r, nblk, &nan);
+    const uint32_t kmax = f2key(zmax);
+    int s = 0;
+    while (s < nblk - 1 && w.part_max[r * SMP_MAX_SLICES + s] != kmax) ++s;
+    int beg, end; slice_of(V, s, nblk, &beg, &end);
+    const float* z = w.z + (long long)r * w.ldz;
+    int bi = 0x7fffffff;
+    for (int i = beg + threadIdx.x; i < end; i += 256) if (f2key(z[i]) == kmax) { bi = i; break; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bi = min(bi, __shfl_xor(bi, o, 64));
+    if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = bi;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) bi = min(bi, s_i[k]);
+        const long long tok = (nan || bi == 0x7fffffff) ? -1 : bi;
+        if (row.tok) *row.tok = tok;
+        if (row.append) *row.append = tok;
+        if (toks_out) toks_out[r] = tok;
+    }
+}
+hipError_t launch_argmax_scores(int V, int n, const SampleRow* rows_dev, float* scores_out_dev, void* scratch, int64_t* toks_out_dev, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18)) return hipErrorInvalidValue;
+    const SampleWs w = carve(scratch, V, n, scores_out_dev);
+    hipLaunchKernelGGL(argmax_scores_kernel, dim3(n), dim3(256), 0, st, V, sample_topkp_slices(V), rows_dev, w, toks_out_dev);
     return hipGetLastError();
 }
 

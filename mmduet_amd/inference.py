@@ -99,6 +99,11 @@ class LiveInferForBenchmark:
         self.top_p = float(getattr(args, 'top_p', 1.0))
         self.sampling_seed = int(getattr(args, 'sampling_seed', 0) or 0)
         # per-token log-probabilities of the responses (off by default; DESIGN.md "Log-probabilities"): response_logprobs grows beside response_token_ids
+        # constrained decoding (DESIGN.md "Constraints"): read with getattr, so the reference's argument schema (arguments_live.py) is untouched.  eos_token_ids None = the
+        # one EOS id of the config (self.eos_token_id below); the set is merged once and handed to the model around every response
+        self.eos_token_ids = getattr(args, 'eos_token_ids', None)
+        self.min_new_tokens = int(getattr(args, 'min_new_tokens', 0) or 0)
+        self.suppress_tokens = list(getattr(args, 'suppress_tokens', None) or ())
         self.output_logprobs = bool(getattr(args, 'output_logprobs', False))
         self.top_logprobs = int(getattr(args, 'top_logprobs', 0) or 0)
         self.frames_per_forward = max(1, int(getattr(args, 'frames_per_forward', 1)))
@@ -385,8 +390,27 @@ class LiveInferForBenchmark:
         self.last_ids = self._no_ids()
         self.last_role = 'user'
 
+    def _response_constraints(self):
+        """The driver's constraint attributes as one merged set (None: nothing beyond the one EOS id is asked for -- the unconstrained loop)."""
+        eos = list(self.eos_token_ids) if self.eos_token_ids else [self.eos_token_id]
+        if len(set(eos)) <= 1 and eos[0] == self.eos_token_id and not self.min_new_tokens and not self.suppress_tokens:
+            return None
+        from . import constraints as _constraints
+        return _constraints.merge(self.model.config.vocab_size, eos, self.min_new_tokens, self.suppress_tokens)
+
     def _native_response(self):
-        """The response's token loop on the device, arg-max or sampled: -> (output ids, cache)."""
+        """The response's token loop on the device, arg-max or sampled, under the driver's constraints if it has any: -> (output ids, cache)."""
+        cons = self._response_constraints()
+        if cons is None:
+            return self._native_response_loop()
+        was = self.model.set_generate_constraints(cons)
+        try:
+            return self._native_response_loop()
+        finally:
+            from . import constraints as _constraints
+            self.model.set_generate_constraints(was or _constraints.OFF)
+
+    def _native_response_loop(self):
         if self.do_sample:
             output_ids, past_key_values, self.generated_token_ids, self._sample_offset = fast_sample_generate(
                 model=self.model, inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values,

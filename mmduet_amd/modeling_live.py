@@ -15,7 +15,7 @@ import weakref
 from typing import Optional
 import torch
 
-from . import _lib
+from . import _lib, constraints as _constraints
 from ._lib import lib, check, MmdConfig, MMD_BF16, MMD_F32, POOL_MODES
 from .configuration_live import VideoHeadLiveLlavaQwenConfig
 from .tokenization_live import build_live_tokenizer_and_update_config
@@ -104,10 +104,12 @@ class KVCacheHandle:
 _U64 = (1 << 64) - 1
 # generate() arguments that ask for something this package does not build: the value that means "off" is accepted, anything else raises
 _GENERATE_OFF = {'num_beams': 1, 'num_beam_groups': 1, 'num_return_sequences': 1, 'min_p': None, 'typical_p': 1.0, 'penalty_alpha': None, 'epsilon_cutoff': 0.0, 'eta_cutoff': 0.0,
-                 'diversity_penalty': 0.0, 'length_penalty': 1.0, 'no_repeat_ngram_size': 0, 'encoder_repetition_penalty': 1.0, 'bad_words_ids': None, 'force_words_ids': None,
-                 'constraints': None, 'logits_processor': None, 'stopping_criteria': None, 'prefix_allowed_tokens_fn': None, 'min_length': 0, 'min_new_tokens': None,
-                 'sequence_bias': None, 'guidance_scale': None, 'assistant_model': None, 'streamer': None, 'output_scores': False, 'output_logits': False,
+                 'diversity_penalty': 0.0, 'length_penalty': 1.0, 'no_repeat_ngram_size': 0, 'encoder_repetition_penalty': 1.0, 'force_words_ids': None,
+                 'constraints': None, 'logits_processor': None, 'stopping_criteria': None, 'prefix_allowed_tokens_fn': None, 'min_length': 0,
+                 'guidance_scale': None, 'assistant_model': None, 'streamer': None, 'output_scores': False, 'output_logits': False,
                  'output_attentions': False, 'output_hidden_states': False, 'early_stopping': False, 'renormalize_logits': False}
+# the constraint arguments (DESIGN.md "Constraints"): merged by constraints.merge, applied on the device
+_GENERATE_CONSTRAINTS = ('min_new_tokens', 'suppress_tokens', 'bad_words_ids', 'sequence_bias')
 _GENERATE_IGNORED = ('attention_mask', 'position_ids', 'use_cache', 'return_dict', 'pad_token_id', 'bos_token_id', 'synced_gpus')
 
 
@@ -130,15 +132,20 @@ class SamplerHandle:
             check(lib().mmd_sampler_create(model._ctx, C.byref(h)), model._ctx, 'mmd_sampler_create')
         self.h = h.value
 
-    def begin(self, eos_token_id, repetition_penalty, generated_token_ids, max_new_tokens, sampling=None):
+    def begin(self, eos_token_id, repetition_penalty, generated_token_ids, max_new_tokens, sampling=None, constraints=None):
         """Start of a response: the penalty list is every id generated so far in this video (it persists across turns, models/modeling_live.py:60-66).
-        sampling: None = arg-max, or dict(temperature, top_k, top_p, seed) handed to mmd_sampler_set_sampling (the Philox offset restarts only when the seed changes)."""
+        sampling: None = arg-max, or dict(temperature, top_k, top_p, seed) handed to mmd_sampler_set_sampling (the Philox offset restarts only when the seed changes).
+        constraints: None = off, or a constraints.Constraints handed to mmd_sampler_set_constraints (with an EOS set given, eos_token_id is ignored)."""
         pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
         prev = list(generated_token_ids) if (generated_token_ids is not None and pen > 0) else []
         arr = (C.c_int64 * max(1, len(prev)))(*prev)
         with self.model._lock:
             self.model._bind_stream()
             check(lib().mmd_sampler_begin(self.h, int(eos_token_id if eos_token_id is not None else -1), pen, arr, len(prev), int(max_new_tokens)), self.model._ctx, 'mmd_sampler_begin')
+            cons_on = constraints is not None and constraints.on
+            if cons_on or getattr(self, '_constraints_on', False):          # (a sampler that never had constraints is not touched)
+                check(lib().mmd_sampler_set_constraints(self.h, *_constraints.c_arrays(constraints if cons_on else None)), self.model._ctx, 'mmd_sampler_set_constraints')
+                self._constraints_on = cons_on
             if sampling is None and not getattr(self, '_sampling_on', False):
                 return          # arg-max, as the sampler was created: nothing to switch
             sm = sampling or {}
@@ -339,6 +346,7 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         self._ctx = h
         self._lock = threading.RLock()      # the Gradio demo calls the model from two threads (demo/app.py:84-85)
         self._logprobs_top, self._last_logprobs = -1, None          # set_generate_logprobs / last_generate_logprobs
+        self._constraints = None          # set_generate_constraints
         self._embed = _Embedding(self)
         self._tower = _VisionTower(self)
         self._finalized = False
@@ -845,6 +853,21 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             check(lib().mmd_set_generate_logprobs(self._ctx, top_n), self._ctx, 'mmd_set_generate_logprobs')
             self._logprobs_top = top_n
 
+    def set_generate_constraints(self, constraints=None, *, eos_token_id=None, min_new_tokens=None, suppress_tokens=None, bad_words_ids=None, sequence_bias=None):
+        """mmd_set_generate_constraints: the following greedy_generate / sample_generate calls decode under the constraints (DESIGN.md "Constraints") -- an EOS set of up to 8
+        ids (the calls' own eos_token_id is then ignored), min_new_tokens, suppressed ids, single-token bad_words_ids and sequence_bias.  Either a constraints.Constraints or
+        the HF-shaped keywords; nothing (or a set that constrains nothing) switches them off, the default.  Returns what was set before."""
+        if constraints is None:
+            constraints = _constraints.merge(self.config.vocab_size, eos_token_id, min_new_tokens, suppress_tokens, bad_words_ids, sequence_bias)
+        if not constraints.on:
+            constraints = None
+        with self._lock:
+            was = getattr(self, '_constraints', None)
+            if constraints is not None or was is not None:
+                check(lib().mmd_set_generate_constraints(self._ctx, *_constraints.c_arrays(constraints)), self._ctx, 'mmd_set_generate_constraints')
+            self._constraints = constraints
+        return was
+
     def _read_generate_logprobs(self, n_tokens):
         top = self._logprobs_top
         lp, slp = torch.empty(n_tokens, dtype=torch.float32), torch.empty(n_tokens, dtype=torch.float32)
@@ -905,6 +928,7 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         if 'max_length' in kwargs and kwargs['max_length'] is not None:
             raise NotImplementedError('generate: max_length is not supported, pass max_new_tokens')
         kwargs.pop('max_length', None)
+        cons_kw = {k: kwargs.pop(k) for k in _GENERATE_CONSTRAINTS if k in kwargs}
         for k, v in kwargs.items():
             if k in _GENERATE_IGNORED:
                 continue
@@ -912,6 +936,16 @@ class VideoHeadLiveLlavaQwenForCausalLM:
                 raise NotImplementedError(f'generate: argument {k!r} is not supported')
             if v is not None and v != _GENERATE_OFF[k]:
                 raise NotImplementedError(f'generate: {k}={v!r} is not supported')
+        if eos_token_id is None:
+            eos_token_id = getattr(self.config, 'eos_token_id', None)
+        if isinstance(eos_token_id, (list, tuple)):
+            eos_token_id = list(dict.fromkeys(int(t) for t in eos_token_id))
+            if len(eos_token_id) <= 1:
+                eos_token_id = eos_token_id[0] if eos_token_id else None
+        # one EOS id and nothing else asked for: the unconstrained loop, as before.  Otherwise the merged set holds for this call (a set switched on for the bare loops is put back)
+        cons = _constraints.merge(self.config.vocab_size, eos_token_id if isinstance(eos_token_id, list) else None, **cons_kw)
+        if isinstance(eos_token_id, list):
+            eos_token_id = eos_token_id[0]          # (ignored by the native call: the set is given)
         prompt = input_ids
         if inputs_embeds is None:
             if input_ids is None:
@@ -923,14 +957,9 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             inputs_embeds = inputs_embeds[None]
         if inputs_embeds.shape[0] != 1:
             raise NotImplementedError('generate: batch size 1 only (streaming is batch 1)')
-        if eos_token_id is None:
-            eos_token_id = getattr(self.config, 'eos_token_id', None)
-        if isinstance(eos_token_id, (list, tuple)):
-            if len(eos_token_id) > 1:
-                raise NotImplementedError('generate: one eos_token_id only')
-            eos_token_id = eos_token_id[0] if eos_token_id else None
         pen = float(repetition_penalty) if repetition_penalty not in (None, 1.0) else None
         max_new_tokens = int(max_new_tokens)
+        cons_was = self.set_generate_constraints(cons) if (cons.on or self._constraints is not None) else None
         was = self._logprobs_top
         if output_logprobs or was >= 0:          # (this call's own setting; a recording switched on for the bare loops is put back afterwards)
             self.set_generate_logprobs(top_logprobs if output_logprobs else -1)
@@ -950,6 +979,8 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         finally:
             if self._logprobs_top != was:
                 self.set_generate_logprobs(was)
+            if cons.on or cons_was is not None:
+                self.set_generate_constraints(cons_was or _constraints.OFF)
         new = torch.tensor([ids], dtype=torch.long, device=self.device).view(1, -1)
         seq = new if prompt is None else torch.cat([prompt.reshape(1, -1).to(device=self.device, dtype=torch.long), new], dim=1)
         if not return_dict_in_generate:
@@ -1009,6 +1040,51 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             check(lib().mmd_op_sample_logprobs(self._ctx, _ptr(lg), n, V, _ptr(prev), 0 if prev is None else prev.numel(), float(repetition_penalty or 0.0), float(temperature),
                                                int(top_k or 0), float(top_p), int(seed) & _U64, int(offset) & _U64, r_arr, int(bool(greedy)), top_n, _ptr(toks), _ptr(info),
                                                _ptr(scores), _ptr(lp), _ptr(top_ids), _ptr(top_lp)), self._ctx, 'mmd_op_sample_logprobs')
+        return toks, info, scores, lp, top_ids, top_lp
+
+    def sample_constrained_op(self, logits, constraints, steps=0, temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, r=None, prev_ids=None, repetition_penalty=None,
+                              greedy=False, top_n=None, return_scores=False):
+        """`sample_logprob_op` under constraints (mmd_op_sample_constrained).  constraints: one constraints.Constraints for every row or a list of one per row; steps: the
+        tokens returned so far, an int or one per row.  top_n None: no records (lp / top ids / top logprobs are None), else 0..8.  ValueError when a row has nothing to draw
+        from.  -> (tokens [n], info [n, 4] or None, scores [n, V] or None, lp [n, 2], top ids, top logprobs)."""
+        lg = logits.to(device=self.device, dtype=torch.float32).contiguous()
+        if lg.ndim == 1:
+            lg = lg[None]
+        n, V = lg.shape
+        cons = [constraints] * n if isinstance(constraints, _constraints.Constraints) else list(constraints)
+        steps = [int(steps)] * n if isinstance(steps, int) else [int(v) for v in steps]
+        if len(cons) != n or len(steps) != n:
+            raise ValueError('one constraint set and one step per row')
+        off = [0]
+        for cs in cons:
+            off.append(off[-1] + len(cs.ids))
+        eos = [([int(t) for t in cs.eos] + [-1] * 8)[:max(8, len(cs.eos))] for cs in cons]
+        if any(len(e) > 8 for e in eos):
+            raise ValueError('at most 8 EOS ids per row')
+        flat_ids = [t for cs in cons for t in cs.ids]
+        flat_bias = [b for cs in cons for b in cs.bias]
+        toks = torch.empty(n, dtype=torch.long, device=self.device)
+        info = None if greedy else torch.empty(n, 4, dtype=torch.float32, device=self.device)
+        scores = torch.empty(n, V, dtype=torch.float32, device=self.device) if return_scores else None
+        prev = torch.as_tensor(prev_ids, dtype=torch.long).to(self.device).contiguous() if prev_ids is not None and len(prev_ids) else None
+        rec = top_n is not None
+        tn = int(top_n or 0)
+        lp = torch.empty(n, 2, dtype=torch.float32) if rec else None
+        top_ids = torch.empty(n, tn, dtype=torch.long) if rec else None
+        top_lp = torch.empty(n, tn, dtype=torch.float32) if rec else None
+        r_arr = None
+        if r is not None:
+            if len(r) != n:
+                raise ValueError('one random word per row')
+            r_arr = (C.c_uint64 * n)(*[int(v) & _U64 for v in r])
+        with self._lock:
+            self._bind_stream()
+            check(lib().mmd_op_sample_constrained(self._ctx, _ptr(lg), n, V, _ptr(prev), 0 if prev is None else prev.numel(), float(repetition_penalty or 0.0), float(temperature),
+                                                  int(top_k or 0), float(top_p), int(seed) & _U64, int(offset) & _U64, r_arr, int(bool(greedy)), tn,
+                                                  (C.c_int32 * (n + 1))(*off), (C.c_int32 * max(1, len(flat_ids)))(*flat_ids), (C.c_float * max(1, len(flat_bias)))(*flat_bias),
+                                                  (C.c_int64 * (8 * n))(*[t for e in eos for t in e]), (C.c_int32 * n)(*[len(cs.eos) for cs in cons]),
+                                                  (C.c_int32 * n)(*[int(cs.min_new) for cs in cons]), (C.c_int32 * n)(*steps),
+                                                  _ptr(toks), _ptr(info), _ptr(scores), _ptr(lp), _ptr(top_ids), _ptr(top_lp)), self._ctx, 'mmd_op_sample_constrained')
         return toks, info, scores, lp, top_ids, top_lp
 
     # ---- measurement --------------------------------------------------------------------------------------------------

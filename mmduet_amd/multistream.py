@@ -68,6 +68,22 @@ class _ModelProxy:
 
     forward = __call__
 
+    def set_generate_constraints(self, constraints=None, **kw):
+        """The real model's call for THIS slot: the set rides on the slot's following generate requests and the scheduler hands it to the slot's sampler beside
+        mmd_sampler_begin (the context-wide setting of the real model is not touched).  Returns what was set before."""
+        from . import constraints as _constraints
+        if constraints is None:
+            constraints = _constraints.merge(self._real.config.vocab_size, **kw)
+        was = self.__dict__.get('_constraints')
+        self.__dict__['_constraints'] = constraints if constraints.on else None
+        return was
+
+    def _is_eos(self, eos_token_id):
+        """EOS test of this slot's responses: the constraint set's EOS ids when it has any, else the call's own id."""
+        cons = self.__dict__.get('_constraints')
+        eos = set(cons.eos) if cons is not None and cons.eos else {eos_token_id}
+        return cons, eos
+
     def sample_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None,
                         temperature=1.0, top_k=0, top_p=1.0, seed=0, offset=0, lane=None):
         """The sampled response of one slot, a scheduler round per token: the slot's sampler draws on the device (mmd_round_multi) on its own Philox lane, so the ids do
@@ -79,11 +95,12 @@ class _ModelProxy:
             return [], past_key_values, int(offset)
         pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
         grow = generated_token_ids is not None and pen > 0
-        gen = dict(slot=self._slot, eos=eos_token_id, max_new=int(max_new_tokens), ids=[], penalty=pen if pen > 0 else None, prev=list(generated_token_ids) if grow else None,
-                   sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, restart=int(offset) == 0))
+        cons, eos_set = self._is_eos(eos_token_id)
+        gen = dict(slot=self._slot, eos=eos_token_id, eos_set=eos_set, constraints=cons, max_new=int(max_new_tokens), ids=[], penalty=pen if pen > 0 else None,
+                   prev=list(generated_token_ids) if grow else None, sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, restart=int(offset) == 0))
         r = self._slot.post(_Request('generate', inputs_embeds, past_key_values, gen=gen))
         if grow:
-            generated_token_ids.extend(t for t in r['ids'] if t != eos_token_id)
+            generated_token_ids.extend(t for t in r['ids'] if t not in eos_set)
         return r['ids'], r['cache'], int(offset) + len(r['ids'])
 
     def greedy_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None):
@@ -91,12 +108,15 @@ class _ModelProxy:
         written but neither fed back nor penalised; HF repetition penalty over every token generated so far in this video)."""
         if hasattr(self._real, 'round_multi') and not self._slot.sched.python_decode:
             # the whole response is ONE request: the scheduler advances it a token per round (mmd_round_multi samples on the device) and wakes this slot when it is complete
-            gen = dict(slot=self._slot, eos=eos_token_id, max_new=int(max_new_tokens), ids=[], penalty=repetition_penalty,
+            cons, eos_set = self._is_eos(eos_token_id)
+            gen = dict(slot=self._slot, eos=eos_token_id, eos_set=eos_set, constraints=cons, max_new=int(max_new_tokens), ids=[], penalty=repetition_penalty,
                        prev=list(generated_token_ids) if (generated_token_ids is not None and repetition_penalty is not None) else None)
             r = self._slot.post(_Request('generate', inputs_embeds, past_key_values, gen=gen))
             if generated_token_ids is not None and repetition_penalty is not None:
-                generated_token_ids.extend(t for t in r['ids'] if t != eos_token_id)
+                generated_token_ids.extend(t for t in r['ids'] if t not in eos_set)
             return r['ids'], r['cache']
+        if self.__dict__.get('_constraints') is not None:
+            raise NotImplementedError('constrained responses of several streams need the native rounds (mmd_round_multi)')
         pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
         seen = generated_token_ids if (generated_token_ids is not None and pen > 0) else None
         x, cache, ids = inputs_embeds, past_key_values, []
@@ -284,10 +304,10 @@ class MultiStreamInfer:
                     if slot.sampler is None:
                         slot.sampler = self.model.new_sampler()
                     g['sampler'] = slot.sampler
-                    if g.get('sampling') is not None:
-                        g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'], sampling=g['sampling'])
-                    else:
-                        g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'])
+                    extra = dict(sampling=g['sampling']) if g.get('sampling') is not None else {}
+                    if g.get('constraints') is not None or getattr(g['sampler'], '_constraints_on', False):          # (a duck-typed sampler without constraints is called as before)
+                        extra['constraints'] = g.get('constraints')
+                    g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'], **extra)
                     segs.append(dict(x=r.x, cache=r.cache, sampler=g['sampler'], sample=True))
                 else:
                     segs.append(dict(x=None, cache=g['cache'], sampler=g['sampler'], feed=True, sample=True))
@@ -309,7 +329,7 @@ class MultiStreamInfer:
                 g = r.gen
                 g['cache'] = o['cache']
                 g['ids'].append(o['token'])
-                if o['token'] == g['eos'] or len(g['ids']) >= g['max_new']:
+                if o['token'] in g.get('eos_set', (g['eos'],)) or len(g['ids']) >= g['max_new']:
                     g['done'] = True
                     r.result = dict(ids=g['ids'], cache=g['cache'])
             elif r.kind == 'forward':
