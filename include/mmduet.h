@@ -160,7 +160,14 @@ int mmd_kv_truncate(mmd_stream* s, int64_t new_len);      /* rollback: remove_as
  * the middle of a multi-frame chunk overwrites the slots behind it and is then dropped -- the frames already encoded behind it are restored, not recomputed */
 int mmd_kv_stash(mmd_stream* s, int64_t from, int64_t to);
 int mmd_kv_unstash(mmd_stream* s);
-int mmd_stream_reset(mmd_stream* s);                      /* LiveInferForBenchmark.reset (test/inference.py:169-183: past_key_values = None): length 0, arena kept */
+/* Sliding context window: slots [from, to) leave every layer's arena and the tokens behind them move down to [from, len - (to - from)), bit for bit (keys keep
+ * the rotation they were written with; nothing is re-rotated).  The length shrinks by to - from, mmd_kv_position stays: tokens written afterwards take slot
+ * mmd_kv_len and RoPE position mmd_kv_position = length + everything dropped so far.  One launch on the context's stream, no host synchronisation; pages stay
+ * mapped; slots at or above the new length are unspecified.  from == to enqueues nothing, to == length is a truncate that keeps the position.
+ * MMD_ERANGE unless 0 <= from <= to <= length, MMD_EINVAL while a stash is held.  mmd_kv_truncate leaves the position offset alone, mmd_stream_reset zeroes it. */
+int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to);
+int64_t mmd_kv_position(const mmd_stream* s);             /* RoPE position of the next token written: mmd_kv_len + tokens dropped (-1: null stream) */
+int mmd_stream_reset(mmd_stream* s);                      /* LiveInferForBenchmark.reset (test/inference.py:169-183: past_key_values = None): length 0, position 0, arena kept */
 int mmd_kv_debug_set_len(mmd_stream* s, int64_t n);       /* measurement aid: mark n slots live without computing them */
 
 /* replaces VideoHeadLiveLlavaQwenForCausalLM.forward body (models/live_llava/video_head_live_llava_qwen.py:141) ==

@@ -44,6 +44,9 @@ def main(argv=None):
     sp.add_argument('--eos_token_ids', type=int, nargs='+', default=None)
     sp.add_argument('--min_new_tokens', type=int, default=0)
     sp.add_argument('--suppress_tokens', type=int, nargs='*', default=[])
+    # sliding context window (DESIGN.md "Context window"): at most N tokens of context (0 = off), the first M kept for good (default: what the stream's first forward encoded)
+    sp.add_argument('--context_window', type=int, default=0)
+    sp.add_argument('--context_sink', type=int, default=None)
     for k, v in vars(sp.parse_known_args(sys.argv[1:] if argv is None else argv)[0]).items():
         setattr(args, k, v)
     args.output_logprobs, args.top_logprobs = args.logprobs is not None, args.logprobs or 0

@@ -95,7 +95,7 @@ template <typename T> __device__ __forceinline__ float silu_t(float x) {
 static inline size_t dtype_size(int dt) { return dt == MMD_F32 ? 4 : 2; }
 
 // device-resident state of a graph-captured decode step (updated by the last kernel of the graph)
-struct StepState { long long n_ctx; long long cap; void* K; void* V; int n_prev; int step; };          // step: index of the decode step within its generate call (the slot of its log-probability record)
+struct StepState { long long n_ctx; long long cap; void* K; void* V; int n_prev; int step; long long pos_off; };          // step: index of the decode step within its generate call (the slot of its log-probability record); pos_off: RoPE position of slot n_ctx minus n_ctx (tokens dropped by mmd_kv_drop)
 
 // ---- the GEMM family (arguments, epilogues, kernel ids and the dispatch decision: gemm_plan.h) ---------------------------
 const GemmTuning& gemm_tuning();          // the process's GemmTuning (MMDUET_GEMV_KSPLIT_SHORT, read once)
@@ -121,15 +121,17 @@ int slab_resid_maxs(int splits);          // the instantiation (slabs a thread l
 constexpr int OP_PLAN_SLAB_RESID = 32;    // mmd_op_gemm_last_plan after mmd_op_slab_resid_rmsnorm: {this, instantiation, splits, blocks = M} (no GEMM_K_* value)
 hipError_t launch_slab_rope_append(const float* slabs, int splits, const void* bias, int S, int nh, int nkv, int d, const float* inv_freq_dev,
                                    int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st, const StepState* dyn = nullptr, int layer = 0,
-                                   int slab_rows = 0);          // slab_rows: rows of one slab when the projection ran over more rows than this stream's S (0 = S); `slabs` points at the stream's first row
-hipError_t launch_rope_table(void* tab, int S, int half, const float* inv_freq_dev, int64_t pos0, hipStream_t st, const StepState* dyn = nullptr);   // float2 [S][half], bf16-rounded
+                                   int slab_rows = 0, int64_t pos_off = 0);          // slab_rows: rows of one slab when the projection ran over more rows than this stream's S (0 = S); `slabs` points at the stream's first row; pos_off: the RoPE position of row s is pos0 + pos_off + s, its slot pos0 + s (dyn: both from *dyn)
+hipError_t launch_rope_table(void* tab, int S, int half, const float* inv_freq_dev, int64_t pos0, hipStream_t st, const StepState* dyn = nullptr);   // float2 [S][half], bf16-rounded; pos0 = the RoPE position of row 0 (dyn: n_ctx + pos_off of *dyn)
 struct ConstraintRow;
 hipError_t launch_advance_state(StepState* st_dev, const int64_t* tok_dev, int64_t* prev_dev, int prev_cap, int64_t eos, int use_penalty, hipStream_t st,
                                 const ConstraintRow* cons_dev = nullptr);          // cons_dev: EOS is membership of its set (read on the device), `eos` is ignored
 hipError_t launch_add_rows(int dtype, void* x, const void* add, int M, int H, int period, hipStream_t st);   // x[m,:] += add[m % period,:]
 hipError_t launch_rope_append_chunk(const void* qkv, int S, int nh, int nkv, const void* tab, int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st);   // bf16, d = 128, transposed V, table from launch_rope_table
 hipError_t launch_rope_append(int dtype, const void* qkv, int S, int nh, int nkv, int d, const float* inv_freq_dev, int64_t pos0, void* q_out,
-                              void* Kc, void* Vc, int64_t cap, int v_transposed, hipStream_t st);
+                              void* Kc, void* Vc, int64_t cap, int v_transposed, hipStream_t st, int64_t pos_off = 0);          // slot pos0 + s, RoPE position pos0 + pos_off + s
+// mmd_kv_drop: in every one of `rows` (layer, kv head) rows of `pitch_bytes`, tokens [to, len) of K (rows of tok_bytes) and of V (transposed 64-token blocks) move down to [from, ...)
+hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, hipStream_t st);
 hipError_t launch_transpose_v(int dtype, const void* src, void* dst, int nkv, int64_t cap, int d, hipStream_t st);
 hipError_t launch_embed(int dtype, const void* table, const int64_t* ids, int k, int H, int64_t vocab, void* out, hipStream_t st);
 hipError_t launch_im2col(int dtype, const void* px, int B, int img, int patch, int grid, int Kpad, void* out, hipStream_t st);

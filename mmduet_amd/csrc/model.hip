@@ -138,6 +138,7 @@ struct mmd_stream {
     mmd_ctx* ctx;
     void* K = nullptr; void* V = nullptr;      // [layers][nkv][cap][d]   (cap = the row STRIDE in tokens)
     int64_t cap = 0, len = 0;
+    int64_t pos_off = 0;                       // tokens dropped in front of the live ones (mmd_kv_drop): the RoPE position of slot t is t + pos_off for every token written from now on
     // virtual-memory arena (default): K / V are address ranges reserved for `cap` tokens per (layer, kv head) row; physical pages back only the
     // first `mapped` tokens of every row and are added chunk by chunk -- growth copies nothing and never needs a second arena
     bool vmm = false;
@@ -1203,7 +1204,26 @@ extern "C" int mmd_kv_unstash(mmd_stream* s) {
     return MMD_OK;
 }
 
-extern "C" int mmd_stream_reset(mmd_stream* s) { if (!s) return MMD_EINVAL; s->len = 0; s->stash_from = s->stash_to = -1; return MMD_OK; }
+extern "C" int mmd_stream_reset(mmd_stream* s) { if (!s) return MMD_EINVAL; s->len = 0; s->pos_off = 0; s->stash_from = s->stash_to = -1; return MMD_OK; }
+
+// Sliding context window: slots [from, to) leave every layer's arena, the tokens behind them move down bit for bit (keys keep the rotation they were written
+// with) and the stream goes on counting RoPE positions where it was: position = slot + pos_off.  One launch on the context's stream (launch_kv_drop), no
+// host synchronisation; pages stay mapped; slots at or above the new length hold unspecified bits.
+extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) {
+    if (!s) return MMD_EINVAL;
+    mmd_ctx* c = s->ctx;
+    if (from < 0 || to < from || to > s->len) FAIL(c, MMD_ERANGE, "kv_drop [%lld, %lld) outside the context (%lld tokens)", (long long)from, (long long)to, (long long)s->len);
+    if (s->stash_from >= 0) FAIL(c, MMD_EINVAL, "kv_drop while tokens [%lld, %lld) are stashed (unstash or drop the stash first)", (long long)s->stash_from, (long long)s->stash_to);
+    if (from == to) return MMD_OK;
+    if (to < s->len) {
+        hipSetDevice(c->device);
+        const size_t tok = (size_t)c->cfg.head_dim * es(c);
+        HIPCHK(c, launch_kv_drop(c->cfg.dtype, s->K, s->V, c->cfg.num_layers * c->cfg.num_kv_heads, (int64_t)((size_t)s->cap * tok), c->cfg.head_dim, from, to, s->len, c->stream));
+    }
+    s->len -= to - from; s->pos_off += to - from;
+    return MMD_OK;
+}
+extern "C" int64_t mmd_kv_position(const mmd_stream* s) { return s ? s->len + s->pos_off : -1; }          // the RoPE position the next token gets
 
 static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need);
 // measurement aid (tools/kv_growth_sweep.py): declare the first n slots of the arena live without computing them, to time a
@@ -1310,7 +1330,7 @@ static int upload_seg_states(StepRun& r) {
     c->seg_slot = (slot + 1) & 7;
     if (!c->seg_event[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->seg_event[slot], hipEventDisableTiming));
     else HIPCHK(c, hipEventSynchronize(c->seg_event[slot]));          // (eight steps old: long done unless the caller queues steps without ever synchronising)
-    for (int j = 0; j < r.p.run_n; ++j) { mmd_stream* sj = r.segs[r.p.run0 + j].s; hs[j].n_ctx = sj->len; hs[j].cap = sj->cap; hs[j].K = sj->K; hs[j].V = sj->V; hs[j].n_prev = 0; hs[j].step = 0; }
+    for (int j = 0; j < r.p.run_n; ++j) { mmd_stream* sj = r.segs[r.p.run0 + j].s; hs[j].n_ctx = sj->len; hs[j].cap = sj->cap; hs[j].K = sj->K; hs[j].V = sj->V; hs[j].n_prev = 0; hs[j].step = 0; hs[j].pos_off = sj->pos_off; }
     HIPCHK(c, hipMemcpyAsync(ds, hs, sizeof(StepState) * r.p.run_n, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->seg_event[slot], st));
     r.seg_states = ds;
@@ -1335,11 +1355,11 @@ static int layer_qkv(StepRun& r, int i, int* splits) {
         const size_t le = kv_layer_elems(c, sj->cap);
         void* q = (char*)c->l_q + (size_t)sg.row0 * nh * d * e; void* K = (char*)sj->K + (size_t)i * le * e; void* V = (char*)sj->V + (size_t)i * le * e;
         if (r.p.schedule != STEP_TILE)
-            HIPCHK(c, launch_slab_rope_append(c->splitk_ws + (size_t)sg.row0 * c->qkv_w, *splits, L.bqkv, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, st, r.dyn, i, S));
+            HIPCHK(c, launch_slab_rope_append(c->splitk_ws + (size_t)sg.row0 * c->qkv_w, *splits, L.bqkv, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, st, r.dyn, i, S, sj->pos_off));
         else if (r.p.chunk_rope)          // vectorised form over the step's (cos, sin) table (built once, before the layer loop)
             HIPCHK(c, launch_rope_append_chunk((char*)c->l_qkv + (size_t)sg.row0 * c->qkv_w * e, sg.rows, nh, nkv, (char*)c->rope_tab + (size_t)sg.row0 * 64 * 8, sj->len, q, K, V, sj->cap, st));
         else
-            HIPCHK(c, launch_rope_append(dt, (char*)c->l_qkv + (size_t)sg.row0 * c->qkv_w * e, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, 1, st));
+            HIPCHK(c, launch_rope_append(dt, (char*)c->l_qkv + (size_t)sg.row0 * c->qkv_w * e, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, 1, st, sj->pos_off));
     }
     return MMD_OK;
 }
@@ -1486,7 +1506,7 @@ static int llm_step_segs(mmd_ctx* c, const StepSeg* segs, int nseg, const void* 
     if (!tile) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * H * e, 0); HIPCHK(c, launch_rmsnorm(dt, c->l_h, c->L[0].ln1, c->l_xn, S, H, g.rms_norm_eps, st)); }
     if (p.run_n > 0) { rc = upload_seg_states(r); if (rc) return rc; }
     // one (cos, sin) table per step and segment: read by the attention kernel's own q / k / v preparation, or by the vectorised RoPE + append kernel of every layer of a chunk
-    if (p.rope_fused || p.chunk_rope) for (int j = 0; j < nseg; ++j) HIPCHK(c, launch_rope_table((char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8, segs[j].rows, 64, c->inv_freq, segs[j].s->len, st, dyn));
+    if (p.rope_fused || p.chunk_rope) for (int j = 0; j < nseg; ++j) HIPCHK(c, launch_rope_table((char*)c->rope_tab + (size_t)segs[j].row0 * 64 * 8, segs[j].rows, 64, c->inv_freq, segs[j].s->len + segs[j].s->pos_off, st, dyn));
     for (int i = 0; i < g.num_layers; ++i) {
         int splits = 1;
         rc = layer_qkv(r, i, &splits); if (rc) return rc;
@@ -2147,7 +2167,7 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
     if (can_graph || (samp && more)) {          // the sampled step reads the list length through *step_dev on the eager route too
         StepState* hs = c->step_host;
-        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->step = 1;
+        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->step = 1; hs->pos_off = s->pos_off;
         HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
     }
     if (samp && more) { rc = post_row(true); if (rc) return rc; }

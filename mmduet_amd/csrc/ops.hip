@@ -301,9 +301,9 @@ hipError_t launch_slab_resid_rmsnorm(const float* slabs, int splits, int M, int 
 
 __global__ void slab_rope_append_kernel(const float* __restrict__ slabs, int splits, const bf16_t* __restrict__ bias, int S, int nh, int nkv, int d,
                                         const float* __restrict__ inv_freq_tab, long long pos0, bf16_t* __restrict__ q_out, bf16_t* __restrict__ Kc,
-                                        bf16_t* __restrict__ Vc, long long cap, const StepState* __restrict__ dyn, int layer, int slab_rows) {
+                                        bf16_t* __restrict__ Vc, long long cap, const StepState* __restrict__ dyn, int layer, int slab_rows, long long pos_off) {
     if (dyn) {                                     // graph replay: position / arena come from device state
-        pos0 = dyn->n_ctx; cap = dyn->cap;
+        pos0 = dyn->n_ctx; cap = dyn->cap; pos_off = dyn->pos_off;
         const long long le = (long long)nkv * cap * d;
         Kc = (bf16_t*)dyn->K + layer * le; Vc = (bf16_t*)dyn->V + layer * le;
     }
@@ -311,7 +311,7 @@ __global__ void slab_rope_append_kernel(const float* __restrict__ slabs, int spl
     const int row_w = (nh + 2 * nkv) * d;
     const long long MN = (long long)slab_rows * row_w;
     const long long base = (long long)s * row_w + (long long)head * d;
-    const long long pos = pos0 + s;
+    const long long pos = pos0 + s;                    // the slot; the angle is taken at pos + pos_off (tokens dropped in front of it, mmd_kv_drop)
     auto val = [&](int i) {                            // rnd(sum of slabs + bias): the bf16 output of the q/k/v projection
         float part[16];
 #pragma unroll
@@ -329,7 +329,7 @@ __global__ void slab_rope_append_kernel(const float* __restrict__ slabs, int spl
     }
     bf16_t* dst = head < nh ? q_out + (long long)s * nh * d + (long long)head * d : Kc + ((long long)(head - nh) * cap + pos) * d;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
-        float ang = (float)pos * inv_freq_tab[i];
+        float ang = (float)(pos + pos_off) * inv_freq_tab[i];
         float c = bf2f(f2bf(cosf(ang))), sn = bf2f(f2bf(sinf(ang)));
         float x1 = val(i), x2 = val(i + half);
         float o1 = bf2f(f2bf(x1 * c)) + bf2f(f2bf(-x2 * sn));
@@ -341,7 +341,7 @@ __global__ void slab_rope_append_kernel(const float* __restrict__ slabs, int spl
 // (cos, sin) of the step's positions, bf16-rounded as the RoPE consumers use them: one table per step, shared by all layers and heads
 // (the decode attention kernel's fused q / k preparation reads it instead of evaluating cosf / sinf per layer)
 __global__ void rope_table_kernel(float2* __restrict__ tab, int half, const float* __restrict__ inv_freq_tab, long long pos0, const StepState* __restrict__ dyn) {
-    if (dyn) pos0 = dyn->n_ctx;
+    if (dyn) pos0 = dyn->n_ctx + dyn->pos_off;
     const int s = blockIdx.x;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
         const float ang = (float)(pos0 + s) * inv_freq_tab[i];
@@ -354,10 +354,10 @@ hipError_t launch_rope_table(void* tab, int S, int half, const float* inv_freq_d
     return hipGetLastError();
 }
 hipError_t launch_slab_rope_append(const float* slabs, int splits, const void* bias, int S, int nh, int nkv, int d, const float* inv_freq_dev,
-                                   int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st, const StepState* dyn, int layer, int slab_rows) {
+                                   int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap, hipStream_t st, const StepState* dyn, int layer, int slab_rows, int64_t pos_off) {
     if (S <= 0) return hipSuccess;
     hipLaunchKernelGGL(slab_rope_append_kernel, dim3(S, nh + 2 * nkv), dim3(64), 0, st, slabs, splits, (const bf16_t*)bias, S, nh, nkv, d, inv_freq_dev,
-                       (long long)pos0, (bf16_t*)q_out, (bf16_t*)Kc, (bf16_t*)Vc, (long long)cap, dyn, layer, slab_rows > 0 ? slab_rows : S);
+                       (long long)pos0, (bf16_t*)q_out, (bf16_t*)Kc, (bf16_t*)Vc, (long long)cap, dyn, layer, slab_rows > 0 ? slab_rows : S, (long long)pos_off);
     return hipGetLastError();
 }
 
@@ -387,7 +387,7 @@ hipError_t launch_add_rows(int dtype, void* x, const void* add, int M, int H, in
 // ---------------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ void rope_append_kernel(const T* __restrict__ qkv, int S, int nh, int nkv, int d, const float* __restrict__ inv_freq_tab, long long pos0,
-                                   T* __restrict__ q_out, T* __restrict__ Kc, T* __restrict__ Vc, long long cap, int v_tr) {
+                                   T* __restrict__ q_out, T* __restrict__ Kc, T* __restrict__ Vc, long long cap, int v_tr, long long pos_off) {
     int s = blockIdx.x;
     int head = blockIdx.y;                 // 0..nh-1 q heads, nh..nh+nkv-1 k heads, then v heads
     int half = d >> 1;
@@ -407,7 +407,7 @@ __global__ void rope_append_kernel(const T* __restrict__ qkv, int S, int nh, int
     }
     T* dst = head < nh ? q_out + (long long)s * nh * d + (long long)head * d : Kc + ((long long)(head - nh) * cap + pos) * d;
     for (int i = threadIdx.x; i < half; i += blockDim.x) {
-        float ang = (float)pos * inv_freq_tab[i];       // fp32 product, like the reference's fp32 outer product
+        float ang = (float)(pos + pos_off) * inv_freq_tab[i];       // fp32 product, like the reference's fp32 outer product
         float c = rnd<T>(cosf(ang)), sn = rnd<T>(sinf(ang));
         float x1 = to_f<T>(src[i]), x2 = to_f<T>(src[i + half]);
         // out[i] = x1*cos + (-x2)*sin ; out[i+half] = x2*cos + x1*sin
@@ -487,11 +487,11 @@ hipError_t launch_rope_append_chunk(const void* qkv, int S, int nh, int nkv, con
 }
 
 hipError_t launch_rope_append(int dtype, const void* qkv, int S, int nh, int nkv, int d, const float* l2, int64_t pos0, void* q_out,
-                              void* Kc, void* Vc, int64_t cap, int v_tr, hipStream_t st) {
+                              void* Kc, void* Vc, int64_t cap, int v_tr, hipStream_t st, int64_t pos_off) {
     if (S <= 0) return hipSuccess;
     dim3 grid(S, nh + 2 * nkv), block(64);
-    if (dtype == MMD_F32) hipLaunchKernelGGL(rope_append_kernel<float>, grid, block, 0, st, (const float*)qkv, S, nh, nkv, d, l2, (long long)pos0, (float*)q_out, (float*)Kc, (float*)Vc, (long long)cap, v_tr);
-    else hipLaunchKernelGGL(rope_append_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)qkv, S, nh, nkv, d, l2, (long long)pos0, (bf16_t*)q_out, (bf16_t*)Kc, (bf16_t*)Vc, (long long)cap, v_tr);
+    if (dtype == MMD_F32) hipLaunchKernelGGL(rope_append_kernel<float>, grid, block, 0, st, (const float*)qkv, S, nh, nkv, d, l2, (long long)pos0, (float*)q_out, (float*)Kc, (float*)Vc, (long long)cap, v_tr, (long long)pos_off);
+    else hipLaunchKernelGGL(rope_append_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)qkv, S, nh, nkv, d, l2, (long long)pos0, (bf16_t*)q_out, (bf16_t*)Kc, (bf16_t*)Vc, (long long)cap, v_tr, (long long)pos_off);
     return hipGetLastError();
 }
 
@@ -980,6 +980,116 @@ hipError_t launch_copy_rows(int dtype, const void* src, int64_t lds_, void* dst,
     if (total <= 0) return hipSuccess;
     if (dtype == MMD_F32) hipLaunchKernelGGL(copy_rows_kernel<float>, dim3(cdiv(total, 256)), dim3(256), 0, st, (const float*)src, (long long)lds_, (float*)dst, (long long)ldd, rows, cols);
     else hipLaunchKernelGGL(copy_rows_kernel<bf16_t>, dim3(cdiv(total, 256)), dim3(256), 0, st, (const bf16_t*)src, (long long)lds_, (bf16_t*)dst, (long long)ldd, rows, cols);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mmd_kv_drop: tokens [to, len) of every (layer, kv head) row move down to [from, from + len - to), bit for bit.  The move overlaps itself whenever
+// to - from < len - to, so it is an OWNER WALK: a part of the row that the shift maps onto itself belongs to one block, which walks it front to back --
+// load a tile into registers, barrier, store.  A tile's destination lies below the next tile's source (to > from), so the one barrier per tile is the
+// whole ordering; blocks never touch each other's bytes, in whatever order they run.
+//   K [cap][d]: the owned part is a 16-byte-unit range of the token row (KU units, 128 bytes where the row allows), every token of it.
+//   V, transposed 64-token blocks ((t, e) at ((t >> 6) * d + e) * 64 + (t & 63)): the owned part is a range of EP dims.  A thread stores one aligned 16-byte
+//   group of destination tokens; its source tokens start (to - from) % VEC elements into an aligned group and may run into the next one (in the next block's
+//   line when the group is a line's last): two aligned loads and a byte funnel.  The group that holds `from` is stored element by element above `from` only.
+// grid (KSEG + ESPLIT, rows): blocks x < KSEG own K units [x * KU, ...), the others V dims [(x - KSEG) * EP, ...).
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int KVD_THREADS = 256, KVD_U = 4;          // a tile = 4 x 16 bytes per thread = 16 KiB per block in flight
+static __device__ __forceinline__ u32x4_t kvd_funnel(const u32x4_t a, const u32x4_t b, int sh) {          // bytes [sh, sh + 16) of a : b, sh < 16 (the same in every thread)
+    const unsigned w[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    const int ws = sh >> 2; const unsigned bs = sh & 3;
+    u32x4_t o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned lo = ws == 0 ? w[i] : ws == 1 ? w[i + 1] : ws == 2 ? w[i + 2] : w[i + 3];
+        const unsigned hi = ws == 0 ? w[i + 1] : ws == 1 ? w[i + 2] : ws == 2 ? w[i + 3] : w[i + 4];
+        o[i] = __builtin_amdgcn_alignbyte(hi, lo, bs);
+    }
+    return o;
+}
+template <int ES>          // ES: bytes per element (2 or 4)
+__global__ __launch_bounds__(KVD_THREADS) void kv_drop_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, long long from, long long to, long long len,
+                                                              int kseg, int ku, int ep, int nb) {
+    constexpr int VEC = 16 / ES, CPL = 64 / VEC;          // tokens per 16-byte group of a V line, groups per line
+    const int tid = threadIdx.x;
+    const long long n = len - to, delta = to - from;
+    u32x4_t ra[KVD_U];
+    if ((int)blockIdx.x < kseg) {
+        const long long tokb = (long long)d * ES;
+        char* row = Kb + (long long)blockIdx.y * pitch + (long long)blockIdx.x * ku * 16;
+        const long long tile = (long long)(KVD_THREADS * KVD_U) / ku;          // tokens per tile
+        for (long long t0 = 0; t0 < n; t0 += tile) {
+            long long off[KVD_U]; bool ok[KVD_U];
+#pragma unroll
+            for (int u = 0; u < KVD_U; ++u) {
+                const int idx = u * KVD_THREADS + tid;
+                const long long t = t0 + idx / ku;
+                ok[u] = idx / ku < tile && t < n;
+                off[u] = t * tokb + (idx % ku) * 16;
+                if (ok[u]) ra[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u]);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < KVD_U; ++u) if (ok[u]) *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u]) = ra[u];
+        }
+        return;
+    }
+    u32x4_t rb[KVD_U];
+    char* row = Vb + (long long)blockIdx.y * pitch;
+    const int e0 = ((int)blockIdx.x - kseg) * ep;
+    const int sh = (int)(delta % VEC) * ES;          // the source group's byte offset inside its aligned 16 bytes
+    const long long newlen = len - delta;
+    const int per_blk = ep * CPL;
+    for (long long b0 = from >> 6; b0 * 64 < newlen; b0 += nb) {          // nb destination blocks of 64 tokens per tile
+        long long dst[KVD_U]; long long tq[KVD_U]; bool ok[KVD_U];
+#pragma unroll
+        for (int u = 0; u < KVD_U; ++u) {
+            const int idx = u * KVD_THREADS + tid;
+            const int bi = idx / per_blk, r = idx % per_blk, e = e0 + r / CPL, g = r % CPL;
+            const long long t = (b0 + bi) * 64 + g * VEC;          // first destination token of the group
+            tq[u] = t;
+            ok[u] = bi < nb && t + VEC > from && t < newlen;
+            dst[u] = ((((t >> 6) * d + e) << 6) + (t & 63)) * ES;
+            if (ok[u]) {
+                const long long s0 = (t + delta) & ~(long long)(VEC - 1), s1 = s0 + VEC;          // the two aligned source groups
+                ra[u] = s0 < len ? *reinterpret_cast<const u32x4_t*>(row + ((((s0 >> 6) * d + e) << 6) + (s0 & 63)) * ES) : u32x4_t{0, 0, 0, 0};
+                rb[u] = sh && s1 < len ? *reinterpret_cast<const u32x4_t*>(row + ((((s1 >> 6) * d + e) << 6) + (s1 & 63)) * ES) : u32x4_t{0, 0, 0, 0};
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KVD_U; ++u) {
+            if (!ok[u]) continue;
+            const u32x4_t o = sh ? kvd_funnel(ra[u], rb[u], sh) : ra[u];
+            // (a group that straddles the new length also writes slots [newlen, t + VEC): unspecified under the contract, and finite -- copies of arena slots, which
+            // are finite by the arena's own invariant, or zeros where the source group starts at or above `len` -- which the masked tail of a key tile relies on)
+            if (tq[u] >= from) *reinterpret_cast<u32x4_t*>(row + dst[u]) = o;
+            else {          // the group that holds `from`: the tokens below it stay
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    if (tq[u] + k < from) continue;
+                    const unsigned w = o[(k * ES) >> 2];
+                    if (ES == 2) *reinterpret_cast<unsigned short*>(row + dst[u] + k * 2) = (unsigned short)(k & 1 ? w >> 16 : w);
+                    else *reinterpret_cast<unsigned*>(row + dst[u] + k * 4) = w;
+                }
+            }
+        }
+    }
+}
+hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, hipStream_t st) {
+    if (from < 0 || to < from || len < to) return hipErrorInvalidValue;
+    if (from == to || to == len || rows <= 0) return hipSuccess;
+    const int es = (int)dtype_size(dtype), units = d * es / 16, vec = 16 / es, cpl = 64 / vec;
+    if ((d * es) % 16 != 0 || (pitch_bytes % 16) != 0 || rows > 65535) return hipErrorInvalidValue;
+    const int ku = units % 8 == 0 ? 8 : units;                                  // 128-byte pieces of a K row where it divides
+    int esplit = d % 4 == 0 ? 4 : 1;
+    while (d % esplit == 0 && (d / esplit) * cpl > KVD_THREADS * KVD_U && esplit < d) esplit *= 2;
+    const int ep = d / esplit;
+    if (d % esplit != 0 || ep * cpl > KVD_THREADS * KVD_U || ku > KVD_THREADS * KVD_U) return hipErrorInvalidValue;
+    const int kseg = units / ku, nb = KVD_THREADS * KVD_U / (ep * cpl);
+    const dim3 grid(kseg + esplit, rows), block(KVD_THREADS);
+    if (es == 4) hipLaunchKernelGGL(kv_drop_kernel<4>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, kseg, ku, ep, nb);
+    else hipLaunchKernelGGL(kv_drop_kernel<2>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, kseg, ku, ep, nb);
     return hipGetLastError();
 }
 

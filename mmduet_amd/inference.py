@@ -41,6 +41,14 @@ def _p1(l0, l1):
     return 1.0 / (1.0 + math.exp(d)) if d < 700.0 else 0.0
 
 
+def context_drop_amount(length, rows, window, sink):
+    """Sliding context window: tokens to drop from [sink, sink + m) before a forward of `rows` rows on a context of `length` tokens -- the smallest m with
+    length - m + rows <= window, at most length - sink (the sink stays); 0 with the window off (window <= 0) or wide enough."""
+    if window <= 0 or length + rows <= window:
+        return 0
+    return max(0, min(length + rows - window, length - sink))
+
+
 class LiveInferForBenchmark:
     def __init__(self, args, model=None, tokenizer=None) -> None:
         assert not (args.bf16 and args.fp16), "only one of --bf16 true and --fp16 true can be set"
@@ -106,6 +114,10 @@ class LiveInferForBenchmark:
         self.suppress_tokens = list(getattr(args, 'suppress_tokens', None) or ())
         self.output_logprobs = bool(getattr(args, 'output_logprobs', False))
         self.top_logprobs = int(getattr(args, 'top_logprobs', 0) or 0)
+        # sliding context window (DESIGN.md "Context window"; off by default): keep `context_sink` tokens at the front (None: whatever the stream's first forward
+        # encoded -- the system prompt and what came with it) and drop the oldest tokens behind them whenever a forward would take the context past `context_window`
+        self.context_window = int(getattr(args, 'context_window', 0) or 0)
+        self.context_sink = getattr(args, 'context_sink', None)
         self.frames_per_forward = max(1, int(getattr(args, 'frames_per_forward', 1)))
         self.overlap_vision = bool(getattr(args, 'overlap_vision', True))
         self.record_head_logits = False          # diagnostics (parity tests, bench.py's self-check): debug_data entries also carry the 4 raw head logits of the frame
@@ -161,6 +173,8 @@ class LiveInferForBenchmark:
         self._vit_out = self._vit_pixels = self._vit_host = None
         self._vit_fused = False
         self._vit_batches, self._vit_events, self._vit_waited = [], [], set()
+        self._sink_tokens = None             # context_sink None: the context length right after this stream's first forward
+        self.dropped_tokens = 0              # tokens the context window took out of this stream
         self.forward_calls = 0              # LLM forwards issued (diagnostics of the chunked schedule)
         self.replayed_frames = 0
 
@@ -299,6 +313,24 @@ class LiveInferForBenchmark:
             return torch.cat([self.last_ids, self._added_stream_prompt_ids], dim=1)
         return self._no_ids()
 
+    def _apply_context_window(self, rows):
+        """Before a forward of `rows` rows on self.past_key_values: drop the oldest tokens behind the sink if the forward would take the context past the window.
+        Only called where no stash is held and no token offset into the cache is kept across the call (a response under a stash waits for the next forward)."""
+        if getattr(self, 'context_window', 0) <= 0 or not self.past_key_values:
+            return
+        sink = self._sink_tokens if self.context_sink is None else int(self.context_sink)
+        if sink is None:
+            return
+        n = len(self.past_key_values)
+        m = context_drop_amount(n, rows, self.context_window, min(sink, n))
+        if m > 0:
+            self.past_key_values = self.model.kv_drop(self.past_key_values, min(sink, n), min(sink, n) + m)
+            self.dropped_tokens += m
+
+    def _note_first_forward(self):
+        if getattr(self, '_sink_tokens', None) is None and self.past_key_values:
+            self._sink_tokens = len(self.past_key_values)
+
     def _embed(self, ids):
         return self.model.get_input_embeddings()(ids.to(self.device)).view(1, -1, self.hidden_size)
 
@@ -315,6 +347,7 @@ class LiveInferForBenchmark:
         self.last_ids = self._prefix_ids_for_next_frame()
         P = int(self.last_ids.shape[1])
         nt = self.frame_num_tokens
+        self._apply_context_window(P + len(frames) * nt)          # (before n0 is read: the frame ends below are offsets into the shortened context)
         x = self._step_input(self.last_ids, frames)
         n0 = len(self.past_key_values) if self.past_key_values else 0
         rows = [P + (j + 1) * nt - 1 for j in range(len(frames))]
@@ -373,6 +406,7 @@ class LiveInferForBenchmark:
         video_time, frame_embeds = self.frame_embeds_queue.popleft()
         scores, _, cache = self._forward_frames([frame_embeds])
         self.past_key_values = cache
+        self._note_first_forward()
         self.frame_idx += 1
         self.num_frames_no_reply += 1
         self.last_role = 'stream'
@@ -383,8 +417,10 @@ class LiveInferForBenchmark:
         query_time, query = self.query_queue.popleft()
         self.last_ids = chat_ids(self.tokenizer, [{'role': 'user', 'content': query}],
                                  add_stream_query_prompt=self.last_role == 'stream', add_stream_prompt=True)
+        self._apply_context_window(int(self.last_ids.shape[1]))
         outputs = self.model(inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values, use_cache=True, return_dict=True)
         self.past_key_values = outputs.past_key_values
+        self._note_first_forward()
         self.forward_calls += 1
         # the reference takes argmax of the last logits here and overwrites it before any use (:254); skipped (lm_head is lazy)
         self.last_ids = self._no_ids()
@@ -424,9 +460,11 @@ class LiveInferForBenchmark:
                 repetition_penalty=self.repetition_penalty, generated_token_ids=self.generated_token_ids)
         return output_ids, past_key_values
 
-    def _generate_response(self):
+    def _generate_response(self, stash_held=False):
         """test/inference.py:257-274."""
         self.last_ids = self._added_stream_generation_ids
+        if getattr(self, 'context_window', 0) > 0 and not stash_held:          # (under a stash the arena may not move: the drop waits for the next forward)
+            self._apply_context_window(int(self.last_ids.shape[1]) + int(self.max_new_tokens or 0))
         self._issue_vit_burst()
         if not self.output_logprobs:
             output_ids, past_key_values = self._native_response()
@@ -504,6 +542,8 @@ class LiveInferForBenchmark:
             chunk = [self.frame_embeds_queue.popleft() for _ in range(k)]
             scores, ends, cache = self._forward_frames([f for _, f in chunk])
             arena_handle = cache
+            if getattr(self, '_sink_tokens', None) is None:
+                self._sink_tokens = len(cache)
             for j in range(k):
                 self.frame_idx += 1
                 self.num_frames_no_reply += 1
@@ -526,7 +566,7 @@ class LiveInferForBenchmark:
                         for item in reversed(chunk[j + 1:]):
                             self.frame_embeds_queue.appendleft(item)
                         self.replayed_frames += k - 1 - j
-                    response = self._generate_response()
+                    response = self._generate_response(stash_held=keep_tail)
                     self.response_token_ids.append(self.last_generated_ids)
                     if self.output_logprobs:
                         self.response_logprobs.append(self.last_generated_logprobs)

@@ -21,8 +21,10 @@ class LiveInferForDemo(LiveInferForBenchmark):
         with self._step_lock:
             self.last_ids = chat_ids(self.tokenizer, [{'role': 'user', 'content': query}],
                                      add_stream_query_prompt=self.last_role == 'stream', add_stream_prompt=True)
+            self._apply_context_window(int(self.last_ids.shape[1]))
             outputs = self.model(inputs_embeds=self._embed(self.last_ids), past_key_values=self.past_key_values, use_cache=True, return_dict=True)
             self.past_key_values = outputs.past_key_values
+            self._note_first_forward()
             self.last_ids = outputs.logits[:, -1:].argmax(dim=-1).cpu()          # (ids live on the host in this driver)
             self.last_role = 'user'
 

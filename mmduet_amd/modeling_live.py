@@ -46,7 +46,7 @@ class _KVArena:
         for i, h in enumerate(pool):
             if lib().mmd_kv_capacity(h) >= int(initial_tokens):
                 pool.pop(i)
-                check(lib().mmd_kv_truncate(h, 0), model._ctx, 'mmd_kv_truncate')
+                check(lib().mmd_stream_reset(h), model._ctx, 'mmd_stream_reset')          # length 0 and position 0 (a recycled arena may have had spans dropped)
                 self.h = h
                 return
         h = C.c_void_p()
@@ -571,6 +571,35 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             self._bind_stream()
             check(lib().mmd_kv_unstash(arena.h), self._ctx, 'mmd_kv_unstash')
         return KVCacheHandle(arena, end)
+
+    def kv_drop(self, handle: KVCacheHandle, start: int, end: int):
+        """Sliding context window: tokens [start, end) leave `handle`'s context; the tokens behind them move down (device move, stream-ordered) and keep the
+        rotary positions they were written with, and whatever is appended next goes on counting from `kv_position`.  -> the handle of the shortened context;
+        every other handle that reached beyond `start` is stale."""
+        if handle.stale:
+            raise RuntimeError('stale KV handle')
+        start, end = int(start), int(end)
+        if not 0 <= start <= end <= handle.length:
+            raise ValueError(f'kv_drop [{start}, {end}) outside the context ({handle.length} tokens)')
+        arena = handle.arena
+        if arena is None or start == end:
+            return handle
+        with self._lock:
+            arena.truncate(handle.length)
+            self._bind_stream()
+            check(lib().mmd_kv_drop(arena.h, start, end), self._ctx, 'mmd_kv_drop')
+            for hd in list(arena.handles):
+                if hd.length > start:
+                    hd.stale = True
+        return KVCacheHandle(arena, handle.length - (end - start))
+
+    def kv_position(self, handle: KVCacheHandle):
+        """The rotary position the next token appended to `handle` gets: its length plus everything `kv_drop` took out of its arena."""
+        if handle is None or handle.arena is None:
+            return 0
+        with self._lock:
+            h = handle.arena.h
+            return handle.length + int(lib().mmd_kv_position(h)) - int(lib().mmd_kv_len(h))
 
     def new_cache(self, initial_tokens=None):
         return KVCacheHandle(_KVArena(self, initial_tokens or self.kv_initial_tokens), 0)
