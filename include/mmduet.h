@@ -29,7 +29,8 @@ extern "C" {
 #define MMD_ENOENT (-2)
 #define MMD_ERANGE (-34)
 #define MMD_EHIP (-5)
-#define MMD_EDOM (-33)         /* a NaN among the logits a token was to be drawn from, or -- under constraints -- no score above -inf */
+#define MMD_EDOM (-33)         /* a NaN among the logits a token was to be taken from -- on EVERY route: plain arg-max, constrained arg-max, draw --, or, under
+                                  constraints, no score above -inf.  No token is returned for that step and none is fed back. */
 
 typedef enum { MMD_F32 = 0, MMD_BF16 = 1 } mmd_dtype;
 /* storage of the decoder's linear-layer weights (q/k/v/o/gate/up/down): MMD_W_FP8_E4M3 = OCP e4m3fn with one fp32 scale per output
@@ -216,7 +217,10 @@ int mmd_frame_step_multi(mmd_ctx* ctx, mmd_stream* const* streams, const int32_t
  *   MMD_SEG_SAMPLE  after the step: lm_head over the segment's last row, repetition penalty over samplers[j]'s list, arg-max (first maximal index) -> tokens_out_host[j]
  *                   and samplers[j]'s token slot.
  * tokens_out_host [n_segs] receives -1 for the other segments; heads as in mmd_frame_step_multi.  ONE stream synchronisation per round (none when nothing is read).
- * At most 32 feed and 32 sampling segments per round. */
+ * At most 32 feed and 32 sampling segments per round.
+ * A NaN among the logits of a sampling segment's row fails the round with MMD_EDOM, whichever way the segment's sampler takes its token (plain arg-max included: the
+ * kernel answers -1 for such a row, never the arg-max of the rest).  The step itself has run: the streams are extended, tokens_out_host holds -1 for that segment, its sampler
+ * has not advanced.  A following round without that sampler runs as usual. */
 typedef struct mmd_sampler mmd_sampler;
 #define MMD_SEG_FEED 1
 #define MMD_SEG_SAMPLE 2
@@ -238,7 +242,10 @@ int mmd_round_multi(mmd_ctx* ctx, mmd_stream* const* streams, const int32_t* seg
 /* replaces fast_greedy_generate (models/modeling_live.py:51-77): feeds prompt_embeds [S,hidden], then up to max_new
  * greedy steps.  prev_ids_host / n_prev: the repetition-penalty list persisted across turns (grown in place, capacity
  * prev_cap); rep_penalty <= 0 disables the penalty (and the list is not updated, like the reference).  EOS is written
- * to out_ids but neither fed back nor added to the list.  out_ids_host int64[max_new]; n_out = tokens written. */
+ * to out_ids but neither fed back nor added to the list.  out_ids_host int64[max_new]; n_out = tokens written.
+ * The arg-max is the first maximal index of pen(l) over the fp32 logits l (-inf everywhere: index 0; +inf: the first +inf).  MMD_EDOM: a NaN among the logits of a step --
+ * wherever it sits, on the penalty list or not; n_out tokens were returned before, the step's token is neither returned nor fed back, and the stream keeps the rows it was
+ * extended by, exactly as mmd_sample_generate leaves it. */
 int mmd_greedy_generate(mmd_ctx* ctx, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty,
                         int64_t* prev_ids_host, int* n_prev, int prev_cap, int64_t* out_ids_host, int max_new, int* n_out);
 
@@ -349,7 +356,8 @@ int mmd_op_sample(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t
                   uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out);
 /* mmd_op_sample with the rows' log-probability records.  greedy != 0: the arg-max with penalty (first maximal index) stands in the draw's place -- temperature, top_k, top_p and
  * the random words are ignored, the scores are pen(l), info_out is not written and may be NULL.  Outputs on the HOST: lp_out_host float[n, 2] = (logprob, sampling_logprob),
- * top_ids_out_host int64[n, top_n], top_lp_out_host float[n, top_n] (0 <= top_n <= 8, else MMD_ERANGE).  Synchronises the stream. */
+ * top_ids_out_host int64[n, top_n], top_lp_out_host float[n, top_n] (0 <= top_n <= 8, else MMD_ERANGE).  Synchronises the stream.  A row with a NaN: token -1 (greedy
+ * too) and NaN records; the call still answers MMD_OK. */
 int mmd_op_sample_logprobs(mmd_ctx* ctx, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
                            uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n, int64_t* tokens_out, float* info_out, float* scores_out,
                            float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host);
@@ -401,6 +409,30 @@ int mmd_op_slab_resid_rmsnorm(mmd_ctx* ctx, const float* slabs, int splits, int 
                               const float* wscale);
 int mmd_op_gemv_chain(mmd_ctx* ctx, int role, const void* X, const void* W, const uint8_t* q8, const float* scale, void* h, const void* gamma, float* ssq, float eps,
                       void* Y, int M, int N, int K, int epi, int max_splits, int* splits_out);
+/* The kernels of the plain greedy token loop (lm_head -> penalty + arg-max -> state advance -> embedding of the winner) on caller-owned device buffers
+ * (tests/test_gpu_greedy.py).  The entries refuse with MMD_EINVAL before anything is launched, synchronise the stream, and go through the launchers and the context scratch
+ * that mmd_greedy_generate and mmd_round_multi use.
+ *
+ * mmd_op_argmax: logits [n, V] fp32; row r's penalty list is entries [prev_off_host[r], prev_off_host[r + 1]) of prev_ids_dev (int64; ids outside [0, V) match no column),
+ * its penalty penalty_host[r] (<= 0: none -- no list and the factor 1, as the generate calls pass it on).  tokens_out int64[n]: the first maximal index of pen(l), -1 for a row
+ * with a NaN.
+ *   form 0  argmax_penalty_kernel + argmax_final_kernel row by row, the list length in the kernel argument (the eager steps of mmd_greedy_generate);
+ *   form 1  the same with the length in a device StepState and 0 in the kernel argument (the captured decode step; the kernel reads the StepState only when penalty != 1);
+ *   form 2  argmax_penalty_multi_kernel + argmax_final_multi_kernel over all n <= 32 rows in ONE launch (mmd_round_multi): row r's token also goes to tok_slots_out[r] (the
+ *           sampler's token slot) and, when its penalty is on, to append_out[r] (the slot behind the sampler's list); a row without penalty leaves append_out[r] alone.
+ *           tok_slots_out / append_out int64[n], ignored (may be NULL) for forms 0 and 1.
+ * Refused: a form outside 0 .. 2, a missing operand, n outside 1 .. 4096 (form 2: 1 .. 32), V < 1, offsets that do not start at 0 or decrease, lists without ids.
+ *
+ * mmd_op_advance_state: ONE launch of advance_state_kernel, no constraints: `token` joins prev_dev[*n_prev] when use_penalty != 0, token != eos_id and *n_prev < prev_cap;
+ * n_ctx and step grow by one either way.  prev_dev int64[>= prev_cap] (device), the three counters in and out on the host.  Refused: *n_prev outside 0 .. prev_cap.
+ *
+ * mmd_op_embed_feed: launch_embed_feed over the context's embedding table: out[rows_host[i], :] = embed[clamp(tok_slots_dev[i], 0, vocab - 1), :] for i < n <= 32; out
+ * [out_rows, hidden] in the context dtype, rows not listed are not written.  Refused: a row index outside [0, out_rows).  (mmd_embed_tokens is embed_kernel, same clamp.) */
+int mmd_op_argmax(mmd_ctx* ctx, int form, const float* logits, int n, int V, const int64_t* prev_ids_dev, const int32_t* prev_off_host, const float* penalty_host,
+                  int64_t* tokens_out, int64_t* tok_slots_out, int64_t* append_out);
+int mmd_op_advance_state(mmd_ctx* ctx, int64_t token, int64_t eos_id, int use_penalty, int64_t* prev_dev, int prev_cap, int* n_prev_inout_host, int64_t* n_ctx_inout_host,
+                         int* step_inout_host);
+int mmd_op_embed_feed(mmd_ctx* ctx, const int64_t* tok_slots_dev, const int32_t* rows_host, int n, int out_rows, void* out);
 /* the first n tokens (n % 64 == 0, n <= mmd_kv_capacity) of one layer of a stream's arena AS STORED: K_out [nkv, n, d] rotated rows, V_out [nkv, n / 64, d, 64] transposed
  * 64-token blocks (token t, dim e of a head at ((t >> 6) * d + e) * 64 + (t & 63)); device buffers in the context dtype.  Synchronises the stream. */
 int mmd_kv_debug_read(mmd_stream* s, int layer, int64_t n, void* K_out, void* V_out);

@@ -126,6 +126,9 @@ _SIGS = {
     'mmd_op_kv_write': (_I, [_VP, _I, _VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I64, _VP, _VP, _VP, _I64, _VP]),
     'mmd_op_slab_resid_rmsnorm': (_I, [_VP, _VP, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _VP]),
     'mmd_op_gemv_chain': (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    'mmd_op_argmax': (_I, [_VP, _I, _VP, _I, _I, _VP, C.POINTER(C.c_int32), C.POINTER(_F), _VP, _VP, _VP]),
+    'mmd_op_advance_state': (_I, [_VP, _I64, _I64, _I, _VP, _I, C.POINTER(_I), C.POINTER(_I64), C.POINTER(_I)]),
+    'mmd_op_embed_feed': (_I, [_VP, _VP, C.POINTER(C.c_int32), _I, _I, _VP]),
     'mmd_kv_debug_read': (_I, [_VP, _I, _I64, _VP, _VP]),
     'mmd_op_attention': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I64, _I64, _I, _I]),
     'mmd_op_attention_bench': (_I, [_VP, _I, _I, _I, _I, _I64, _I, _I, C.POINTER(_F)]),
@@ -166,6 +169,6 @@ def check(rc, ctx=None, what=''):
     if rc == 0:
         return
     msg = lib().mmd_last_error(ctx)
-    if rc == MMD_EDOM:          # a NaN among the logits a token was to be drawn from: never turned into an index
+    if rc == MMD_EDOM:          # a NaN among the logits a token was to be taken from -- drawn or arg-max, every native call alike: never turned into an index
         raise ValueError(f'{what or "libmmduet_hip"}: {msg.decode() if msg else "NaN in the logits"}')
     raise MmduetError(f'{what or "libmmduet_hip"} failed ({rc}): {msg.decode() if msg else "?"}')

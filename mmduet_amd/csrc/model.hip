@@ -1825,7 +1825,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
     if (n_sample && !c->round_logits) {
         rc = dev_alloc(c, (void**)&c->round_logits, (size_t)MMD_ROUND_MAX_SAMPLERS * V * sizeof(float), false); if (rc) return rc;
         rc = dev_alloc(c, &c->round_hidden, (size_t)MMD_ROUND_MAX_SAMPLERS * H * e); if (rc) return rc;
-        rc = dev_alloc(c, &c->round_scratch, sample_batch_scratch_bytes()); if (rc) return rc;
+        if (!c->round_scratch) { rc = dev_alloc(c, &c->round_scratch, sample_batch_scratch_bytes()); if (rc) return rc; }          // (mmd_op_argmax may have brought it)
         rc = dev_alloc(c, (void**)&c->round_toks_dev, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)); if (rc) return rc;
         HIPCHK(c, hipHostMalloc((void**)&c->round_toks_host, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)));
     }
@@ -1866,7 +1866,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         mmd_sampler* sp = samplers[sample_seg[i]];
         tokens_out_host[sample_seg[i]] = tok;
         if (i >= n_greedy) sp->offset += 1;
-        if (i >= n_plain && tok < 0) FAIL(c, MMD_EDOM, "segment %d: a NaN among the logits, or every score is -inf: no token drawn", sample_seg[i]);
+        if (tok < 0) FAIL(c, MMD_EDOM, "segment %d: a NaN among the logits, or every score is -inf: no token drawn", sample_seg[i]);
         sp->step += 1;
         const bool is_eos = (sp->cons.on && sp->cons.n_eos > 0) ? std::find(sp->cons.eos, sp->cons.eos + sp->cons.n_eos, tok) != sp->cons.eos + sp->cons.n_eos : tok == sp->eos;
         if (sp->penalty > 0.f && !is_eos && sp->n_prev < sp->prev_cap) sp->n_prev += 1;          // (EOS is neither fed back nor penalised: models/modeling_live.py:66-72)
@@ -2129,7 +2129,8 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         HIPCHK(c, hipStreamSynchronize(st));
         *tok = c->tok_host[0];
         if (samp) ++*samp->offset_inout;
-        if ((samp || cons_on) && *tok < 0) FAIL(c, MMD_EDOM, cons_on ? "NaN in the logits, or every score is -inf under the constraints: no token drawn" : "NaN in the logits: no token drawn");
+        // every route: the plain arg-max answers -1 for a row with a NaN too (argmax_final_kernel)
+        if (*tok < 0) FAIL(c, MMD_EDOM, cons_on ? "NaN in the logits, or every score is -inf under the constraints: no token drawn" : "NaN in the logits: no token drawn");
         return MMD_OK;
     };
     // step 0: the prompt (eager)
@@ -2703,6 +2704,80 @@ extern "C" int mmd_op_gemv_chain(mmd_ctx* c, int role, const void* X, const void
     dev_free(c, Wp); if (Wp8) dev_free(c, Wp8);
     if (e != hipSuccess) FAIL(c, MMD_EHIP, "gemv_chain: launch failed: %s", hipGetErrorString(e));
     if (splits_out) *splits_out = role == GEMV_CONSUMER && epi == EPI_NONE ? splits : 0;
+    return MMD_OK;
+}
+// the kernels of the plain greedy token loop on caller-owned buffers (tests/test_gpu_greedy.py): the production launchers over the context's own scratch, nothing else.
+// What is refused is refused before any launch.
+extern "C" int mmd_op_argmax(mmd_ctx* c, int form, const float* logits, int n, int V, const int64_t* prev_ids_dev, const int32_t* prev_off_host, const float* penalty_host,
+                             int64_t* tokens_out, int64_t* tok_slots_out, int64_t* append_out) {
+    if (!c) return MMD_EINVAL;
+    if (form < 0 || form > 2) FAIL(c, MMD_EINVAL, "argmax: form %d (0 list length in the argument, 1 in a StepState, 2 the multi-row launch)", form);
+    if (!logits || !tokens_out || !prev_off_host || !penalty_host || n < 1 || n > 4096 || V < 1) FAIL(c, MMD_EINVAL, "argmax: missing operand, or n %d outside 1 .. 4096, or V %d < 1", n, V);
+    if (form == 2 && (n > MMD_ROUND_MAX_SAMPLERS || !tok_slots_out || !append_out)) FAIL(c, MMD_EINVAL, "argmax: form 2 takes at most %d rows, token slots and append slots", MMD_ROUND_MAX_SAMPLERS);
+    if (prev_off_host[0] != 0) FAIL(c, MMD_EINVAL, "argmax: the list offsets start at 0");
+    for (int r = 0; r < n; ++r) if (prev_off_host[r + 1] < prev_off_host[r]) FAIL(c, MMD_EINVAL, "argmax: the list offsets decrease at row %d", r);
+    if (prev_off_host[n] > 0 && !prev_ids_dev) FAIL(c, MMD_EINVAL, "argmax: lists without ids");
+    hipSetDevice(c->device);
+    hipStream_t st = c->stream;
+    // per row what generate_impl / mmd_round_multi hand on: penalty off -> no list and the factor 1
+    auto len_of = [&](int r) { return penalty_host[r] > 0.f ? prev_off_host[r + 1] - prev_off_host[r] : 0; };
+    auto pen_of = [&](int r) { return penalty_host[r] > 0.f ? penalty_host[r] : 1.f; };
+    StepState* dyn = nullptr;
+    hipError_t e = hipSuccess;
+    if (form == 1) {
+        std::vector<StepState> hs((size_t)n);
+        for (int r = 0; r < n; ++r) { memset(&hs[r], 0, sizeof(StepState)); hs[r].n_prev = len_of(r); }
+        HIPCHK(c, hipMalloc((void**)&dyn, sizeof(StepState) * n));
+        e = hipMemcpy(dyn, hs.data(), sizeof(StepState) * n, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess && form == 2) {
+        if (!c->round_scratch) { int rc = dev_alloc(c, &c->round_scratch, sample_batch_scratch_bytes()); if (rc) return rc; }
+        SampleBatch b{};
+        for (int r = 0; r < n; ++r) {
+            b.prev[r] = prev_ids_dev + prev_off_host[r]; b.n_prev[r] = len_of(r); b.penalty[r] = pen_of(r);
+            b.tok[r] = tok_slots_out + r; b.append[r] = penalty_host[r] > 0.f ? append_out + r : nullptr;
+        }
+        e = launch_sample_batch(logits, V, b, n, tokens_out, c->round_scratch, st);
+    } else if (e == hipSuccess) {
+        for (int r = 0; r < n && e == hipSuccess; ++r)          // (one row after the other through the one scratch: same stream)
+            e = launch_argmax_penalty(logits + (size_t)r * V, V, prev_ids_dev + prev_off_host[r], form == 1 ? 0 : len_of(r), pen_of(r), tokens_out + r, st, dyn ? dyn + r : nullptr, c->argmax_scratch);
+    }
+    hipStreamSynchronize(st);
+    if (dyn) hipFree(dyn);
+    if (e != hipSuccess) FAIL(c, MMD_EHIP, "argmax: form %d failed: %s", form, hipGetErrorString(e));
+    return MMD_OK;
+}
+// one launch of advance_state_kernel without constraints on a StepState of its own: the token and the state go in and come out on the host, the list is the caller's
+extern "C" int mmd_op_advance_state(mmd_ctx* c, int64_t token, int64_t eos_id, int use_penalty, int64_t* prev_dev, int prev_cap, int* n_prev_inout_host, int64_t* n_ctx_inout_host,
+                                    int* step_inout_host) {
+    if (!c) return MMD_EINVAL;
+    if (!prev_dev || !n_prev_inout_host || !n_ctx_inout_host || !step_inout_host) FAIL(c, MMD_EINVAL, "advance_state: missing operand");
+    if (prev_cap < 0 || *n_prev_inout_host < 0 || *n_prev_inout_host > prev_cap) FAIL(c, MMD_EINVAL, "advance_state: list length %d outside 0 .. prev_cap %d", *n_prev_inout_host, prev_cap);
+    hipSetDevice(c->device);
+    struct { StepState s; int64_t tok; } h;
+    memset(&h, 0, sizeof(h));
+    h.s.n_prev = *n_prev_inout_host; h.s.n_ctx = *n_ctx_inout_host; h.s.step = *step_inout_host; h.tok = token;
+    char* dev = nullptr;
+    HIPCHK(c, hipMalloc((void**)&dev, sizeof(h)));
+    hipError_t e = hipMemcpy(dev, &h, sizeof(h), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_advance_state((StepState*)dev, (const int64_t*)(dev + offsetof(decltype(h), tok)), prev_dev, prev_cap, eos_id, use_penalty ? 1 : 0, c->stream, nullptr);
+    hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(&h, dev, sizeof(h), hipMemcpyDeviceToHost);
+    hipFree(dev);
+    if (e != hipSuccess) FAIL(c, MMD_EHIP, "advance_state failed: %s", hipGetErrorString(e));
+    *n_prev_inout_host = h.s.n_prev; *n_ctx_inout_host = h.s.n_ctx; *step_inout_host = h.s.step;
+    return MMD_OK;
+}
+// launch_embed_feed over the context's embedding table: out[rows_host[i], :] = embed[clamp(tok_slots_dev[i]), :], out [out_rows, hidden] in the context dtype
+extern "C" int mmd_op_embed_feed(mmd_ctx* c, const int64_t* tok_slots_dev, const int32_t* rows_host, int n, int out_rows, void* out) {
+    NEED_FINAL(c);
+    if (!tok_slots_dev || !rows_host || !out || n < 1 || n > MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_EINVAL, "embed_feed: missing operand, or n %d outside 1 .. %d", n, MMD_ROUND_MAX_SAMPLERS);
+    for (int i = 0; i < n; ++i) if (rows_host[i] < 0 || rows_host[i] >= out_rows) FAIL(c, MMD_EINVAL, "embed_feed: row %d outside the %d rows of the output", rows_host[i], out_rows);
+    FeedBatch f{};
+    for (int i = 0; i < n; ++i) { f.tok[i] = tok_slots_dev + i; f.row[i] = rows_host[i]; }
+    const hipError_t e = launch_embed_feed(c->cfg.dtype, c->embed, f, n, c->cfg.hidden_size, c->cfg.vocab_size, out, c->stream);
+    hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) FAIL(c, MMD_EHIP, "embed_feed failed: %s", hipGetErrorString(e));
     return MMD_OK;
 }
 extern "C" int mmd_op_rope_append(mmd_ctx* c, void* qkv, int S, int nh, int nkv, int d, float theta, int64_t pos0, void* q_out, void* Kc, void* Vc, int64_t cap) {

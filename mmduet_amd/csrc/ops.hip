@@ -709,9 +709,12 @@ hipError_t launch_heads(int dtype, const void* hidden, int64_t ldh, const int32_
 // Single block; V up to a few 100k.
 // ---------------------------------------------------------------------------------------------------------------
 // two stages (V = 152064: one block would crawl through 600 KB alone): ARGMAX_BLOCKS blocks reduce their slice to a
-// (value, index) candidate, one block picks the winner; ties -> smallest index, like torch.argmax
+// (value, index) candidate, one block picks the winner; ties -> smallest index, like torch.argmax; a NaN in the row -> -1
 #define ARGMAX_BLOCKS 64
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+// A NaN beats every number and is never displaced (v != v && bv == bv; a NaN against a NaN keeps the one held): a row's winner is a NaN exactly when one of its raw logits is
+// (pen(NaN) is NaN, and a positive finite penalty makes no NaN of a number).  The final kernels then write -1, which the host turns into MMD_EDOM like the other routes --
+// with the plain `v > bv` a NaN lost every comparison and the row answered with the arg-max of the rest, a row of NaN with 0x7fffffff.  Rows without NaN: the same bits as before.
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi) || (v != v && bv == bv); }
 
 __global__ __launch_bounds__(256) void argmax_penalty_kernel(const float* __restrict__ logits, int V, const int64_t* __restrict__ prev, int n_prev, float penalty,
                                                              float* __restrict__ cand_v, int* __restrict__ cand_i, const StepState* __restrict__ dyn) {
@@ -751,7 +754,7 @@ __global__ void argmax_final_kernel(const float* __restrict__ cand_v, const int*
         float ov = __shfl_xor(best, o, 64); int oi = __shfl_xor(bi, o, 64);
         if (better(ov, oi, best, bi)) { best = ov; bi = oi; }
     }
-    if (lane == 0) *out_id = bi;
+    if (lane == 0) *out_id = best != best ? -1 : bi;          // a NaN in the row: no token
 }
 hipError_t launch_argmax_penalty(const float* logits, int V, const int64_t* prev_ids_dev, int n_prev, float penalty, int64_t* out_id, hipStream_t st,
                                  const StepState* dyn, void* scratch) {
@@ -804,8 +807,9 @@ __global__ void argmax_final_multi_kernel(const float* __restrict__ cand_v, cons
         if (better(ov, oi, best, bi)) { best = ov; bi = oi; }
     }
     if (lane == 0) {
-        *b.tok[r] = bi; toks_out[r] = bi;
-        if (b.append[r]) *b.append[r] = bi;
+        const int64_t t = best != best ? -1 : bi;          // a NaN in the row: no token (the host fails the round; the append slot lies beyond the list's count)
+        *b.tok[r] = t; toks_out[r] = t;
+        if (b.append[r]) *b.append[r] = t;
     }
 }
 hipError_t launch_sample_batch(const float* logits, int V, const SampleBatch& b, int n, int64_t* toks_out_dev, void* scratch, hipStream_t st) {

@@ -914,6 +914,7 @@ class VideoHeadLiveLlavaQwenForCausalLM:
 
     def greedy_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None,
                         generated_token_ids=None):
+        """mmd_greedy_generate: -> (ids, cache).  NaN logits raise ValueError, as in `sample_generate`: no id is made up for such a step."""
         return self._native_generate(inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty, generated_token_ids)[:2]
 
     def sample_generate(self, inputs_embeds, past_key_values, eos_token_id, max_new_tokens, repetition_penalty=None, generated_token_ids=None,

@@ -41,6 +41,13 @@ class RawOps:
         self.m = VideoHeadLiveLlavaQwenForCausalLM(product_config(cfgd), torch_dtype=dtype, max_vit_batch=2, max_step_tokens=max_step_tokens, kv_initial_tokens=256)
         self.ctx, self.dtype, self.dev = self.m._ctx, dtype, self.m.device
 
+    @classmethod
+    def around(cls, model):
+        """The raw calls on a model that exists already -- one with its weights loaded: mmd_op_embed_feed reads the context's embedding table."""
+        self = cls.__new__(cls)
+        self.m, self.ctx, self.dtype, self.dev = model, model._ctx, model.dtype, model.device
+        return self
+
     def t(self, x):
         return x.to(device=self.dev, dtype=self.dtype).contiguous()
 
@@ -162,6 +169,35 @@ class RawOps:
         rc = lib().mmd_op_gemv_chain(self.ctx, role, _ptr(X), _ptr(W), _ptr(q8), _ptr(scale), _ptr(h), _ptr(gamma), _ptr(ssq), eps, _ptr(Y), M, N, K, EPI[epi], max_splits, C.byref(n))
         torch.cuda.synchronize()
         return rc, n.value
+
+    # ---- the kernels of the greedy token loop (tests/test_gpu_greedy.py): every call returns the native code, refusals are part of what is tested ----
+    def argmax(self, form, logits, prev_ids, prev_off, penalties, tokens_out, tok_slots_out=None, append_out=None, n=None, V=None):
+        """mmd_op_argmax on caller-owned device buffers: logits [n, V] fp32, prev_ids int64 (all lists back to back, or None), prev_off a list of n + 1 offsets, penalties a
+        list of n floats (<= 0: none); tokens_out / tok_slots_out / append_out int64 [n] (the last two for form 2)."""
+        n = logits.shape[0] if n is None else n
+        V = logits.shape[1] if V is None else V
+        off = (C.c_int32 * len(prev_off))(*prev_off)
+        pen = (C.c_float * max(1, len(penalties)))(*penalties)
+        self.m._bind_stream()
+        rc = lib().mmd_op_argmax(self.ctx, form, _ptr(logits), n, V, _ptr(prev_ids), off, pen, _ptr(tokens_out), _ptr(tok_slots_out), _ptr(append_out))
+        torch.cuda.synchronize()
+        return rc
+
+    def advance_state(self, token, eos, use_penalty, prev, prev_cap, n_prev, n_ctx, step):
+        """mmd_op_advance_state: prev a device int64 buffer of at least prev_cap slots.  -> (return code, n_prev, n_ctx, step afterwards)"""
+        a, b, c = C.c_int(n_prev), C.c_int64(n_ctx), C.c_int(step)
+        self.m._bind_stream()
+        rc = lib().mmd_op_advance_state(self.ctx, int(token), int(eos), int(use_penalty), _ptr(prev), prev_cap, C.byref(a), C.byref(b), C.byref(c))
+        torch.cuda.synchronize()
+        return rc, a.value, b.value, c.value
+
+    def embed_feed(self, tok_slots, rows, out, out_rows=None):
+        """mmd_op_embed_feed: tok_slots device int64 [n], rows a list of n row indices of out [out_rows, H]"""
+        r = (C.c_int32 * max(1, len(rows)))(*rows)
+        self.m._bind_stream()
+        rc = lib().mmd_op_embed_feed(self.ctx, _ptr(tok_slots), r, len(rows), out.shape[0] if out_rows is None else out_rows, _ptr(out))
+        torch.cuda.synchronize()
+        return rc
 
     def attention_last_form(self):
         f = (C.c_int * 2)()

@@ -145,6 +145,8 @@ def test_nan_rows_and_argument_checks(model):
         toks, info, _, lp, top_ids, top_lp = model.sample_logprob_op(lg, r=words(5, 3), top_n=2, **kw)
         assert torch.isnan(lp[2]).all() and torch.isnan(top_lp[2]).all()
         assert torch.isfinite(lp[[0, 1, 3, 4]]).all() and torch.isfinite(top_lp[[0, 1, 3, 4]]).all()
+        toks = toks.cpu()
+        assert toks[2] == -1 and (toks[[0, 1, 3, 4]] >= 0).all()          # the arg-max too: no index is made up for a row with a NaN
     with pytest.raises(Exception):
         model.sample_logprob_op(lg, top_n=9)
     with pytest.raises(Exception):
