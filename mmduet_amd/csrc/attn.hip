@@ -14,6 +14,9 @@
 // attn_simple_kernel (any dtype / head_dim): one wave per (row, head); the fp32 parity path and the cross-check of
 //   the MFMA kernel.
 // softmax statistics are fp32; P is rounded to the storage type before P.V (flash / sdpa semantics).
+//
+// Which of the kernels below runs, over which grid, with how many key splits and which merge behind it is decided in attn_plan.h (attn_plan / attn_plan_decode_multi: pure host
+// functions, tested without a GPU against tests/attn_regimes.py).  The launchers at the end of this file only launch what the plan says.
 #include "common.h"
 #include <cstdlib>
 
@@ -35,8 +38,6 @@ struct AttnP {
     int nseg;           // > 0 (decode form only): grid.x = nseg independent streams of S rows each (consecutive rows of q / out / slabs / rope_tab), stream j's context, capacity
                         // and arena base in dyn[j] (AttnArgs::segs); partials [seg][split][rows]
 };
-
-static thread_local int g_last_form[2] = {0, 0};          // (diagnostic only: which form the most recent launch took, mmd_op_attention_last_form)
 
 __device__ __forceinline__ long long v_off(const AttnP& p, long long tok, int e) {
     return p.v_tr ? (((tok >> 6) * p.d + e) << 6) + (tok & 63) : tok * p.v_ts + e;
@@ -951,134 +952,6 @@ __global__ __launch_bounds__(256) void attn_combine128_rows_kernel(AttnP p, int 
 #include "attn_w1.h"
 #include "attn_chunk.h"
 
-// attn_gqa128_w1_kernel (attn_w1.h): `qblocks` row blocks of block_rows (multiple of 16, <= 256) per kv head, `splits` key splits (the caller's choice)
-static hipError_t launch_gqa128_w1(AttnP& p, const AttnArgs& a, hipStream_t st, int qblocks, int block_rows, int splits_hint) {
-    const int G = a.nh / a.nkv, rows_total = a.S * G;
-    const long long n_tot = a.n_ctx + a.S;
-    const int tiles = cdiv(n_tot, 64);
-    int splits = splits_hint < 1 ? 1 : splits_hint;
-    if (!a.ws) splits = 1;
-    if (splits > tiles) splits = tiles;
-    if (splits > 64) splits = 64;
-    while (splits > 1 && (size_t)splits * a.nkv * rows_total * (128 + 2) * sizeof(float) > a.ws_bytes) --splits;
-    const int per = cdiv(tiles, splits) * 64;
-    splits = cdiv(n_tot, per);
-    p.splits = splits; p.kv_per_split = per; p.block_rows = block_rows;
-    const int nrows_all = a.nkv * rows_total;
-    p.ws_o = a.ws;
-    p.ws_ml = a.ws ? a.ws + (size_t)splits * nrows_all * 128 : nullptr;
-    static bool attr_set[64] = {};
-    int dev = 0; hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_gqa128_w1_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((attn_gqa128_w1_kernel<2, 8>), dim3(qblocks, a.nkv, splits), dim3(512), 4 * 32768, st, p);
-    if (splits > 1) hipLaunchKernelGGL(attn_combine128_kernel, dim3(cdiv(nrows_all, 4)), dim3(256), 0, st, p, nrows_all);
-    return hipGetLastError();
-}
-// geometry for `rows_total` stacked rows per kv head: the fewest row blocks (<= 256 rows each), balanced in whole 16-row tiles; key splits fill the chip
-// (one block per CU) -- but never below 2 tiles per split.
-static hipError_t launch_gqa128_w1_auto(AttnP& p, const AttnArgs& a, hipStream_t st) {
-    const int G = a.nh / a.nkv, rows_total = a.S * G;
-    const int row_tiles = cdiv(rows_total, 16);
-    const int qblocks = cdiv(row_tiles, 16);
-    const int block_rows = cdiv(row_tiles, qblocks) * 16;
-    const int tiles = cdiv(a.n_ctx + a.S, 64);
-    // key splits by the cost model of launch_gqa128 (unit: one key tile of one resident block): rounds of 256 blocks, ~2 tiles of prologue / epilogue per block,
-    // and the merge reads splits x rows x 520 B
-    const int blocks = qblocks * a.nkv;
-    const double rows_all = (double)a.nkv * rows_total;
-    int maxs = tiles / 2; if (maxs < 1) maxs = 1; if (maxs > 64) maxs = 64;
-    int splits = 1; double best = 1e30;
-    for (int sp = 1; sp <= maxs; ++sp) {
-        const double rounds = (double)cdiv((long long)blocks * sp, 256);
-        const double cost = rounds * ((double)cdiv(tiles, sp) + 2.0) + (sp > 1 ? sp * rows_all * 6.7e-5 + 1.5 : 0.0);
-        if (cost < best - 1e-9) { best = cost; splits = sp; }
-    }
-    return launch_gqa128_w1(p, a, st, qblocks, block_rows, splits);
-}
-
-template <int RT>
-static hipError_t launch_gqa128(AttnP& p, const AttnArgs& a, hipStream_t st) {
-    const int G = a.nh / a.nkv, rows_total = a.S * G;
-    // chunks (>= 1024 rows per kv head): 256-row blocks, one per CU, four-slot ring
-    const bool chunk8 = RT == 2 && rows_total >= 1024;
-    const int qblocks = cdiv(rows_total, chunk8 ? 256 : 64 * RT);
-    const int resident = chunk8 ? 256 : 512;                       // blocks the chip holds at once
-    const long long n_tot = a.n_ctx + a.S;
-    const int blocks = qblocks * a.nkv;
-    const int tiles = cdiv(n_tot, 64);
-    int splits = 1;
-    if (a.dyn) {
-        splits = a.dyn_splits;                                     // fixed grid under graph replay; empty splits write (m = -inf, l = 0)
-    } else if (rows_total <= 16 && a.ws) {
-        splits = 64;                                               // decode: same key ranges as the graph-replayed form -> identical bits
-        if (splits > tiles) splits = tiles;
-    } else if (a.ws) {
-        // split-KV choice by a small cost model (units: one key tile of one block with two blocks resident per CU, ~2.6 us): the grid
-        // runs in rounds of 512 resident blocks, a block costs its tiles plus ~2 tiles of prologue, and the merge kernel reads
-        // splits x rows x 520 B.  Measured against it at S = 49 / 392 / 1274, n = 15 k: picks 42 / 5 / 7 splits (33 / 152 / 440 us; the
-        // old fixed target of 576 blocks gave 42 / 202 / 485 us).
-        const double rows_all = (double)a.nkv * rows_total;
-        int maxs = tiles / 2; if (maxs < 1) maxs = 1; if (maxs > 64) maxs = 64;
-        while (maxs > 1 && (size_t)maxs * a.nkv * rows_total * (128 + 2) * sizeof(float) > a.ws_bytes) --maxs;
-        double best = 1e30;
-        for (int sp = 1; sp <= maxs; ++sp) {
-            const double rounds = (double)cdiv((long long)blocks * sp, resident);          // (a 256-row block's tile costs about what two resident 128-row blocks' tiles do: swept 1.0 .. 2.6, flat)
-            const double cost = rounds * ((double)cdiv(tiles, sp) + 2.0) + (sp > 1 ? sp * rows_all * 6.7e-5 + 1.5 : 0.0);
-            if (cost < best - 1e-9) { best = cost; splits = sp; }
-        }
-    }
-    if constexpr (RT == 2) {
-        // chunks: the contiguous (stream-K) decomposition of attn_chunk.h where the (unit, key split) grid is a bad fit -- it needs splits to fill the chip (each split is one more
-        // fp32 partial per row) or leaves a fifth of it idle -- and a block's range is long enough to carry its per-segment costs (>= 14 tiles; 40+ units).  Measured against
-        // the grid form over S = 147 .. 1911, 0 .. 30 k keys (profiles/r05_attention_chunk.md): 1.04 - 1.39 x where this rule takes it, the grid form elsewhere.
-        if (chunk8 && a.variant == 0 && !a.dyn && a.ws && blocks >= 40) {
-            const double eff = (double)blocks * splits / ((double)cdiv((long long)blocks * splits, resident) * resident);
-            if (chunk_tiles_total(a) / 256 >= 14 && !(splits == 1 && eff >= 0.8)) {
-                const hipError_t e = launch_gqa128_chunk(p, a, st);
-                if (e == hipSuccess) { g_last_form[0] = 8; return e; }
-                (void)hipGetLastError();
-            }
-        }
-    }
-    int per = cdiv(tiles, splits) * 64;
-    if (!a.dyn) splits = cdiv(n_tot, per);
-    p.splits = splits; p.kv_per_split = per;
-    const int nrows_all = a.nkv * rows_total;
-    p.ws_o = a.ws;
-    p.ws_ml = a.ws ? a.ws + (size_t)splits * nrows_all * 128 : nullptr;
-    // decode geometry (one query block per kv head, at most one block per CU): the four-slot ring; MMDUET_ATTN_DECODE_RING=0 keeps the two-slot form (A/B switch)
-    static const bool ring_off = getenv("MMDUET_ATTN_DECODE_RING") && atoi(getenv("MMDUET_ATTN_DECODE_RING")) == 0;
-    if (RT == 1 && qblocks == 1 && a.nkv * splits <= 256 && rows_total <= 16 && !ring_off) {
-        static bool attr_set[64] = {};
-        int dev = 0; hipGetDevice(&dev);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_gqa128_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
-            if (e != hipSuccess) return e;
-            attr_set[dev] = true;
-        }
-        hipLaunchKernelGGL((attn_gqa128_kernel<1, 4>), dim3(qblocks, a.nkv, splits), dim3(256), 4 * 32768, st, p);
-    } else if (chunk8) {
-        static bool attr8_set[64] = {};
-        int dev = 0; hipGetDevice(&dev);
-        if (dev >= 0 && dev < 64 && !attr8_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)attn_gqa128_kernel<2, 4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
-            if (e != hipSuccess) return e;
-            attr8_set[dev] = true;
-        }
-        hipLaunchKernelGGL((attn_gqa128_kernel<2, 4, 8>), dim3(qblocks, a.nkv, splits), dim3(512), 4 * 32768, st, p);
-    } else
-        hipLaunchKernelGGL((attn_gqa128_kernel<RT>), dim3(qblocks, a.nkv, splits), dim3(256), 2 * 32768, st, p);
-    if (splits > 1) {
-        if (nrows_all <= 64 && splits <= 64) hipLaunchKernelGGL(attn_combine128_rows_kernel, dim3(nrows_all), dim3(256), 0, st, p, nrows_all);
-        else hipLaunchKernelGGL(attn_combine128_kernel, dim3(cdiv(nrows_all, 4)), dim3(256), 0, st, p, nrows_all);
-    }
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // attn_rowmajor_kernel: MHSA over token-major K/V rows (the fused SigLIP qkv buffer; head_dim 72 -> 96 for QK^T, 80 for
 // P.V).  Same register-resident softmax pipeline as attn_gqa128_kernel; the V^T operand comes from a ROW-MAJOR V tile via
@@ -1534,163 +1407,89 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
     }
 }
 
-template <int NC, int DVT, bool EXACT = false>
-static hipError_t launch_rowmajor(AttnP& p, const AttnArgs& a, hipStream_t st, bool f16 = false) {
-    p.splits = 1; p.kv_per_split = 0;
-    if (f16) hipLaunchKernelGGL((attn_rowmajor_kernel<NC, DVT, true, EXACT>), dim3(cdiv(a.S, 128), a.nh, a.batch), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((attn_rowmajor_kernel<NC, DVT, false, EXACT>), dim3(cdiv(a.S, 128), a.nh, a.batch), dim3(256), 0, st, p);
-    return hipGetLastError();
+// ------------------------------------------------------------------------------------------------------------------
+// Launchers: attn_plan.h decides, the code below maps the plan's integers to instantiations and launches.
+static const AttnTuning& attn_tuning() {          // the process's AttnTuning: read from the environment once
+    static const AttnTuning tune = [] {
+        AttnTuning t;
+        if (const char* s = getenv("MMDUET_ATTN_DECODE_RING")) t.decode_ring = atoi(s) != 0;
+        if (const char* s = getenv("MMDUET_VIT_ATTN_RING")) t.vit_ring = atoi(s) != 0;
+        return t; }();
+    return tune;
 }
-
-template <int DP>
-static hipError_t launch_mfma(AttnP& p, const AttnArgs& a, hipStream_t st) {
-    int G = a.nh / a.nkv;
-    int rows_total = a.S * G;
-    int qtiles = cdiv(rows_total, 64);
-    int by = a.nkv * a.batch;
-    long long n_tot = a.n_ctx + a.S;
-    int blocks = qtiles * by;
-    int splits = 1;
-    if (blocks < 256) {
-        int want = cdiv(512, blocks);
-        int maxs = (int)(n_tot / 256); if (maxs < 1) maxs = 1;
-        splits = want < maxs ? want : maxs;
-        if (splits > 64) splits = 64;
-        if (a.ws == nullptr) splits = 1;
-        while (splits > 1 && (size_t)splits * by * rows_total * (DP + 2) * sizeof(float) > a.ws_bytes) --splits;
+// more dynamic LDS than a kernel gets by default: raise KERNEL's limit once per device
+template <auto KERNEL>
+static hipError_t ensure_dyn_lds(int bytes) {
+    static bool attr_set[64] = {};
+    int dev = 0; hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || attr_set[dev]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    attr_set[dev] = e == hipSuccess;
+    return e;
+}
+static hipError_t launch_plan(const AttnPlan& pl, AttnP& p, const AttnArgs& a, hipStream_t st) {
+    if (a.plan_out) { a.plan_out[0] = pl.valid() ? pl.form : 0; a.plan_out[1] = pl.valid() ? pl.splits : 1; }
+    if (!pl.valid()) return hipErrorInvalidValue;
+    p.splits = pl.splits; p.kv_per_split = pl.kv_per_split; p.block_rows = pl.block_rows;
+    if (pl.ws_ml_off >= 0 && a.ws) { p.ws_o = a.ws; p.ws_ml = a.ws + pl.ws_ml_off; }
+    const dim3 grid(pl.gx, pl.gy, pl.gz), threads(pl.threads), mgrid(pl.merge_gx);
+#define ATTN_GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, threads, pl.lds, st, p)
+#define ATTN_GO_RING(...) do { const hipError_t e_ = ensure_dyn_lds<__VA_ARGS__>(pl.lds); if (e_ != hipSuccess) return e_; ATTN_GO(__VA_ARGS__); } while (0)
+#define ATTN_GO_ROWMAJOR(NC, DVT, EXACT) do { if (pl.f16) ATTN_GO(attn_rowmajor_kernel<NC, DVT, true, EXACT>); else ATTN_GO(attn_rowmajor_kernel<NC, DVT, false, EXACT>); } while (0)
+#define ATTN_GO_MFMA(DP) do { ATTN_GO(attn_mfma_kernel<DP>); if (pl.merge == ATTN_MERGE_GENERIC) hipLaunchKernelGGL((attn_combine_kernel<DP>), mgrid, dim3(64), 0, st, p, pl.merge_rows); } while (0)
+    switch (pl.kernel) {
+    case ATTN_K_SIMPLE: if (pl.f32) ATTN_GO(attn_simple_kernel<float>); else ATTN_GO(attn_simple_kernel<bf16_t>); break;
+    case ATTN_K_MFMA: if (pl.dp == 32) ATTN_GO_MFMA(32); else if (pl.dp == 64) ATTN_GO_MFMA(64); else if (pl.dp == 96) ATTN_GO_MFMA(96); else ATTN_GO_MFMA(128); break;
+    case ATTN_K_ROWMAJOR:
+        if (pl.nc == 1) ATTN_GO_ROWMAJOR(1, 2, false); else if (pl.nc == 2) ATTN_GO_ROWMAJOR(2, 4, false); else if (pl.exact) ATTN_GO_ROWMAJOR(3, 5, true);
+        else if (pl.nc == 3) ATTN_GO_ROWMAJOR(3, 6, false); else ATTN_GO_ROWMAJOR(4, 8, false);
+        break;
+    case ATTN_K_D72_RING: if (pl.f16) ATTN_GO(attn_d72_ring_kernel<true>); else ATTN_GO(attn_d72_ring_kernel<false>); break;
+    case ATTN_K_GQA128:
+        if (pl.nslot == 4 && pl.waves == 4) ATTN_GO_RING(attn_gqa128_kernel<1, 4>);
+        else if (pl.waves == 8) ATTN_GO_RING(attn_gqa128_kernel<2, 4, 8>);
+        else if (pl.rt == 1) ATTN_GO(attn_gqa128_kernel<1>); else ATTN_GO(attn_gqa128_kernel<2>);
+        break;
+    case ATTN_K_GQA128_W1: ATTN_GO_RING(attn_gqa128_w1_kernel<2, 8>); break;
+    case ATTN_K_GQA128_CHUNK: {
+        const hipError_t e = ensure_dyn_lds<attn_gqa128_chunk_kernel>(pl.lds); if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(attn_gqa128_chunk_kernel, grid, threads, pl.lds, st, p, pl.tab);
+        break; }
+    default: return hipErrorInvalidValue;
     }
-    int per = (int)round_up(cdiv(n_tot, splits), 32);
-    splits = cdiv(n_tot, per);
-    p.splits = splits; p.kv_per_split = per;
-    int nrows_all = by * rows_total;
-    p.ws_o = a.ws;
-    p.ws_ml = a.ws ? a.ws + (size_t)splits * nrows_all * DP : nullptr;
-    hipLaunchKernelGGL((attn_mfma_kernel<DP>), dim3(qtiles, by, splits), dim3(256), 0, st, p);
-    if (splits > 1) hipLaunchKernelGGL((attn_combine_kernel<DP>), dim3(nrows_all), dim3(64), 0, st, p, nrows_all);
+#undef ATTN_GO_MFMA
+#undef ATTN_GO_ROWMAJOR
+#undef ATTN_GO_RING
+#undef ATTN_GO
+    if (pl.merge == ATTN_MERGE_ROWS) hipLaunchKernelGGL(attn_combine128_rows_kernel, mgrid, dim3(256), 0, st, p, pl.merge_rows);
+    else if (pl.merge == ATTN_MERGE_128) hipLaunchKernelGGL(attn_combine128_kernel, mgrid, dim3(256), 0, st, p, pl.merge_rows);
+    else if (pl.merge == ATTN_MERGE_CHUNK) hipLaunchKernelGGL(attn_combine128_chunk_kernel, mgrid, dim3(256), 0, st, p, pl.tab, pl.merge_rows, pl.nb);
     return hipGetLastError();
 }
 
-// Decode rows of SEVERAL streams in one launch (mmd_round_multi's talking streams): grid.x = stream, each stream's keys cut into the same number of splits so that
-// nseg x nkv x splits blocks fill the chip once (one stream alone: 64 splits of ~4 tiles at 15 k keys; four streams: 16 splits of ~15 tiles -- a quarter of the
-// launches, partial rows and merge work per token).  a = the FIRST stream's rows (q / out / slabs / rope_tab; the others follow at S-row steps); a.segs (device)
-// holds every stream's context length, capacity and arena base.  bf16, head_dim 128, S x G <= 16.
+// a = the FIRST stream's rows (q / out / slabs / rope_tab; the others follow at S-row steps); a.segs (device) holds every stream's context length, capacity and arena base
 hipError_t launch_attention_decode_multi(const AttnArgs& a, hipStream_t st) {
-    const int G = a.nh / a.nkv, rows_total = a.S * G;
-    if (a.nseg < 1 || a.nseg > 64 || !a.segs || a.d != 128 || !a.v_transposed || a.k_ts != 128 || rows_total > 16 || !a.ws || a.nseg * a.nkv > 256) return hipErrorInvalidValue;
-    if (a.qkv_slabs && (a.n_slabs < 1 || a.n_slabs > 4)) return hipErrorInvalidValue;
     AttnP p;
-    p.q = a.q; p.K = nullptr; p.V = nullptr; p.out = a.out; p.ldq = a.ldq; p.ldo = a.ldo;
+    p.q = a.q; p.K = nullptr; p.V = nullptr; p.out = a.out; p.ws_o = nullptr; p.ws_ml = nullptr; p.ldq = a.ldq; p.ldo = a.ldo;
     p.k_hs = 0; p.k_ts = a.k_ts; p.v_hs = 0; p.v_ts = a.v_ts; p.q_bs = 0; p.kv_bs = 0; p.o_bs = 0;
     p.n_ctx = 0; p.S = a.S; p.nh = a.nh; p.nkv = a.nkv; p.d = a.d; p.causal = 1; p.v_tr = 1; p.dyn = a.segs; p.layer = a.layer;
     p.scale_log2 = (1.0f / sqrtf((float)a.d)) * 1.4426950408889634f;
     p.slabs = a.qkv_slabs; p.n_slabs = a.n_slabs; p.qkv_bias = a.qkv_bias; p.rope_tab = (const float2*)a.rope_tab; p.slab_rows = a.slab_rows > 0 ? a.slab_rows : a.S * a.nseg;
-    p.block_rows = 0; p.nseg = a.nseg;
-    int splits = 256 / (a.nseg * a.nkv);
-    if (splits > 64) splits = 64;
-    if (splits < 2) splits = 2;                    // (the merge kernel writes the output: at least two partials keep one code path; > 32 streams per round never occur)
-    const int nrows_all = a.nkv * rows_total;
-    while (splits > 2 && (size_t)a.nseg * splits * nrows_all * (128 + 2) * sizeof(float) > a.ws_bytes) --splits;
-    if ((size_t)a.nseg * splits * nrows_all * (128 + 2) * sizeof(float) > a.ws_bytes || a.nseg * a.nkv * splits > 512) return hipErrorInvalidValue;
-    p.splits = splits; p.kv_per_split = 0;         // (per stream, computed in the kernel from its own context length -- the dyn path)
-    p.ws_o = a.ws;
-    p.ws_ml = a.ws + (size_t)a.nseg * splits * nrows_all * 128;
-    static bool attr_set[64] = {};
-    int dev = 0; hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_gqa128_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL((attn_gqa128_kernel<1, 4>), dim3(a.nseg, a.nkv, splits), dim3(256), 4 * 32768, st, p);
-    hipLaunchKernelGGL(attn_combine128_rows_kernel, dim3(a.nseg * nrows_all), dim3(256), 0, st, p, nrows_all);
-    g_last_form[0] = 9; g_last_form[1] = splits;
-    return hipGetLastError();
+    p.nseg = a.nseg;
+    return launch_plan(attn_plan_decode_multi(a), p, a, st);
 }
 
-void attn_last_form(int* out2) { out2[0] = g_last_form[0]; out2[1] = g_last_form[1]; }          // (of the calling thread's most recent launch; model.hip copies it into the context right behind every LLM attention launch)
-static hipError_t launch_attention_(int dtype, const AttnArgs& a, hipStream_t st, AttnP& p);
 hipError_t launch_attention(int dtype, const AttnArgs& a, hipStream_t st) {
-    if (a.S <= 0) return hipSuccess;
-    AttnP p; p.splits = 1;
-    g_last_form[0] = 0;
-    const hipError_t e = launch_attention_(dtype, a, st, p);
-    g_last_form[1] = p.splits;
-    return e;
-}
-static hipError_t launch_attention_(int dtype, const AttnArgs& a, hipStream_t st, AttnP& p) {
+    const AttnPlan pl = attn_plan(dtype, a, attn_tuning());
+    if (pl.form == ATTN_PLAN_EMPTY) return hipSuccess;
+    AttnP p;
     p.q = a.q; p.K = a.K; p.V = a.V; p.out = a.out; p.ws_o = nullptr; p.ws_ml = nullptr;
     p.ldq = a.ldq; p.ldo = a.ldo;
     p.k_hs = a.k_hs; p.k_ts = a.k_ts; p.v_hs = a.v_hs; p.v_ts = a.v_ts;
     p.q_bs = a.q_bstride; p.kv_bs = a.kv_bstride; p.o_bs = a.o_bstride;
     p.n_ctx = a.n_ctx; p.S = a.S; p.nh = a.nh; p.nkv = a.nkv; p.d = a.d; p.causal = a.causal;
-    p.splits = 1; p.kv_per_split = 0; p.v_tr = a.v_transposed; p.dyn = a.dyn; p.layer = a.layer;
+    p.v_tr = a.v_transposed; p.dyn = a.dyn; p.layer = a.layer;
     p.scale_log2 = (1.0f / sqrtf((float)a.d)) * 1.4426950408889634f;
     p.slabs = a.qkv_slabs; p.n_slabs = a.n_slabs; p.qkv_bias = a.qkv_bias; p.rope_tab = (const float2*)a.rope_tab; p.slab_rows = a.slab_rows > 0 ? a.slab_rows : a.S; p.nseg = 0;
-    const bool f16 = dtype == MMD_F16;          // the fp16 vision tower: the row-major kernel only
-    bool can_mfma = (dtype == MMD_BF16 || f16) && (a.d % 8) == 0 && a.d <= 128 && (a.ldq % 8) == 0 && (a.k_ts % 8) == 0 && (a.v_ts % 8) == 0 &&
-                    (a.k_hs % 8) == 0 && (a.v_hs % 8) == 0 && (a.kv_bstride % 8) == 0 && (a.q_bstride % 8) == 0;
-    int variant = a.variant;
-    const bool can_gqa128 = can_mfma && a.d == 128 && a.v_transposed && a.batch == 1 && a.k_ts == 128;
-    // token-major K/V rows (ViT fused qkv): the transpose-read kernel; it keeps a whole sequence per (head, batch) block
-    const bool can_rowmajor = can_mfma && !a.v_transposed && a.n_ctx + a.S < (1 << 30) && (a.o_bstride % 4) == 0 && (a.ldo % 4) == 0 &&
-                              (a.n_ctx + a.S) * (a.k_ts > a.v_ts ? a.k_ts : a.v_ts) < (1ll << 31);          // (its staging loads address a sequence with 32-bit element offsets)
-    if (variant == 0) variant = can_gqa128 ? 3 : (can_rowmajor && a.S >= 64 ? 4 : (can_mfma ? 2 : 1));
-    if (a.qkv_slabs && variant != 3) return hipErrorInvalidValue;
-    if (f16 && variant != 4) return hipErrorInvalidValue;
-    if (variant == 4) {
-        if (!can_rowmajor) return hipErrorInvalidValue;
-        g_last_form[0] = 6;
-        if (a.d <= 32) return launch_rowmajor<1, 2>(p, a, st, f16);
-        if (a.d <= 64) return launch_rowmajor<2, 4>(p, a, st, f16);
-        if (a.d == 72 && !a.causal && (a.k_ts % 8) == 0 && (a.v_ts % 8) == 0 && (a.k_hs % 8) == 0 && (a.v_hs % 8) == 0 && (a.kv_bstride % 8) == 0 &&
-            ((uintptr_t)a.K % 16) == 0 && ((uintptr_t)a.V % 16) == 0 && ((uintptr_t)a.q % 16) == 0 && (a.ldq % 8) == 0 && (a.q_bstride % 8) == 0 && a.n_ctx + a.S > 0) {
-            // SigLIP-so400m, bidirectional: K / V tiles by LDS-DMA into two slots, four blocks per CU (MMDUET_VIT_ATTN_RING=0: the register-staged kernel, A/B)
-            static const bool ring_off = getenv("MMDUET_VIT_ATTN_RING") && atoi(getenv("MMDUET_VIT_ATTN_RING")) == 0;
-            if (!ring_off) {
-                p.splits = 1; p.kv_per_split = 0; g_last_form[0] = 7;
-                const size_t lds = (size_t)2 * 2 * 10 * 512 * sizeof(bf16_t);
-                const dim3 grid(cdiv(a.S, 128), a.nh, a.batch);
-                if (f16) hipLaunchKernelGGL((attn_d72_ring_kernel<true>), grid, dim3(256), lds, st, p);
-                else hipLaunchKernelGGL((attn_d72_ring_kernel<false>), grid, dim3(256), lds, st, p);
-                return hipGetLastError();
-            }
-        }
-        if (a.d > 64 && a.d <= 80) return launch_rowmajor<3, 5, true>(p, a, st, f16);          // SigLIP-so400m: 72 -> five 16-wide output tiles, known at compile time
-        if (a.d <= 96) return launch_rowmajor<3, 6>(p, a, st, f16);
-        return launch_rowmajor<4, 8>(p, a, st, f16);
-    }
-    if (variant == 2 && !can_mfma) return hipErrorInvalidValue;
-    if (variant == 6) {          // the chunk kernel's contiguous decomposition, forced (attn_chunk.h)
-        if (!can_gqa128 || a.qkv_slabs || a.dyn || a.S * (a.nh / a.nkv) < 256) return hipErrorInvalidValue;
-        g_last_form[0] = 8;
-        return launch_gqa128_chunk(p, a, st);
-    }
-    if (variant == 5) {          // software-pipelined waves, balanced row blocks (attn_w1.h)
-        if (!can_gqa128 || a.qkv_slabs || a.dyn) return hipErrorInvalidValue;
-        g_last_form[0] = 5;
-        return launch_gqa128_w1_auto(p, a, st);
-    }
-    if (variant == 3) {
-        if (!can_gqa128) return hipErrorInvalidValue;
-        const int rows_total = a.S * (a.nh / a.nkv);
-        if (a.qkv_slabs && (rows_total > 64 || a.k_ts != 128 || a.n_slabs < 1 || a.n_slabs > 4)) return hipErrorInvalidValue;        // the fused q/k/v preparation lives in the decode form only
-        // per-frame steps and short chunks over a long context (17 .. 768 stacked rows per kv head, >= 64 key tiles): attn_gqa128_w1_kernel -- two balanced row blocks of whole
-        // 16-row tiles instead of three 128-row blocks, one block per CU on the four-slot ring (S = 49 over 15 k keys: 31.6 -> 27.7 us incl. the merge; below 4 k keys its
-        // longer pipeline fill loses 2-20 %, from 1 k rows up the 256-row phase-split form is 8 % faster: profiles/r05_attn_small_s.md)
-        if (a.variant == 0 && !a.qkv_slabs && !a.dyn && rows_total > 16 && rows_total <= 768 && a.n_ctx + a.S >= 4096 && a.ws) { g_last_form[0] = 5; return launch_gqa128_w1_auto(p, a, st); }
-        g_last_form[0] = rows_total <= 64 ? 3 : 4;
-        return rows_total <= 64 ? launch_gqa128<1>(p, a, st) : launch_gqa128<2>(p, a, st);
-    }
-    g_last_form[0] = variant == 1 ? 1 : 2;
-    if (variant == 1) {
-        if (a.d > 128) return hipErrorInvalidValue;
-        dim3 grid(a.S, a.nh, a.batch);
-        if (dtype == MMD_F32) hipLaunchKernelGGL(attn_simple_kernel<float>, grid, dim3(64), 0, st, p);
-        else hipLaunchKernelGGL(attn_simple_kernel<bf16_t>, grid, dim3(64), 0, st, p);
-        return hipGetLastError();
-    }
-    if (a.d <= 32) return launch_mfma<32>(p, a, st);
-    if (a.d <= 64) return launch_mfma<64>(p, a, st);
-    if (a.d <= 96) return launch_mfma<96>(p, a, st);
-    return launch_mfma<128>(p, a, st);
+    return launch_plan(pl, p, a, st);
 }

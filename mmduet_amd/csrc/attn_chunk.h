@@ -16,13 +16,10 @@
 // Rounding points = attn_gqa128_kernel's; a row's result depends on where its unit is cut (fp32 summation order of the partials), deterministically.
 #pragma once
 
-// unit geometry: start[bx] = key tiles of the units 0 .. bx - 1 of one kv head (start[qblocks] = tiles per kv head); built on the host once per launch, rides in the
-// kernel argument (the attention kernel and the merge read it with scalar loads: recomputing it per wave cost the merge 280 us at 35 k rows)
+// unit geometry: ChunkTab (attn_plan.h, where plan_gqa128_chunk builds it -- the host side of the formulas below -- and decides whether this form takes a launch)
 #ifndef CHUNK_DBG
 #define CHUNK_DBG 0          // timing-only ablations (wrong results): tools/probes/chunk_ablate.sh
 #endif
-constexpr int CHUNK_TAB = 128, CHUNK_UNITS = 512;
-struct ChunkTab { int qblocks; int start[CHUNK_TAB + 1]; unsigned short b0[CHUNK_UNITS], b1[CHUNK_UNITS]; };          // b0 / b1[kvh * qblocks + bx]: first / last block that shares the unit
 // block b of nb owns linear tiles [b * W / nb, (b + 1) * W / nb)
 __device__ __forceinline__ long long chunk_cut(long long W, int nb, int b) { return (W * b) / nb; }
 __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, ChunkTab tab) {
@@ -344,59 +341,4 @@ __global__ __launch_bounds__(256) void attn_combine128_chunk_kernel(AttnP p, Chu
     bf16_t* orow = (bf16_t*)p.out + (long long)tok * p.ldo + (long long)head * 128;
     s16x2_t o = {(short)f2bf(a0 * inv), (short)f2bf(a1 * inv)};
     *reinterpret_cast<s16x2_t*>(orow + lane * 2) = o;
-}
-
-// host side of the same formulas: key tiles per unit, total, and the most blocks that share one unit
-static int chunk_unit_tiles_host(int rows_total, int G, long long n_ctx, int S, int causal, int bx) {
-    const int last_row = (bx * 256 + 255 < rows_total - 1) ? bx * 256 + 255 : rows_total - 1;
-    const long long n_tot = n_ctx + S;
-    long long lim = causal ? n_ctx + (long long)(last_row / G) + 1 : n_tot;
-    if (lim > n_tot) lim = n_tot;
-    return (int)((lim + 63) >> 6);
-}
-static int chunk_block_of_host(long long W, int nb, long long tile) {
-    int b = (int)((tile * nb) / W);
-    while (b + 1 < nb && (W * (b + 1)) / nb <= tile) ++b;
-    while (b > 0 && (W * b) / nb > tile) --b;
-    return b;
-}
-// linear tiles per block of the contiguous decomposition (the dispatcher's criterion: short ranges pay a q load / pipeline fill / partial per segment)
-static long long chunk_tiles_total(const AttnArgs& a) {
-    const int G = a.nh / a.nkv, rows_total = a.S * G, qblocks = cdiv(rows_total, 256);
-    long long W1 = 0;
-    for (int b = 0; b < qblocks; ++b) W1 += chunk_unit_tiles_host(rows_total, G, a.n_ctx, a.S, a.causal, b);
-    return W1 * a.nkv;
-}
-static hipError_t launch_gqa128_chunk(AttnP& p, const AttnArgs& a, hipStream_t st) {
-    const int G = a.nh / a.nkv, rows_total = a.S * G, qblocks = cdiv(rows_total, 256);
-    if (qblocks > CHUNK_TAB || qblocks * a.nkv > CHUNK_UNITS) return hipErrorInvalidValue;
-    ChunkTab tab; tab.qblocks = qblocks; tab.start[0] = 0;
-    long long W1 = 0; int tmax = 0;
-    for (int b = 0; b < qblocks; ++b) { const int t = chunk_unit_tiles_host(rows_total, G, a.n_ctx, a.S, a.causal, b); W1 += t; if (t > tmax) tmax = t; tab.start[b + 1] = (int)W1; }
-    for (int b = qblocks + 1; b <= CHUNK_TAB; ++b) tab.start[b] = (int)W1;
-    const long long W = W1 * a.nkv;
-    int nb = 256; if (W < nb) nb = (int)W;
-    const int nrows_all = a.nkv * rows_total;
-    for (int k = 0; k < a.nkv; ++k)
-        for (int b = 0; b < qblocks; ++b) {
-            const long long us = (long long)k * W1 + tab.start[b];
-            tab.b0[k * qblocks + b] = (unsigned short)chunk_block_of_host(W, nb, us);
-            tab.b1[k * qblocks + b] = (unsigned short)chunk_block_of_host(W, nb, us + (tab.start[b + 1] - tab.start[b]) - 1);
-        }
-    // without a workspace every unit must be whole: one block per unit; with one, bound the parts per unit by the workspace
-    int parts_max = (int)(tmax / (W / nb)) + 2;
-    if (!a.ws || parts_max > 64 || (size_t)parts_max * nrows_all * (128 + 2) * sizeof(float) > a.ws_bytes) return hipErrorInvalidValue;          // (the caller falls back to attn_gqa128_kernel)
-    p.splits = parts_max; p.kv_per_split = 0;
-    p.ws_o = a.ws;
-    p.ws_ml = a.ws + (size_t)parts_max * nrows_all * 128;
-    static bool attr_set[64] = {};
-    int dev = 0; hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_gqa128_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 32768);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(attn_gqa128_chunk_kernel, dim3(nb), dim3(512), 4 * 32768, st, p, tab);
-    hipLaunchKernelGGL(attn_combine128_chunk_kernel, dim3(cdiv(nrows_all, 4)), dim3(256), 0, st, p, tab, nrows_all, nb);
-    return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 #include <string>
 #include "../../include/mmduet.h"
 #include "gemm_plan.h"          // GemmArgs, GemmPlan and the dispatch decision (host-only: no GPU header), cdiv / round_up, MMD_F16
+#include "attn_plan.h"          // AttnArgs, AttnPlan and the attention dispatch decision (host-only too)
 
 typedef uint16_t bf16_t;   // raw bfloat16 storage
 
@@ -208,26 +209,5 @@ hipError_t launch_letterbox(const uint8_t* src, int T, int H, int W, int new_w, 
 hipError_t launch_preprocess(int dtype, const uint8_t* frames, int T, int R, int size, const int32_t* coef, const int32_t* bounds, int ksize,
                              uint8_t* tmp, void* out, hipStream_t st);
 
-struct AttnArgs {
-    const void* q; int64_t ldq;      // [S, nh*d] row stride ldq
-    const void* K; const void* V;    // element (kv head h, token t, e) at K + h*k_hs + t*k_ts + e
-    int64_t k_hs, k_ts, v_hs, v_ts;  // arena: hs = cap*d, ts = d ; fused ViT qkv rows: hs = d, ts = 3C
-    int v_transposed;                // V arena stored transposed in 64-token blocks (see attn.hip); v_ts unused then
-    void* out; int64_t ldo;          // [S, nh*d]
-    int S, nh, nkv, d;
-    int64_t n_ctx;                   // keys before this step; total keys = n_ctx + S
-    int causal;
-    int batch; int64_t q_bstride, kv_bstride, o_bstride;   // ViT: batch of independent sequences (elements)
-    float* ws; size_t ws_bytes;      // split-KV partials
-    int variant;
-    const StepState* dyn; int layer; int dyn_splits;   // graph mode (attn_gqa128 only)
-    // decode steps (rows <= 64, attn_gqa128<1> only): q / k / v are still the qkv projection's fp32 K-slabs.  The attention kernel itself reduces
-    // them (+ bias), applies RoPE from the step's (cos, sin) table, builds its q fragments in registers and -- the block whose key range holds a new
-    // position -- appends that token's K row / V column to the arena before staging the tile: no slab_rope_append launch, no q buffer.
-    const float* qkv_slabs = nullptr; int n_slabs = 0; const void* qkv_bias = nullptr; const void* rope_tab = nullptr;   // slabs [n][slab_rows][(nh+2nkv)*d] (this step's first row); tab float2 [S][d/2]
-    int slab_rows = 0;               // rows of one slab = the projection's M (0: S); larger than S when one GEMV served several streams' rows (mmd_round_multi)
-    const StepState* segs = nullptr; int nseg = 0;   // launch_attention_decode_multi: the streams' (context length, capacity, arena base), device
-};
 hipError_t launch_attention(int dtype, const AttnArgs& a, hipStream_t st);
-void attn_last_form(int* out2);          // {form, key splits} of the calling thread's most recent launch_attention* (attn.hip)
 hipError_t launch_attention_decode_multi(const AttnArgs& a, hipStream_t st);     // decode rows of a.nseg streams in one launch (attn.hip)

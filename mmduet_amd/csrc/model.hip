@@ -1387,7 +1387,8 @@ static int layer_attention(const StepRun& r, int i, int splits) {
         double kvb = 0, fl = 0;
         for (int j = run0; j < run0 + run_n; ++j) { const double nk = (double)(r.segs[j].s->len + r.segs[j].rows); kvb += 2.0 * nk * nkv * d * e; fl += 4.0 * r.segs[j].rows * nk * nh * d; }
         ProfScope ps(c, MMD_K_ATTN_LLM, kvb + 2.0 * rr * run_n * nh * d * e, fl);
-        { const hipError_t le = launch_attention_decode_multi(a, st); attn_last_form(c->last_form); HIPCHK(c, le); }
+        a.plan_out = c->last_form;
+        HIPCHK(c, launch_attention_decode_multi(a, st));
     }
     for (int j = 0; j < r.nseg; ++j) {
         if (j >= run0 && j < run0 + run_n) continue;
@@ -1400,7 +1401,8 @@ static int layer_attention(const StepRun& r, int i, int splits) {
         a.dyn = r.dyn; a.dyn_splits = 64;
         double kvb = 2.0 * (double)(nj + Sj) * nkv * d * e;
         ProfScope ps(c, MMD_K_ATTN_LLM, kvb + 2.0 * Sj * nh * d * e, 4.0 * Sj * (double)(nj + Sj) * nh * d);
-        { const hipError_t le = launch_attention(g.dtype, a, st); attn_last_form(c->last_form); HIPCHK(c, le); }
+        a.plan_out = c->last_form;
+        HIPCHK(c, launch_attention(g.dtype, a, st));
     }
     return MMD_OK;
 }
@@ -2640,8 +2642,8 @@ extern "C" int mmd_op_kv_write(mmd_ctx* c, int writer, const void* src, int n_sl
             a.q = nullptr; a.ldq = (int64_t)nh * d; a.K = Kc; a.V = Vc; a.k_hs = cap * d; a.k_ts = d; a.v_hs = cap * d; a.v_ts = d; a.v_transposed = 1; a.out = attn_out; a.ldo = (int64_t)nh * d;
             a.S = S; a.nh = nh; a.nkv = nkv; a.d = d; a.n_ctx = pos0; a.causal = 1; a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.variant = 3;
             a.qkv_slabs = (const float*)src; a.slab_rows = slab_rows; a.n_slabs = n_slabs; a.qkv_bias = bias; a.rope_tab = tab;
+            a.plan_out = c->last_form;
             e = launch_attention(c->cfg.dtype, a, c->stream);
-            attn_last_form(c->last_form);
         }
     }
     const int rc = done(MMD_OK);
@@ -2806,8 +2808,8 @@ extern "C" int mmd_op_attention(mmd_ctx* c, const void* q, const void* Kc, const
         HIPCHK(c, launch_transpose_v(c->cfg.dtype, Vc, vt, nkv, cap, d, c->stream));
         a.V = vt; a.v_transposed = 1;
     }
+    a.plan_out = c->last_form;
     hipError_t le = launch_attention(c->cfg.dtype, a, c->stream);
-    attn_last_form(c->last_form);
     if (vt) { hipStreamSynchronize(c->stream); dev_free(c, vt); }
     HIPCHK(c, le);
     return MMD_OK;
@@ -2828,7 +2830,7 @@ extern "C" int mmd_op_attention_bench(mmd_ctx* c, int S, int nh, int nkv, int d,
     AttnArgs a; memset(&a, 0, sizeof(a));
     a.q = q; a.ldq = (int64_t)nh * d; a.K = K; a.V = V; a.k_hs = cap * d; a.k_ts = d; a.v_hs = cap * d; a.v_ts = d; a.out = o; a.ldo = (int64_t)nh * d;
     a.S = S; a.nh = nh; a.nkv = nkv; a.d = d; a.n_ctx = n_ctx; a.causal = 1; a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.variant = variant;
-    a.v_transposed = 1;
+    a.v_transposed = 1; a.plan_out = c->last_form;
     hipEvent_t ea, eb; hipEventCreate(&ea); hipEventCreate(&eb);
     for (int i = 0; i < 3; ++i) HIPCHK(c, launch_attention(c->cfg.dtype, a, c->stream));
     hipEventRecord(ea, c->stream);
