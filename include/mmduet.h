@@ -455,6 +455,12 @@ int mmd_op_decode_last_route(mmd_ctx* ctx);
  * mean): out9 = {schedule (0 tile, 1 fused slabs, 2 decode chain), rope_fused, chunk_rope, sparse_last, run0, run_n, run_all (the batched decode attention's run of segments),
  * down_slab_norm, mlp_pm} */
 int mmd_op_step_last_plan(mmd_ctx* ctx, int* out9);
+/* the plan the most recent token selection of this context was launched from (select_plan() of mmduet_amd/csrc/select_plan.h; after a generate call whose steps replayed a
+ * captured step: the plan that step was captured from): out22 = {kind (0 arg-max, 1 constrained arg-max, 2 draw), single, any_k, any_p, needs_row, needs_cons, record,
+ * scores_after_argmax, record_greedy, advance}, then whose selection it was -- 0 a raw operator, 1 a generate call, 2 a round -- and that caller's own plan: a generate call's
+ * {can_graph, upload_state, post_row_dynamic, post_row_each_eager_step, post_cons_dynamic, post_cons_each_eager_step, host_appends_penalty, pen_key_is_value, key_sel, key_lp,
+ * key_cons_gen}, a round's {n_plain, n_greedy, n_sample, any_k, any_p, any_cons_sampled} (the rest of the 11 unspecified) */
+int mmd_op_select_last_plan(mmd_ctx* ctx, int* out22);
 int mmd_op_pool(mmd_ctx* ctx, const void* x, void* y, int B, int grid, int H, int mode, int stride);
 
 #ifdef __cplusplus

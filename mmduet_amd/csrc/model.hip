@@ -8,6 +8,7 @@
 //   fast_greedy_generate (models/modeling_live.py:51-77) -> mmd_greedy_generate
 #include "common.h"
 #include "step_plan.h"
+#include "select_plan.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -32,6 +33,11 @@ struct Prof {
     std::vector<Pending> pending;
     double ms[MMD_K_COUNT] = {0}; int64_t n[MMD_K_COUNT] = {0}; double bytes[MMD_K_COUNT] = {0}; double flops[MMD_K_COUNT] = {0};
 };
+
+static_assert(SELECT_ROUND_MAX_ROWS == MMD_ROUND_MAX_SAMPLERS, "select_plan.h restates the rows of one launch");
+enum { SELECT_OF_OP = 0, SELECT_OF_GENERATE = 1, SELECT_OF_ROUND = 2 };
+constexpr int SELECT_LAST_FIELDS = SELECT_PLAN_FIELDS + 1 + GENERATE_PLAN_FIELDS;          // (a RoundBlocks is the shorter tail)
+static_assert(ROUND_BLOCKS_FIELDS <= GENERATE_PLAN_FIELDS, "the tail of select_last holds either");
 
 // a validated constraint set on the host (DESIGN.md "Constraints"): the table sorted by id, ids unique
 struct ConsSet { bool on = false; int n = 0, n_eos = 0, min_new = 0; int64_t eos[CONS_MAX_EOS] = {}; int32_t ids[CONS_MAX_TABLE] = {}; float bias[CONS_MAX_TABLE] = {}; };
@@ -105,6 +111,8 @@ struct mmd_ctx {
     int last_plan[4] = {-1, 0, 0, 0};   // kernel / tiles / splits / blocks of the most recent gemm() (mmd_op_gemm_last_plan)
     StepSwitches sw;                   // the A/B switches of the step schedule (step_plan.h), read from the environment in mmd_create
     int step_last[STEP_PLAN_FIELDS] = {0};          // the plan of the most recent LLM step of THIS context (mmd_op_step_last_plan)
+    // the SelectPlan the most recent token selection launched from, then whose it was (SELECT_OF_*) and that caller's GeneratePlan / RoundBlocks (mmd_op_select_last_plan)
+    int select_last[SELECT_LAST_FIELDS] = {0};
     bool gemm_half = false;            // the GEMMs issued right now belong to the fp16 vision tower (cfg.tower_f16): IEEE-half operands
     int tower_ring_flags = -1, tower_ring_blocks = 0;   // mmd_set_tower_share: persistent-grid cap of the tower's ring GEMMs beside a response's decoding
     int hid_compact = 0;               // > 0: l_hid holds that many compact rows (in the order of the `need` list) instead of all S rows of the step
@@ -1225,7 +1233,6 @@ extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) {
 }
 extern "C" int64_t mmd_kv_position(const mmd_stream* s) { return s ? s->len + s->pos_off : -1; }          // the RoPE position the next token gets
 
-static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need);
 // measurement aid (tools/kv_growth_sweep.py): declare the first n slots of the arena live without computing them, to time a
 // step at a given context length (the slots hold zeros / stale data -- numerically meaningless, same memory traffic)
 extern "C" int mmd_kv_debug_set_len(mmd_stream* s, int64_t n) {
@@ -1667,10 +1674,8 @@ static int cons_upload_table(mmd_ctx* c, const ConsSet& s, int32_t* ids_dev, flo
     return MMD_OK;
 }
 
-// one draw's parameters; SampleCall: which of the chain's filter kernels a launch over such rows needs
+// one draw's parameters
 struct SampleArgs { float temperature; int top_k; float top_p; uint64_t seed; uint64_t* offset_inout; };
-struct SampleCall { bool any_k, any_p; };
-static SampleCall sample_call(const SampleArgs& a, int V) { return SampleCall{a.top_k > 0 && a.top_k < V, a.top_p < 1.f}; }
 // every field of a row descriptor.  pen off: no list entry counts and the penalty is 1; n_prev_ptr (a decode step: &StepState::n_prev) overrides n_prev on the device
 static void fill_sample_row(SampleRow& r, const SampleArgs& a, const int64_t* prev, bool pen, int n_prev, int prev_cap, float penalty, const int* n_prev_ptr, int64_t* tok,
                             int64_t* append, uint32_t lane, uint32_t advance) {
@@ -1686,8 +1691,49 @@ static int sample_reserve(mmd_ctx* c) {
 }
 static int check_sampling(mmd_ctx* c, float temperature, int top_k, float top_p) {
     if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1 (got %g, %d, %g)", temperature, top_k, top_p);
-    if (c->cfg.vocab_size > (1 << 18)) FAIL(c, MMD_ERANGE, "sampling handles vocabularies up to 2^18 entries");
     return MMD_OK;
+}
+// the rows of a selection as select_plan() takes them
+static SelectRows select_rows(bool sampled, bool constrained, bool record, int n, bool single, bool dyn, int V, const SampleArgs* a) {
+    SelectRows r;
+    r.sampled = sampled; r.constrained = constrained; r.record = record; r.n = n; r.single = single; r.dyn = dyn; r.V = V;
+    if (a) { r.top_k = a->top_k; r.top_p = a->top_p; }
+    return r;
+}
+static int select_refused(mmd_ctx* c, const SelectPlan& p) { if (p.rc) FAIL(c, p.rc, "%s", p.error); return MMD_OK; }
+
+// ---- the one place a token selection is launched from ---------------------------------------------------------------------------------------------------
+// Everything a selection's launches are handed besides the plan; which of it a launch reads is the plan's business (select_plan.h), nothing is decided here.
+struct SelectIO {
+    const float* logits; int V, n;     // [n, V] fp32
+    SampleRow* rows; const ConstraintRow* cons; const LogprobOut* lp;          // descriptors on the device, one per row; where the records go
+    int64_t* toks;                     // tokens out (a draw may have none: its rows' descriptors name the slots)
+    void* scratch; void* lp_scratch;   // the chain's and the records' scratch
+    void* am_scratch = nullptr;        // the arg-max's candidates
+    const SampleBatch* batch = nullptr;          // SEL_ARGMAX over a block: the rows' lists and slots
+    const int64_t* prev = nullptr; int n_prev = 0; float penalty = 1.f; const StepState* dyn = nullptr;          // SEL_ARGMAX, single: the list rides in kernel arguments
+    const unsigned long long* r_words = nullptr; float* info = nullptr; float* scores = nullptr;          // the raw operator's: explicit random words, the draw's info, the z rows
+};
+static hipError_t select_enqueue(mmd_ctx* c, const SelectPlan& p, const SelectIO& io) {
+    hipStream_t st = c->stream; hipError_t e = hipSuccess;
+    const ConstraintRow* cons = p.needs_cons ? io.cons : nullptr;
+    const LogprobOut* lp = p.record ? io.lp : nullptr;
+    p.fields(c->select_last);
+    switch (p.kind) {
+    case SEL_DRAW:          // (the draw records sampling_logprob itself)
+        e = launch_sample_batch_topkp(io.logits, io.V, io.n, io.rows, p.any_k, p.any_p, io.r_words, io.toks, io.info, io.scores, io.scratch, st, lp, cons);
+        break;
+    case SEL_CONS_ARGMAX:          // the chain's scores with nothing filtered, then the first maximal index of z
+        e = launch_sample_scores_unfiltered(io.logits, io.V, io.n, io.rows, io.scores, io.scratch, st, cons);
+        if (e == hipSuccess) e = launch_argmax_scores(io.V, io.n, io.rows, io.scores, io.scratch, io.toks, st);
+        break;
+    default:
+        e = p.single ? launch_argmax_penalty(io.logits, io.V, io.prev, io.n_prev, io.penalty, io.toks, st, io.dyn, io.am_scratch)
+                     : launch_sample_batch(io.logits, io.V, *io.batch, io.n, io.toks, io.am_scratch, st);
+        if (e == hipSuccess && p.scores_after_argmax) e = launch_sample_scores_unfiltered(io.logits, io.V, io.n, io.rows, io.scores, io.scratch, st);
+    }
+    if (e == hipSuccess && p.record) e = launch_logprob_rows(io.logits, io.V, io.n, *lp, p.record_greedy, io.scores, io.scratch, io.lp_scratch, st);
+    return e;
 }
 
 extern "C" int mmd_sampler_create(mmd_ctx* c, mmd_sampler** out) {
@@ -1737,6 +1783,7 @@ extern "C" int mmd_sampler_set_sampling(mmd_sampler* sp, float temperature, int 
     mmd_ctx* c = sp->ctx;
     if (!(temperature > 0.f)) { sp->sampling = false; return MMD_OK; }
     int rc = check_sampling(c, temperature, top_k, top_p); if (rc) return rc;
+    rc = select_refused(c, select_plan(select_rows(true, false, false, 1, false, false, c->cfg.vocab_size, nullptr))); if (rc) return rc;
     if (!sp->seeded || seed != sp->seed) { sp->seed = seed; sp->offset = 0; sp->seeded = true; }
     sp->sampling = true; sp->temperature = temperature; sp->top_k = top_k; sp->top_p = top_p;
     return MMD_OK;
@@ -1746,7 +1793,7 @@ extern "C" int mmd_sampler_set_constraints(mmd_sampler* sp, const int64_t* eos_i
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
     ConsSet s; int rc = cons_validate(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
     if (s.on) {
-        if (c->cfg.vocab_size > (1 << 18)) FAIL(c, MMD_ERANGE, "constraints handle vocabularies up to 2^18 entries");
+        rc = select_refused(c, select_plan(select_rows(false, true, false, 1, false, false, c->cfg.vocab_size, nullptr))); if (rc) return rc;
         rc = cons_reserve(c); if (rc) return rc;
         if (!sp->cons_bias_dev) {
             if (hipMalloc((void**)&sp->cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&sp->cons_bias_dev, CONS_MAX_TABLE * sizeof(float)) != hipSuccess)
@@ -1772,40 +1819,15 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
     hipStream_t st = c->stream; const int H = c->cfg.hidden_size, V = c->cfg.vocab_size; const size_t e = es(c);
     // the round's input rows: embeddings handed in per segment, or -- FEED -- the embedding of the token the segment's sampler drew in the round before
     FeedBatch feed; int n_feed = 0;
-    // sampling rows: the arg-max ones first, the ones whose sampler has sampling on behind them (two passes over the segments), so each kind is one block of logits rows
-    SampleBatch sb; int n_sample = 0; int32_t sample_row[MMD_ROUND_MAX_SAMPLERS]; int sample_seg[MMD_ROUND_MAX_SAMPLERS];
-    // with constraints (mmd_sampler_set_constraints) three blocks: plain arg-max | constrained arg-max | sampled.  The last two have row descriptors (and constraint
-    // descriptors, empty for an unconstrained sampled row) in slots 1.. of the context's arrays, in the order of their logits rows
-    int n_plain = 0, n_greedy = 0; bool any_k = false, any_p = false, any_cons_sampled = false; uint64_t no_offset = 0;
-    for (int pass = 0; pass < 3; ++pass)
+    std::vector<RoundSeg> rsegs((size_t)n_segs);
     for (int j = 0; j < n_segs; ++j) {
         const int fl = seg_flags ? seg_flags[j] : 0;
         mmd_sampler* sp = samplers ? samplers[j] : nullptr;
         if ((fl & (MMD_SEG_FEED | MMD_SEG_SAMPLE)) && (!sp || sp->ctx != c)) FAIL(c, MMD_EINVAL, "segment %d feeds / samples without a sampler of this context", j);
-        if (pass == 0 && n_greedy < n_plain) n_greedy = n_plain;
-        if (pass > 0) {
-            if (!(fl & MMD_SEG_SAMPLE)) continue;
-            if (pass == 1 ? (sp->sampling || !sp->cons.on) : !sp->sampling) continue;
-            if (n_sample >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d sampling segments", MMD_ROUND_MAX_SAMPLERS);
-            for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
-            if (n_sample == n_plain) { rc = sample_reserve(c); if (rc) return rc; }
-            if (sp->cons.on) { rc = cons_reserve(c); if (rc) return rc; }
-            const bool pen = sp->penalty > 0.f;
-            const SampleArgs a = pass == 1 ? SampleArgs{1.f, 0, 1.f, 0, &no_offset} : SampleArgs{sp->temperature, sp->top_k, sp->top_p, sp->seed, &sp->offset};
-            const int slot = 1 + n_sample - n_plain;
-            fill_sample_row(c->samp_rows_host[slot], a, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr, sp->tok_dev,
-                            (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr, pass == 1 ? 0 : sp->lane, 0);
-            if (c->cons_rows_host) {
-                if (sp->cons.on) cons_fill_row(c->cons_rows_host[slot], sp->cons, sp->cons_ids_dev, sp->cons_bias_dev, sp->eos, V, sp->step, nullptr);
-                else c->cons_rows_host[slot] = ConstraintRow{};
-            }
-            if (pass == 2) { any_k |= sample_call(a, V).any_k; any_p |= sample_call(a, V).any_p; any_cons_sampled |= sp->cons.on; }
-            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample;
-            if (pass == 1) n_greedy = n_sample;
-            continue;
-        }
-        if (fl & MMD_SEG_FEED) {
-            if (segs[j].rows != 1) FAIL(c, MMD_EINVAL, "a feed segment is one row (segment %d has %d)", j, segs[j].rows);
+        RoundSeg& r = rsegs[j];
+        r.feed = (fl & MMD_SEG_FEED) != 0; r.sample = (fl & MMD_SEG_SAMPLE) != 0; r.rows = segs[j].rows;
+        if (sp) { r.sampling = sp->sampling; r.constrained = sp->cons.on; r.sampler = (int)sp->lane; r.top_k = sp->top_k; r.top_p = sp->top_p; }          // (lane: the sampler's index within its context)
+        if (r.feed) {
             if (n_feed >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d feed segments", MMD_ROUND_MAX_SAMPLERS);
             feed.tok[n_feed] = sp->tok_dev; feed.row[n_feed] = segs[j].row0; ++n_feed;
         } else {
@@ -1813,15 +1835,34 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             void* dst = (char*)c->l_h + (size_t)segs[j].row0 * H * e;
             if (seg_embeds[j] != dst) HIPCHK(c, hipMemcpyAsync(dst, seg_embeds[j], (size_t)segs[j].rows * H * e, hipMemcpyDeviceToDevice, st));
         }
-        if ((fl & MMD_SEG_SAMPLE) && !sp->sampling && !sp->cons.on) {
-            if (n_sample >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d sampling segments", MMD_ROUND_MAX_SAMPLERS);
-            for (int k = 0; k < n_sample; ++k) if (samplers[sample_seg[k]] == sp) FAIL(c, MMD_EINVAL, "a sampler may appear once per round");
-            const bool pen = sp->penalty > 0.f;
-            sb.prev[n_sample] = sp->prev_dev; sb.n_prev[n_sample] = pen ? sp->n_prev : 0; sb.penalty[n_sample] = pen ? sp->penalty : 1.f;
-            sb.tok[n_sample] = sp->tok_dev; sb.append[n_sample] = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
-            sample_row[n_sample] = segs[j].row0 + segs[j].rows - 1; sample_seg[n_sample] = j; ++n_sample; n_plain = n_greedy = n_sample;
+    }
+    // sampling rows: three blocks of logits rows, plain arg-max | constrained arg-max | sampled (round_blocks).  The last two have row descriptors (and constraint descriptors,
+    // empty for an unconstrained sampled row) in slots 1.. of the context's arrays, in the order of their logits rows
+    const RoundBlocks rb = round_blocks(rsegs.data(), n_segs, V);
+    if (rb.rc) FAIL(c, rb.rc, "%s", rb.error);
+    const int n_plain = rb.n_plain, n_greedy = rb.n_greedy, n_sample = rb.n_sample; const int* sample_seg = rb.order;
+    SampleBatch sb; int32_t sample_row[MMD_ROUND_MAX_SAMPLERS]; uint64_t no_offset = 0;
+    if (n_sample > n_plain) { rc = sample_reserve(c); if (rc) return rc; }
+    for (int i = 0; i < n_sample; ++i) {
+        const int j = sample_seg[i]; mmd_sampler* sp = samplers[j];
+        const bool pen = sp->penalty > 0.f;
+        int64_t* append = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
+        sample_row[i] = segs[j].row0 + segs[j].rows - 1;
+        if (i < n_plain) {
+            sb.prev[i] = sp->prev_dev; sb.n_prev[i] = pen ? sp->n_prev : 0; sb.penalty[i] = pen ? sp->penalty : 1.f; sb.tok[i] = sp->tok_dev; sb.append[i] = append;
+            continue;
+        }
+        if (sp->cons.on) { rc = cons_reserve(c); if (rc) return rc; }
+        const bool draw = i >= n_greedy;
+        const SampleArgs a = draw ? SampleArgs{sp->temperature, sp->top_k, sp->top_p, sp->seed, &sp->offset} : SampleArgs{1.f, 0, 1.f, 0, &no_offset};
+        const int slot = 1 + i - n_plain;
+        fill_sample_row(c->samp_rows_host[slot], a, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr, sp->tok_dev, append, draw ? sp->lane : 0, 0);
+        if (c->cons_rows_host) {
+            if (sp->cons.on) cons_fill_row(c->cons_rows_host[slot], sp->cons, sp->cons_ids_dev, sp->cons_bias_dev, sp->eos, V, sp->step, nullptr);
+            else c->cons_rows_host[slot] = ConstraintRow{};
         }
     }
+    c->select_last[SELECT_PLAN_FIELDS] = SELECT_OF_ROUND; rb.fields(c->select_last + SELECT_PLAN_FIELDS + 1);
     if (n_sample && !tokens_out_host) FAIL(c, MMD_EINVAL, "sampling segments need tokens_out_host");
     if (n_feed) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_embed_feed(c->cfg.dtype, c->embed, feed, n_feed, H, V, c->l_h, st)); }
     if (n_sample && !c->round_logits) {
@@ -1844,18 +1885,24 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             rows = c->round_hidden;
         }
         rc = gemm(c, rows, H, c->lm_head, H, nullptr, nullptr, 0, c->round_logits, V, n_sample, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-        if (n_plain) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_sample_batch(c->round_logits, V, sb, n_plain, c->round_toks_dev, c->round_scratch, st)); }
+        // one block of the round's logits rows; the descriptors of a row behind the plain ones sit in slot 1 + (row - n_plain).  (The sampled rows reuse the constrained arg-max's scratch: same stream.)
+        auto block = [&](int kind) -> hipError_t {
+            const SelectPlan p = rb.plan(kind);
+            const int r0 = rb.row0(kind);
+            SelectIO io{};
+            io.logits = c->round_logits + (size_t)r0 * V; io.V = V; io.n = rb.rows(kind); io.toks = c->round_toks_dev + r0;
+            io.rows = p.needs_row ? c->samp_rows_dev + 1 + (r0 - n_plain) : nullptr; io.cons = p.needs_cons ? c->cons_rows_dev + 1 + (r0 - n_plain) : nullptr;
+            io.scratch = c->samp_scratch; io.am_scratch = c->round_scratch; io.batch = &sb;
+            return select_enqueue(c, p, io);
+        };
+        if (n_plain) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, block(SEL_ARGMAX)); }
         if (n_sample > n_plain) {
-            const int nd = n_sample - n_plain, nc = n_greedy - n_plain, ns = n_sample - n_greedy;
+            const int nd = n_sample - n_plain;
             HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev + 1, c->samp_rows_host + 1, sizeof(SampleRow) * nd, hipMemcpyHostToDevice, st));          // (the round's synchronisation frees the staging)
-            if (nc || any_cons_sampled) HIPCHK(c, hipMemcpyAsync(c->cons_rows_dev + 1, c->cons_rows_host + 1, sizeof(ConstraintRow) * nd, hipMemcpyHostToDevice, st));
+            if (n_greedy > n_plain || rb.any_cons_sampled) HIPCHK(c, hipMemcpyAsync(c->cons_rows_dev + 1, c->cons_rows_host + 1, sizeof(ConstraintRow) * nd, hipMemcpyHostToDevice, st));
             ProfScope ps(c, MMD_K_OTHER, 0, 0);
-            if (nc) {          // constrained arg-max: the chain's scores with nothing filtered, then the first maximal index of z.  (The sampled rows below reuse the scratch: same stream.)
-                HIPCHK(c, launch_sample_scores_unfiltered(c->round_logits + (size_t)n_plain * V, V, nc, c->samp_rows_dev + 1, nullptr, c->samp_scratch, st, c->cons_rows_dev + 1));
-                HIPCHK(c, launch_argmax_scores(V, nc, c->samp_rows_dev + 1, nullptr, c->samp_scratch, c->round_toks_dev + n_plain, st));
-            }
-            if (ns) HIPCHK(c, launch_sample_batch_topkp(c->round_logits + (size_t)n_greedy * V, V, ns, c->samp_rows_dev + 1 + nc, any_k, any_p, nullptr, c->round_toks_dev + n_greedy, nullptr, nullptr,
-                                                        c->samp_scratch, st, nullptr, any_cons_sampled ? c->cons_rows_dev + 1 + nc : nullptr));
+            if (n_greedy > n_plain) HIPCHK(c, block(SEL_CONS_ARGMAX));
+            if (n_sample > n_greedy) HIPCHK(c, block(SEL_DRAW));
         }
         HIPCHK(c, hipMemcpyAsync(c->round_toks_host, c->round_toks_dev, sizeof(int64_t) * n_sample, hipMemcpyDeviceToHost, st));
     }
@@ -1970,69 +2017,47 @@ extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int
     return MMD_OK;
 }
 
-// log-probabilities behind an arg-max over logits_ws: the chain's scores for row descriptor 0 (T = 1, no filter: the penalty alone), then the record
-static int greedy_logprobs_enqueue(mmd_ctx* c, const LogprobOut& lp) {
-    const int V = c->cfg.vocab_size; hipStream_t st = c->stream;
-    HIPCHK(c, launch_sample_scores_unfiltered(c->logits_ws, V, 1, c->samp_rows_dev, nullptr, c->samp_scratch, st));
-    HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, lp, true, nullptr, c->samp_scratch, c->lp_scratch, st));
-    return MMD_OK;
+// what a generate call's selection launches over: the context's one-row buffers -- logits_ws, row / constraint descriptor 0, tok_dev; the plain arg-max takes the penalty list
+// in kernel arguments (dyn: its length from *dyn)
+static SelectIO generate_select_io(mmd_ctx* c, const SelectPlan& p, bool pen, float rep_penalty, int np, const StepState* dyn, const LogprobOut* lp) {
+    SelectIO io{};
+    io.logits = c->logits_ws; io.V = c->cfg.vocab_size; io.n = 1; io.rows = c->samp_rows_dev; io.cons = c->cons_rows_dev; io.lp = lp;
+    io.toks = p.kind == SEL_DRAW ? nullptr : c->tok_dev;          // (the draw's row descriptor names tok_dev itself)
+    io.scratch = c->samp_scratch; io.lp_scratch = c->lp_scratch; io.am_scratch = c->argmax_scratch;
+    io.prev = c->prev_dev; io.n_prev = pen ? (np < c->prev_cap ? np : c->prev_cap) : 0; io.penalty = pen ? rep_penalty : 1.f; io.dyn = dyn;
+    return io;
 }
 
-// the constrained arg-max over logits_ws: the chain's scores for row descriptor 0 under constraint descriptor 0 (T = 1, no filter), the first maximal index of them into
-// tok_dev, and -- recording on -- the record from the same scores
-static int constrained_argmax_enqueue(mmd_ctx* c, const ConstraintRow* cons, const LogprobOut* lp) {
-    const int V = c->cfg.vocab_size; hipStream_t st = c->stream;
-    HIPCHK(c, launch_sample_scores_unfiltered(c->logits_ws, V, 1, c->samp_rows_dev, nullptr, c->samp_scratch, st, cons));
-    HIPCHK(c, launch_argmax_scores(V, 1, c->samp_rows_dev, nullptr, c->samp_scratch, c->tok_dev, st));
-    if (lp) HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, *lp, true, nullptr, c->samp_scratch, c->lp_scratch, st));
-    return MMD_OK;
-}
-
-// one decode step (feed the previously drawn token, draw the next) enqueued on the stream; `dyn` selects the
-// graph-capturable form that reads position / arena / penalty-list length from device state
-// `samp`: the sampling chain over row descriptor 0 takes the arg-max's place; its penalty list always grows on the device
-// `lp`: the step records its token's log-probabilities (the kernels stand between the choice of the token and the state's advance)
-// `cons`: constraint descriptor 0 on the device (DESIGN.md "Constraints"): the chain's scores take it; the arg-max becomes the first maximal index of those scores (row
-// descriptor 0 is then posted for every arg-max step, as for the log-probabilities); the state's advance tests the EOS set
-static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const SampleCall* samp = nullptr,
-                               const LogprobOut* lp = nullptr, const ConstraintRow* cons = nullptr) {
+// one decode step (feed the previously drawn token, choose the next as `sel` says) enqueued on the stream; `dyn` selects the graph-capturable form that reads position / arena /
+// penalty-list length from device state.  `lp`: where the step records (the kernels stand between the choice of the token and the state's advance)
+static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, const SelectPlan& sel, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const LogprobOut* lp) {
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size;
     // the next token's embedding is gathered straight into the residual-stream buffer (llm_step_segs skips its copy when embeds == l_h)
     HIPCHK(c, launch_embed(g.dtype, c->embed, c->tok_dev, 1, H, g.vocab_size, c->l_h, st));
     int rc = llm_step_impl(c, s, c->l_h, 1, nullptr, dyn); if (rc) return rc;
     rc = gemm(c, c->l_hid, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, g.vocab_size, 1, g.vocab_size, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-    if (samp) {
-        HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, g.vocab_size, 1, c->samp_rows_dev, samp->any_k, samp->any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lp, cons));
-        if (lp) HIPCHK(c, launch_logprob_rows(c->logits_ws, g.vocab_size, 1, *lp, false, nullptr, c->samp_scratch, c->lp_scratch, st));
-        HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st, cons));
-        return MMD_OK;
-    }
-    if (cons) { rc = constrained_argmax_enqueue(c, cons, lp); if (rc) return rc; }
-    else {
-        HIPCHK(c, launch_argmax_penalty(c->logits_ws, g.vocab_size, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, dyn, c->argmax_scratch));
-        if (lp) { rc = greedy_logprobs_enqueue(c, *lp); if (rc) return rc; }
-    }
-    if (dyn) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st, cons));
+    HIPCHK(c, select_enqueue(c, sel, generate_select_io(c, sel, pen, rep_penalty, np, dyn, lp)));
+    if (sel.advance) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st, sel.needs_cons ? c->cons_rows_dev : nullptr));
     return MMD_OK;
 }
 
-// captures one dynamic decode step into dg for the key (key_pen, eos_id, sel).  Capture runs on the context's own stream (the legacy null stream -- torch's default --
+// captures one dynamic decode step into dg for the key (key_pen, eos_id, the plan's key).  Capture runs on the context's own stream (the legacy null stream -- torch's default --
 // cannot be captured); the instantiated graph is then launched on whatever stream the caller bound
-static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, bool pen, float rep_penalty, int np, int64_t eos_id, const SampleCall* samp, float key_pen, int sel, const LogprobOut* lp,
-                               const ConstraintRow* cons, uint32_t cons_gen) {
+static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, const SelectPlan& sel, const GeneratePlan& gp, bool pen, float rep_penalty, int np, int64_t eos_id, float key_pen,
+                               const LogprobOut* lp) {
     hipStream_t st = c->stream;
     dg.drop();
     HIPCHK(c, hipStreamSynchronize(st));
     c->stream = c->own_stream;
     hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
     if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
-    int rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, c->step_dev, samp, lp, cons);
+    int rc = decode_step_enqueue(c, s, sel, pen, rep_penalty, np, eos_id, c->step_dev, lp);
     hipError_t ce = hipStreamEndCapture(c->own_stream, &dg.src);
     c->stream = st;
     if (rc) { dg.drop(); return rc; }
     HIPCHK(c, ce);
     HIPCHK(c, hipGraphInstantiate(&dg.exec, dg.src, nullptr, nullptr, 0));
-    dg.pen = key_pen; dg.eos = eos_id; dg.sel = sel; dg.lp = lp ? lp->top_n : -1; dg.cons = cons_gen;
+    dg.pen = key_pen; dg.eos = eos_id; dg.sel = gp.key_sel; dg.lp = gp.key_lp; dg.cons = gp.key_cons_gen;
     return MMD_OK;
 }
 
@@ -2066,13 +2091,13 @@ static int logprob_reserve(mmd_ctx* c, int need) {
 }
 
 // ---- the token loop of a response: prompt step, then one token in, one token out --------------------------------------------------------------------------
-// samp == nullptr: arg-max (+ repetition penalty).  Otherwise the sampling chain of sample.hip stands where the arg-max stood.  Everything the chain needs per step is
-// in row descriptor 0 on the device: the penalty-list length is read through &step_dev->n_prev and grown by advance_state_kernel, the Philox offset is advanced by the
-// draw kernel, so the captured step is replayed as it is for any temperature / top_k / top_p / seed.  Draw i of the call uses offset *offset_inout + i; *offset_inout
-// advances with every token read (EOS included).  *n_out is up to date whenever the call returns.
-// Log-probabilities (mmd_set_generate_logprobs): every step, the prompt's included, records behind its draw into lp_rec[step]; the captured step reads its index from
-// step_dev->step.  After an arg-max the chain's scores run over row descriptor 0 (T = 1, nothing filtered); on the eager route that descriptor is posted again before every
-// step, because there the list length rides in kernel arguments.  Nothing is read back here: mmd_generate_logprobs_read copies the records once.
+// samp == nullptr: arg-max (+ repetition penalty).  Otherwise the sampling chain of sample.hip stands where the arg-max stood.  Which launches choose a token is
+// select_plan()'s answer, what surrounds them -- captured or eager steps, which descriptor is posted when, who grows the penalty list -- generate_plan()'s (select_plan.h);
+// this function follows the two.  Everything the chain needs per step is in row descriptor 0 on the device: the penalty-list length is read through &step_dev->n_prev and
+// grown by advance_state_kernel, the Philox offset is advanced by the draw kernel, so the captured step is replayed as it is for any temperature / top_k / top_p / seed.
+// Draw i of the call uses offset *offset_inout + i; *offset_inout advances with every token read (EOS included).  *n_out is up to date whenever the call returns.
+// Log-probabilities (mmd_set_generate_logprobs): every step, the prompt's included, records behind its choice into lp_rec[step]; the captured step reads its index from
+// step_dev->step.  Nothing is read back here: mmd_generate_logprobs_read copies the records once.
 static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
                          int64_t* out_ids_host, int max_new, int* n_out, const SampleArgs* samp) {
     c->dec_route = 0; *n_out = 0;
@@ -2084,17 +2109,17 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     int rc;
     if (samp) { rc = check_sampling(c, samp->temperature, samp->top_k, samp->top_p); if (rc) return rc; }
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size, V = g.vocab_size; const size_t e = es(c);
+    const bool cons_on = c->cons.on;
+    const SelectPlan sel0 = select_plan(select_rows(samp != nullptr, cons_on, lp_on, 1, true, false, V, samp));          // the prompt step's choice
+    rc = select_refused(c, sel0); if (rc) return rc;
     const bool pen = rep_penalty > 0.f;
     int np = (pen && n_prev) ? *n_prev : 0;
     if (pen) { rc = penalty_reserve(c, np + max_new); if (rc) return rc; }
-    const bool cons_on = c->cons.on;
-    if (cons_on && V > (1 << 18)) FAIL(c, MMD_ERANGE, "constraints handle vocabularies up to 2^18 entries");
-    if (samp || lp_on || cons_on) { rc = sample_reserve(c); if (rc) return rc; }
+    if (sel0.needs_row) { rc = sample_reserve(c); if (rc) return rc; }
     // constraints on: descriptor 0 on the device carries the EOS set (the call's own eos_id when the set is empty), min_new and the table; the captured step reads the response
     // step through &step_dev->step, an eager arg-max step gets it posted.  EOS below is membership of that set.
     ConstraintRow crow{};
     if (cons_on) cons_fill_row(crow, c->cons, c->cons_ids_dev, c->cons_bias_dev, eos_id, V, 0, nullptr);
-    const ConstraintRow* consp = cons_on ? c->cons_rows_dev : nullptr;
     auto post_cons = [&](bool dynamic, int step) -> int {
         crow.step = step; crow.step_ptr = dynamic ? &c->step_dev->step : nullptr;
         c->cons_rows_host[0] = crow;
@@ -2102,29 +2127,19 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         return MMD_OK;
     };
     auto is_eos = [&](int64_t t) -> bool { return cons_on ? cons_is_eos(crow, t) : t == eos_id; };
-    if (lp_on) {
-        if (V > (1 << 18)) FAIL(c, MMD_ERANGE, "log-probabilities handle vocabularies up to 2^18 entries");
-        rc = logprob_reserve(c, max_new); if (rc) return rc;
-    }
+    if (lp_on) { rc = logprob_reserve(c, max_new); if (rc) return rc; }
     if (np > 0) HIPCHK(c, hipMemcpyAsync(c->prev_dev, prev_ids_host, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
-    const SampleCall call = samp ? sample_call(*samp, V) : SampleCall{false, false};
-    const SampleCall* callp = samp ? &call : nullptr;
-    auto post_row = [&](bool dynamic) -> int {          // (every earlier upload from this staging slot has been waited for: a token read lies in between)
-        fill_sample_row(c->samp_rows_host[0], *samp, c->prev_dev, pen, np < c->prev_cap ? np : c->prev_cap, c->prev_cap, rep_penalty, dynamic ? &c->step_dev->n_prev : nullptr,
-                        c->tok_dev, nullptr, c->sample_lane, 1);
-        HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
-        return MMD_OK;
-    };
     uint64_t no_offset = 0;
-    auto post_lp_row = [&](bool dynamic) -> int {          // the arg-max's descriptor for the log-probability scores: the penalty at T = 1, no filter, no draw
+    // row descriptor 0: the draw's row, or -- behind an arg-max -- the row of the scores that the constraints and the records read: the penalty at T = 1, no filter, no draw.
+    // (Every earlier upload from this staging slot has been waited for: a token read lies in between.)
+    auto post_row = [&](bool dynamic) -> int {
         const SampleArgs plain{1.f, 0, 1.f, 0, &no_offset};
-        fill_sample_row(c->samp_rows_host[0], plain, c->prev_dev, pen, np < c->prev_cap ? np : c->prev_cap, c->prev_cap, rep_penalty, dynamic ? &c->step_dev->n_prev : nullptr,
-                        nullptr, nullptr, 0, 0);
+        fill_sample_row(c->samp_rows_host[0], samp ? *samp : plain, c->prev_dev, pen, np < c->prev_cap ? np : c->prev_cap, c->prev_cap, rep_penalty, dynamic ? &c->step_dev->n_prev : nullptr,
+                        samp ? c->tok_dev : nullptr, nullptr, samp ? c->sample_lane : 0, samp ? 1 : 0);
         HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
         return MMD_OK;
     };
     LogprobOut lpo{c->lp_rec, c->lp_cap, nullptr, 0, c->tok_dev, lp_top};
-    const LogprobOut* lpp = lp_on ? &lpo : nullptr;
     int produced = 0;
     auto read_token = [&](int64_t* tok) -> int {
         HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -2140,17 +2155,10 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     {
         const void* last = (const char*)c->l_hid + (size_t)(S - 1) * H * e;
         rc = gemm(c, last, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, V, 1, V, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-        if (samp) { rc = post_row(false); if (rc) return rc; }
-        else if (lp_on || cons_on) { rc = post_lp_row(false); if (rc) return rc; }
-        if (cons_on) { rc = post_cons(false, 0); if (rc) return rc; }
+        if (sel0.needs_row) { rc = post_row(false); if (rc) return rc; }
+        if (sel0.needs_cons) { rc = post_cons(false, 0); if (rc) return rc; }
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        if (samp) {
-            HIPCHK(c, launch_sample_batch_topkp(c->logits_ws, V, 1, c->samp_rows_dev, call.any_k, call.any_p, nullptr, nullptr, nullptr, nullptr, c->samp_scratch, st, lpp, consp));
-            if (lp_on) HIPCHK(c, launch_logprob_rows(c->logits_ws, V, 1, lpo, false, nullptr, c->samp_scratch, c->lp_scratch, st));
-        }
-        else if (cons_on) { rc = constrained_argmax_enqueue(c, consp, lpp); if (rc) return rc; }
-        else HIPCHK(c, launch_argmax_penalty(c->logits_ws, V, c->prev_dev, pen ? (np < c->prev_cap ? np : c->prev_cap) : 0, pen ? rep_penalty : 1.f, c->tok_dev, st, nullptr, c->argmax_scratch));
-        if (lp_on && !samp && !cons_on) { rc = greedy_logprobs_enqueue(c, lpo); if (rc) return rc; }
+        HIPCHK(c, select_enqueue(c, sel0, generate_select_io(c, sel0, pen, rep_penalty, np, nullptr, &lpo)));
     }
     int64_t tok = 0;
     rc = read_token(&tok); if (rc) return rc;
@@ -2161,47 +2169,48 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
         ++np;
     }
-    // steps 1..: one token in, one token out.  bf16 + fused schedule: replay a captured hipGraph of the whole step
-    // (~255 kernels) instead of launching them one by one -- the decode step is made of 5-50 us kernels and is otherwise
-    // paced by host launch latency.
-    const bool more = !stop && max_new > 1;
-    const bool can_graph = more && !c->no_graph && !c->sw.no_fuse && c->prof.on == 0 && g.dtype == MMD_BF16 && c->L[0].wqkv_p != nullptr &&
-                           g.hidden_size <= 4096 && g.head_dim == 128;     // head_dim 128: the attention kernel that reads *dyn
-    if (can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
-    if (can_graph || (samp && more)) {          // the sampled step reads the list length through *step_dev on the eager route too
+    // steps 1..: one token in, one token out
+    GenerateShape shape;
+    shape.sampled = samp != nullptr; shape.constrained = cons_on; shape.record = lp_on; shape.pen = pen; shape.max_new = max_new; shape.first_is_eos = stop;
+    shape.V = V; if (samp) { shape.top_k = samp->top_k; shape.top_p = samp->top_p; }
+    shape.lp_top = lp_top; shape.cons_gen = c->cons_gen;
+    shape.gate.no_graph = c->no_graph; shape.gate.no_fuse = c->sw.no_fuse; shape.gate.prof_on = c->prof.on != 0; shape.gate.dtype = g.dtype; shape.gate.qkv_p = c->L[0].wqkv_p != nullptr;
+    shape.gate.H = g.hidden_size; shape.gate.d = g.head_dim;
+    const GeneratePlan gp = generate_plan(shape);
+    const SelectPlan sel = select_plan(select_rows(samp != nullptr, cons_on, lp_on, 1, true, gp.can_graph, V, samp));          // the steps' choice
+    c->select_last[SELECT_PLAN_FIELDS] = SELECT_OF_GENERATE; gp.fields(c->select_last + SELECT_PLAN_FIELDS + 1);
+    if (gp.can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
+    if (gp.upload_state) {
         StepState* hs = c->step_host;
         hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->step = 1; hs->pos_off = s->pos_off;
         HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
     }
-    if (samp && more) { rc = post_row(true); if (rc) return rc; }
-    if ((lp_on || cons_on) && !samp && can_graph) { rc = post_lp_row(true); if (rc) return rc; }
-    if (cons_on && (can_graph || (samp && more))) { rc = post_cons(true, 1); if (rc) return rc; }
-    if (can_graph) lpo.dyn = c->step_dev;
+    if (gp.post_row_dynamic) { rc = post_row(true); if (rc) return rc; }
+    if (gp.post_cons_dynamic) { rc = post_cons(true, 1); if (rc) return rc; }
+    if (gp.can_graph) lpo.dyn = c->step_dev;
     DecodeGraph& dg = samp ? c->dec_sampled : c->dec_greedy;
-    if (can_graph) {
-        // arg-max: the penalty value rides in a kernel argument.  sampled: the value is in the row descriptor, the step holds penalty on / off and which filters run
-        const float key_pen = pen ? (samp ? 1.f : rep_penalty) : 0.f;
-        const int sel = (call.any_k ? 1 : 0) | (call.any_p ? 2 : 0);
+    if (gp.can_graph) {
+        const float key_pen = pen ? (gp.pen_key_is_value ? rep_penalty : 1.f) : 0.f;
         c->dec_route = 1;
-        const uint32_t cons_gen = cons_on ? c->cons_gen : 0;
-        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != sel || dg.lp != lp_top || dg.cons != cons_gen) {
-            rc = capture_decode_step(c, s, dg, pen, rep_penalty, np, eos_id, callp, key_pen, sel, lpp, consp, cons_gen); if (rc) { c->dec_route = 0; return rc; }
+        if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != gp.key_sel || dg.lp != gp.key_lp || dg.cons != gp.key_cons_gen) {
+            rc = capture_decode_step(c, s, dg, sel, gp, pen, rep_penalty, np, eos_id, key_pen, &lpo); if (rc) { c->dec_route = 0; return rc; }
             c->dec_route = 2;
         }
+        sel.fields(c->select_last);          // the plan the replayed step was captured from
     }
     for (int i = 1; i < max_new && !stop; ++i) {
-        if (can_graph) { HIPCHK(c, hipGraphLaunch(dg.exec, st)); s->len += 1; }
+        if (gp.can_graph) { HIPCHK(c, hipGraphLaunch(dg.exec, st)); s->len += 1; }
         else {
-            if ((lp_on || cons_on) && !samp) { rc = post_lp_row(false); if (rc) return rc; }
-            if (cons_on && !samp) { rc = post_cons(false, i); if (rc) return rc; }
+            if (gp.post_row_each_eager_step) { rc = post_row(false); if (rc) return rc; }
+            if (gp.post_cons_each_eager_step) { rc = post_cons(false, i); if (rc) return rc; }
             lpo.idx0 = i;
-            rc = decode_step_enqueue(c, s, pen, rep_penalty, np, eos_id, nullptr, callp, lpp, consp); if (rc) return rc;
+            rc = decode_step_enqueue(c, s, sel, pen, rep_penalty, np, eos_id, nullptr, &lpo); if (rc) return rc;
         }
         rc = read_token(&tok); if (rc) return rc;
         out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
         if (is_eos(tok)) break;
-        if (pen) {          // (arg-max, eager: the list grows by a copy here; every other route grows it in advance_state_kernel)
-            if (!samp && !can_graph && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (pen) {          // (the list grows by a copy here or in advance_state_kernel)
+            if (gp.host_appends_penalty && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
             if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
             ++np;
         }
@@ -2270,56 +2279,76 @@ extern "C" int mmd_generate_logprobs_read(mmd_ctx* c, float* logprob_host, float
     return MMD_OK;
 }
 
-// raw operator: n rows of logits through the sampling chain, one set of parameters, row i on lane i (MMD_ROUND_MAX_SAMPLERS rows per launch)
-// lp_host != null (mmd_op_sample_logprobs): the rows' log-probability records too; greedy: the multi-row arg-max with penalty stands in the draw's place
-static int op_sample_impl(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
-                          uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out,
-                          bool greedy, int top_n, float* lp_host, int64_t* top_ids_host, float* top_lp_host) {
-    if (!c) return MMD_EINVAL;
-    hipSetDevice(c->device);
+// raw operator: n rows of logits through the selection, one set of parameters, row i on lane i (MMD_ROUND_MAX_SAMPLERS rows per launch).  lp_host != null: the rows'
+// log-probability records too.  oc != null: one constraint set per row.  greedy: the arg-max stands in the draw's place -- the multi-row arg-max with penalty, under
+// constraints the first maximal index of the unfiltered scores (select_plan decides).  fail_no_token: a row without a token (-1) fails the call with MMD_EDOM.
+struct OpConstraints { const ConsSet* sets; const int32_t* tab_off; const int32_t* step; };          // row i's table: entries [tab_off[i], tab_off[i + 1]) of the tables back to back
+// the argument checks the three entries share (`who` names the entry in the message); greedy: the chain's parameters are those of the unfiltered scores
+static int op_select_check(mmd_ctx* c, const char* who, const float* logits, const int64_t* tokens_out, const float* info_out, bool greedy, int n, int V, int n_prev,
+                           const int64_t* prev_ids_dev, float& temperature, int& top_k, float& top_p) {
     if (greedy) { temperature = 1.f; top_k = 0; top_p = 1.f; }
-    if (!logits || !tokens_out || (!info_out && !greedy) || n < 1 || n > 4096 || V < 1 || V > (1 << 18) || n_prev < 0 || (n_prev > 0 && !prev_ids_dev)) FAIL(c, MMD_EINVAL, "bad mmd_op_sample arguments");
+    if (!logits || !tokens_out || (!info_out && !greedy) || n < 1 || n > 4096 || V < 1 || V > SELECT_MAX_V || n_prev < 0 || (n_prev > 0 && !prev_ids_dev)) FAIL(c, MMD_EINVAL, "bad %s arguments", who);
     if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1");
+    return MMD_OK;
+}
+static int op_select_impl(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
+                          uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out,
+                          bool greedy, int top_n, float* lp_host, int64_t* top_ids_host, float* top_lp_host, const OpConstraints* oc, bool fail_no_token) {
     hipStream_t st = c->stream;
-    const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS;
-    std::vector<SampleRow> rows((size_t)n);
+    const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS, total = oc ? oc->tab_off[n] : 0;
     const SampleArgs a{temperature, top_k, top_p, seed, &offset};
-    for (int i = 0; i < n; ++i) fill_sample_row(rows[i], a, prev_ids_dev, rep_penalty > 0.f && n_prev > 0, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
-    SampleRow* rows_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
+    const bool pen_on = rep_penalty > 0.f && n_prev > 0;
+    const SelectPlan plan = select_plan(select_rows(!greedy, oc != nullptr, lp_host != nullptr, chunk, false, false, V, &a));          // of every chunk
+    SampleRow* rows_dev = nullptr; ConstraintRow* cons_dev = nullptr; int32_t* ids_dev = nullptr; float* bias_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
     LogprobRec* rec_dev = nullptr; void* lp_scratch = nullptr; void* am_scratch = nullptr;
-    int rc = MMD_OK;
     auto release = [&]() {
         hipStreamSynchronize(st);
-        if (rows_dev) hipFree(rows_dev); if (r_dev) hipFree(r_dev); if (scratch) hipFree(scratch);
-        if (rec_dev) hipFree(rec_dev); if (lp_scratch) hipFree(lp_scratch); if (am_scratch) hipFree(am_scratch);
+        if (rows_dev) hipFree(rows_dev); if (cons_dev) hipFree(cons_dev); if (ids_dev) hipFree(ids_dev); if (bias_dev) hipFree(bias_dev); if (r_dev) hipFree(r_dev);
+        if (scratch) hipFree(scratch); if (rec_dev) hipFree(rec_dev); if (lp_scratch) hipFree(lp_scratch); if (am_scratch) hipFree(am_scratch);
     };
 #define OPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { release(); FAIL(c, MMD_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
+    std::vector<SampleRow> rows((size_t)n); std::vector<ConstraintRow> crows(oc ? (size_t)n : 0); std::vector<int32_t> ids((size_t)(total > 0 ? total : 1)); std::vector<float> bias(ids.size());
     OPCHK(hipMalloc((void**)&rows_dev, sizeof(SampleRow) * n));
     OPCHK(hipMalloc(&scratch, sample_topkp_scratch_bytes(V, chunk, scores_out == nullptr)));
-    OPCHK(hipMemcpyAsync(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice, st));
-    if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpyAsync(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice, st)); }
-    if (lp_host) { OPCHK(hipMalloc((void**)&rec_dev, sizeof(LogprobRec) * n)); OPCHK(hipMalloc(&lp_scratch, logprob_scratch_bytes(chunk))); }
-    if (greedy) OPCHK(hipMalloc(&am_scratch, sample_batch_scratch_bytes()));
-    const SampleCall call = sample_call(a, V);
-    const bool pen_on = rep_penalty > 0.f && n_prev > 0;
+    if (oc) {
+        OPCHK(hipMalloc((void**)&cons_dev, sizeof(ConstraintRow) * n));
+        OPCHK(hipMalloc((void**)&ids_dev, sizeof(int32_t) * ids.size()));
+        OPCHK(hipMalloc((void**)&bias_dev, sizeof(float) * bias.size()));
+    }
+    for (int i = 0; i < n; ++i) {
+        fill_sample_row(rows[i], a, prev_ids_dev, pen_on, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
+        if (!oc) continue;
+        const int o = oc->tab_off[i];
+        for (int k = 0; k < oc->sets[i].n; ++k) { ids[o + k] = oc->sets[i].ids[k]; bias[o + k] = oc->sets[i].bias[k]; }          // (sorted by cons_validate)
+        cons_fill_row(crows[i], oc->sets[i], ids_dev + o, bias_dev + o, -1, V, oc->step[i], nullptr);
+    }
+    // (synchronous copies: the vectors above are pageable)
+    OPCHK(hipMemcpy(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice));
+    if (oc) {
+        OPCHK(hipMemcpy(cons_dev, crows.data(), sizeof(ConstraintRow) * n, hipMemcpyHostToDevice));
+        OPCHK(hipMemcpy(ids_dev, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
+        OPCHK(hipMemcpy(bias_dev, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice));
+    }
+    if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpy(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice)); }
+    if (plan.record) { OPCHK(hipMalloc((void**)&rec_dev, sizeof(LogprobRec) * n)); OPCHK(hipMalloc(&lp_scratch, logprob_scratch_bytes(chunk))); }
+    if (plan.kind == SEL_ARGMAX) OPCHK(hipMalloc(&am_scratch, sample_batch_scratch_bytes()));
+    c->select_last[SELECT_PLAN_FIELDS] = SELECT_OF_OP;
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = n - i0 < chunk ? n - i0 : chunk;
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        const float* lg = logits + (size_t)i0 * V; float* sc = scores_out ? scores_out + (size_t)i0 * V : nullptr;
         const LogprobOut lpo{rec_dev, n, nullptr, i0, tokens_out + i0, top_n};
-        if (greedy) {
-            SampleBatch b{};
-            for (int r = 0; r < m; ++r) { b.prev[r] = prev_ids_dev; b.tok[r] = tokens_out + i0 + r; b.append[r] = nullptr; b.n_prev[r] = pen_on ? n_prev : 0; b.penalty[r] = pen_on ? rep_penalty : 1.f; }
-            OPCHK(launch_sample_batch(lg, V, b, m, tokens_out + i0, am_scratch, st));
-            OPCHK(launch_sample_scores_unfiltered(lg, V, m, rows_dev + i0, sc, scratch, st));
-        } else {
-            OPCHK(launch_sample_batch_topkp(lg, V, m, rows_dev + i0, call.any_k, call.any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4, sc, scratch, st,
-                                            lp_host ? &lpo : nullptr));
-        }
-        if (lp_host) OPCHK(launch_logprob_rows(lg, V, m, lpo, greedy, sc, scratch, lp_scratch, st));
+        SampleBatch b{};
+        for (int r = 0; r < m; ++r) { b.prev[r] = prev_ids_dev; b.tok[r] = tokens_out + i0 + r; b.append[r] = nullptr; b.n_prev[r] = pen_on ? n_prev : 0; b.penalty[r] = pen_on ? rep_penalty : 1.f; }
+        SelectIO io{};
+        io.logits = logits + (size_t)i0 * V; io.V = V; io.n = m; io.rows = rows_dev + i0; io.cons = oc ? cons_dev + i0 : nullptr; io.lp = &lpo; io.toks = tokens_out + i0;
+        io.scratch = scratch; io.lp_scratch = lp_scratch; io.am_scratch = am_scratch; io.batch = &b;
+        io.r_words = r_dev ? r_dev + i0 : nullptr; io.info = info_out ? info_out + (size_t)i0 * 4 : nullptr; io.scores = scores_out ? scores_out + (size_t)i0 * V : nullptr;
+        OPCHK(select_enqueue(c, plan, io));
     }
     OPCHK(hipStreamSynchronize(st));
-    if (lp_host) {
+    std::vector<int64_t> toks(fail_no_token ? (size_t)n : 0);
+    if (fail_no_token) OPCHK(hipMemcpy(toks.data(), tokens_out, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+    if (plan.record) {
         std::vector<LogprobRec> h((size_t)n);
         OPCHK(hipMemcpy(h.data(), rec_dev, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost));
         std::vector<float> l1((size_t)n), l2((size_t)n);
@@ -2328,12 +2357,17 @@ static int op_sample_impl(mmd_ctx* c, const float* logits, int n, int V, const i
     }
 #undef OPCHK
     release();
-    return rc;
+    for (size_t i = 0; i < toks.size(); ++i) if (toks[i] < 0) FAIL(c, MMD_EDOM, "row %d: a NaN among the logits, or every score is -inf under the constraints: no token drawn", (int)i);
+    return MMD_OK;
 }
 
 extern "C" int mmd_op_sample(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
                              uint64_t seed, uint64_t offset, const uint64_t* r_host, int64_t* tokens_out, float* info_out, float* scores_out) {
-    return op_sample_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, false, 0, nullptr, nullptr, nullptr);
+    if (!c) return MMD_EINVAL;
+    hipSetDevice(c->device);
+    int rc = op_select_check(c, "mmd_op_sample", logits, tokens_out, info_out, false, n, V, n_prev, prev_ids_dev, temperature, top_k, top_p); if (rc) return rc;
+    return op_select_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, false, 0, nullptr, nullptr, nullptr,
+                          nullptr, false);
 }
 
 extern "C" int mmd_op_sample_logprobs(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
@@ -2342,12 +2376,15 @@ extern "C" int mmd_op_sample_logprobs(mmd_ctx* c, const float* logits, int n, in
     if (!c) return MMD_EINVAL;
     if (top_n < 0 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "top_n 0..%d, got %d", LP_MAX_TOP, top_n);
     if (!lp_out_host || (top_n > 0 && (!top_ids_out_host || !top_lp_out_host))) FAIL(c, MMD_EINVAL, "bad mmd_op_sample_logprobs arguments");
-    return op_sample_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, greedy != 0, top_n,
-                          lp_out_host, top_ids_out_host, top_lp_out_host);
+    hipSetDevice(c->device);
+    int rc = op_select_check(c, "mmd_op_sample", logits, tokens_out, info_out, greedy != 0, n, V, n_prev, prev_ids_dev, temperature, top_k, top_p); if (rc) return rc;
+    // (greedy without constraints: the multi-row arg-max with penalty, then the unfiltered scores for the record -- SEL_ARGMAX over a block, not the constrained route)
+    return op_select_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, greedy != 0, top_n,
+                          lp_out_host, top_ids_out_host, top_lp_out_host, nullptr, false);
 }
 
 // raw operator of the constrained chain: mmd_op_sample_logprobs with one constraint set per row.  Row i's table is entries [tab_off[i], tab_off[i + 1]) of tab_ids / tab_bias;
-// every set goes through cons_validate (the limits of mmd_set_generate_constraints).  greedy: the constrained arg-max (scores with nothing filtered, first maximal index).
+// every set goes through cons_validate (the limits of mmd_set_generate_constraints).  Unlike the two entries above, a row without a token fails the call.
 extern "C" int mmd_op_sample_constrained(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
                                          uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n,
                                          const int32_t* tab_off_host, const int32_t* tab_ids_host, const float* tab_bias_host, const int64_t* eos_host, const int32_t* n_eos_host,
@@ -2355,11 +2392,8 @@ extern "C" int mmd_op_sample_constrained(mmd_ctx* c, const float* logits, int n,
                                          int64_t* tokens_out, float* info_out, float* scores_out, float* lp_out_host, int64_t* top_ids_out_host, float* top_lp_out_host) {
     if (!c) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (greedy) { temperature = 1.f; top_k = 0; top_p = 1.f; }
-    if (!logits || !tokens_out || (!info_out && !greedy) || n < 1 || n > 4096 || V < 1 || V > (1 << 18) || n_prev < 0 || (n_prev > 0 && !prev_ids_dev) || !tab_off_host || !n_eos_host ||
-        !min_new_host || !step_host)
-        FAIL(c, MMD_EINVAL, "bad mmd_op_sample_constrained arguments");
-    if (!(temperature > 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)) FAIL(c, MMD_EINVAL, "sampling needs temperature > 0, top_k >= 0, 0 < top_p <= 1");
+    if (!tab_off_host || !n_eos_host || !min_new_host || !step_host) FAIL(c, MMD_EINVAL, "bad mmd_op_sample_constrained arguments");
+    int rc = op_select_check(c, "mmd_op_sample_constrained", logits, tokens_out, info_out, greedy != 0, n, V, n_prev, prev_ids_dev, temperature, top_k, top_p); if (rc) return rc;
     if (lp_out_host && (top_n < 0 || top_n > LP_MAX_TOP)) FAIL(c, MMD_ERANGE, "top_n 0..%d, got %d", LP_MAX_TOP, top_n);
     if (lp_out_host && top_n > 0 && (!top_ids_out_host || !top_lp_out_host)) FAIL(c, MMD_EINVAL, "bad mmd_op_sample_constrained arguments");
     if (tab_off_host[0] != 0) FAIL(c, MMD_EINVAL, "table offsets start at 0");
@@ -2367,69 +2401,13 @@ extern "C" int mmd_op_sample_constrained(mmd_ctx* c, const float* logits, int n,
     for (int i = 0; i < n; ++i) {
         const int o = tab_off_host[i], m = tab_off_host[i + 1] - o;
         if (m < 0 || step_host[i] < 0) FAIL(c, MMD_EINVAL, "row %d: bad table offsets or step", i);
-        int rc = cons_validate(c, V, eos_host ? eos_host + (size_t)i * CONS_MAX_EOS : nullptr, n_eos_host[i], min_new_host[i], tab_ids_host ? tab_ids_host + o : nullptr,
-                               tab_bias_host ? tab_bias_host + o : nullptr, m, sets[i]);
+        rc = cons_validate(c, V, eos_host ? eos_host + (size_t)i * CONS_MAX_EOS : nullptr, n_eos_host[i], min_new_host[i], tab_ids_host ? tab_ids_host + o : nullptr,
+                           tab_bias_host ? tab_bias_host + o : nullptr, m, sets[i]);
         if (rc) return rc;
     }
-    hipStream_t st = c->stream;
-    const int chunk = n < MMD_ROUND_MAX_SAMPLERS ? n : MMD_ROUND_MAX_SAMPLERS, total = tab_off_host[n];
-    SampleRow* rows_dev = nullptr; ConstraintRow* cons_dev = nullptr; int32_t* ids_dev = nullptr; float* bias_dev = nullptr; unsigned long long* r_dev = nullptr; void* scratch = nullptr;
-    LogprobRec* rec_dev = nullptr; void* lp_scratch = nullptr;
-    auto release = [&]() {
-        hipStreamSynchronize(st);
-        if (rows_dev) hipFree(rows_dev); if (cons_dev) hipFree(cons_dev); if (ids_dev) hipFree(ids_dev); if (bias_dev) hipFree(bias_dev); if (r_dev) hipFree(r_dev);
-        if (scratch) hipFree(scratch); if (rec_dev) hipFree(rec_dev); if (lp_scratch) hipFree(lp_scratch);
-    };
-#define OPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { release(); FAIL(c, MMD_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
-    OPCHK(hipMalloc((void**)&rows_dev, sizeof(SampleRow) * n));
-    OPCHK(hipMalloc((void**)&cons_dev, sizeof(ConstraintRow) * n));
-    OPCHK(hipMalloc((void**)&ids_dev, sizeof(int32_t) * (total > 0 ? total : 1)));
-    OPCHK(hipMalloc((void**)&bias_dev, sizeof(float) * (total > 0 ? total : 1)));
-    OPCHK(hipMalloc(&scratch, sample_topkp_scratch_bytes(V, chunk, scores_out == nullptr)));
-    std::vector<SampleRow> rows((size_t)n); std::vector<ConstraintRow> crows((size_t)n); std::vector<int32_t> ids((size_t)(total > 0 ? total : 1)); std::vector<float> bias(ids.size());
-    const SampleArgs a{temperature, top_k, top_p, seed, &offset};
-    for (int i = 0; i < n; ++i) {
-        fill_sample_row(rows[i], a, prev_ids_dev, rep_penalty > 0.f && n_prev > 0, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
-        const int o = tab_off_host[i];
-        for (int k = 0; k < sets[i].n; ++k) { ids[o + k] = sets[i].ids[k]; bias[o + k] = sets[i].bias[k]; }          // (sorted by cons_validate)
-        cons_fill_row(crows[i], sets[i], ids_dev + o, bias_dev + o, -1, V, step_host[i], nullptr);
-    }
-    // (synchronous copies: the vectors above are pageable)
-    OPCHK(hipMemcpy(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(cons_dev, crows.data(), sizeof(ConstraintRow) * n, hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(ids_dev, ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(bias_dev, bias.data(), sizeof(float) * bias.size(), hipMemcpyHostToDevice));
-    if (r_host) { OPCHK(hipMalloc((void**)&r_dev, sizeof(uint64_t) * n)); OPCHK(hipMemcpy(r_dev, r_host, sizeof(uint64_t) * n, hipMemcpyHostToDevice)); }
-    if (lp_out_host) { OPCHK(hipMalloc((void**)&rec_dev, sizeof(LogprobRec) * n)); OPCHK(hipMalloc(&lp_scratch, logprob_scratch_bytes(chunk))); }
-    const SampleCall call = sample_call(a, V);
-    for (int i0 = 0; i0 < n; i0 += chunk) {
-        const int m = n - i0 < chunk ? n - i0 : chunk;
-        ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        const float* lg = logits + (size_t)i0 * V; float* sc = scores_out ? scores_out + (size_t)i0 * V : nullptr;
-        const LogprobOut lpo{rec_dev, n, nullptr, i0, tokens_out + i0, top_n};
-        if (greedy) {
-            OPCHK(launch_sample_scores_unfiltered(lg, V, m, rows_dev + i0, sc, scratch, st, cons_dev + i0));
-            OPCHK(launch_argmax_scores(V, m, rows_dev + i0, sc, scratch, tokens_out + i0, st));
-        } else {
-            OPCHK(launch_sample_batch_topkp(lg, V, m, rows_dev + i0, call.any_k, call.any_p, r_dev ? r_dev + i0 : nullptr, tokens_out + i0, info_out + (size_t)i0 * 4, sc, scratch, st,
-                                            lp_out_host ? &lpo : nullptr, cons_dev + i0));
-        }
-        if (lp_out_host) OPCHK(launch_logprob_rows(lg, V, m, lpo, greedy != 0, sc, scratch, lp_scratch, st));
-    }
-    OPCHK(hipStreamSynchronize(st));
-    std::vector<int64_t> toks((size_t)n);
-    OPCHK(hipMemcpy(toks.data(), tokens_out, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-    if (lp_out_host) {
-        std::vector<LogprobRec> h((size_t)n);
-        OPCHK(hipMemcpy(h.data(), rec_dev, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost));
-        std::vector<float> l1((size_t)n), l2((size_t)n);
-        unpack_logprobs(h.data(), n, top_n, l1.data(), l2.data(), top_ids_out_host, top_lp_out_host);
-        for (int i = 0; i < n; ++i) { lp_out_host[2 * i] = l1[i]; lp_out_host[2 * i + 1] = l2[i]; }
-    }
-#undef OPCHK
-    release();
-    for (int i = 0; i < n; ++i) if (toks[i] < 0) FAIL(c, MMD_EDOM, "row %d: a NaN among the logits, or every score is -inf under the constraints: no token drawn", i);
-    return MMD_OK;
+    const OpConstraints oc{sets.data(), tab_off_host, step_host};
+    return op_select_impl(c, logits, n, V, prev_ids_dev, n_prev, rep_penalty, temperature, top_k, top_p, seed, offset, r_host, tokens_out, info_out, scores_out, greedy != 0, top_n,
+                          lp_out_host, top_ids_out_host, top_lp_out_host, &oc, true);
 }
 
 // ---- measurement -------------------------------------------------------------------------------------------------------
@@ -2547,6 +2525,7 @@ extern "C" int mmd_op_gemm_last_plan(mmd_ctx* c, int* out4) {
 // the decode steps of the most recent generate call: 0 none or eager, 1 replayed an existing captured step, 2 captured in that call, then replayed
 extern "C" int mmd_op_decode_last_route(mmd_ctx* c) { return c ? c->dec_route : MMD_EINVAL; }
 extern "C" int mmd_op_step_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < STEP_PLAN_FIELDS; ++i) out[i] = c->step_last[i]; return MMD_OK; }
+extern "C" int mmd_op_select_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < SELECT_LAST_FIELDS; ++i) out[i] = c->select_last[i]; return MMD_OK; }
 // times one GEMM shape on the context's stream with HIP events (weights packed once, outside the timed region)
 extern "C" int mmd_op_gemm_bench(mmd_ctx* c, int M, int N, int K, int epi, int variant, int iters, float* avg_ms_out, const void* Xin, const void* Win) {
     if (!c || !avg_ms_out || iters <= 0) return MMD_EINVAL;

@@ -940,6 +940,21 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         check(lib().mmd_op_step_last_plan(self._ctx, out), self._ctx, 'step_last_plan')
         return dict(zip(self.STEP_PLAN_FIELDS, out))
 
+    SELECT_PLAN_FIELDS = ('kind', 'single', 'any_k', 'any_p', 'needs_row', 'needs_cons', 'record', 'scores_after_argmax', 'record_greedy', 'advance')
+    GENERATE_PLAN_FIELDS = ('can_graph', 'upload_state', 'post_row_dynamic', 'post_row_each_eager_step', 'post_cons_dynamic', 'post_cons_each_eager_step', 'host_appends_penalty',
+                            'pen_key_is_value', 'key_sel', 'key_lp', 'key_cons_gen')
+    ROUND_BLOCKS_FIELDS = ('n_plain', 'n_greedy', 'n_sample', 'any_k', 'any_p', 'any_cons_sampled')
+
+    def select_last_plan(self):
+        """The plan the most recent token selection was launched from (mmd_op_select_last_plan): dict(select=..., generate=... | None, round=... | None) over the three field
+        lists above; kind 0 arg-max, 1 constrained arg-max, 2 draw.  generate / round: the plan of the generate call / round the selection belonged to."""
+        ns, ng = len(self.SELECT_PLAN_FIELDS), len(self.GENERATE_PLAN_FIELDS)
+        out = (C.c_int * (ns + 1 + ng))()
+        check(lib().mmd_op_select_last_plan(self._ctx, out), self._ctx, 'select_last_plan')
+        tail = out[ns + 1:]
+        return dict(select=dict(zip(self.SELECT_PLAN_FIELDS, out[:ns])), generate=dict(zip(self.GENERATE_PLAN_FIELDS, tail)) if out[ns] == 1 else None,
+                    round=dict(zip(self.ROUND_BLOCKS_FIELDS, tail)) if out[ns] == 2 else None)
+
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, frames=None, past_key_values=None, max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,
                  repetition_penalty=None, eos_token_id=None, seed=None, return_dict_in_generate=False, output_logprobs=False, top_logprobs=0, **kwargs):
