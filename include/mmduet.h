@@ -268,9 +268,21 @@ int mmd_set_sample_lane(mmd_ctx* ctx, int lane);
  * following generate calls of the context; anything else is MMD_ERANGE.  The captured decode step is keyed by the setting too.  The records stay on the device until
  * mmd_generate_logprobs_read copies those of the most recent generate call (ONE copy, then a stream synchronisation): logprob_host / sampling_logprob_host float[cap_tokens],
  * top_ids_host int64[cap_tokens, top_n], top_logprob_host float[cap_tokens, top_n] (host; each may be NULL); *n_out = that call's token count, 0 if it did not record;
- * MMD_ERANGE if cap_tokens is smaller.  mmd_round_multi does not record. */
+ * MMD_ERANGE if cap_tokens is smaller.
+ * mmd_round_multi records per sampler.  mmd_sampler_set_logprobs: -1 off (the default: a round enqueues and posts what it does without this feature), 0..8 on with that many
+ * alternatives, anything else MMD_ERANGE; refused for vocabularies above 2^18 like the context-wide setting.  It is called at a response boundary -- before
+ * mmd_sampler_begin, or after it and before the response's first sampled token -- and returns MMD_EINVAL once the running response has returned a token (a response is over
+ * with its EOS or its max_new-th token; switching then discards its records).  The records live in a sampler-owned device array sized for the response's max_new, grown (the
+ * stream drained first) at mmd_sampler_begin or here, whichever comes second.  In a round a recording sampler's row writes the record of its token into the slot of the
+ * response's token count; samplers that record, with different top_n, and samplers that do not may share a round, and a row's numbers do not depend on the others.  Nothing
+ * more crosses to the host per round and the round's one synchronisation stays one.  A round that fails with MMD_EDOM leaves the failing sampler's count where it was.
+ * mmd_sampler_logprobs_read: the records of the response begun by the most recent mmd_sampler_begin, shapes and meaning as mmd_generate_logprobs_read (logprob and the
+ * alternatives over the raw logits, sampling_logprob over z and its kept set, under constraints too); *n_out = the tokens that sampler's rounds have returned so far in the
+ * response (EOS included), 0 when the sampler does not record; ONE copy, then a stream synchronisation; MMD_ERANGE if cap_tokens is smaller than *n_out. */
 int mmd_set_generate_logprobs(mmd_ctx* ctx, int top_n);
 int mmd_generate_logprobs_read(mmd_ctx* ctx, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out);
+int mmd_sampler_set_logprobs(mmd_sampler* sp, int top_n);
+int mmd_sampler_logprobs_read(mmd_sampler* sp, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out);
 
 /* Constrained decoding (DESIGN.md "Constraints"; what HF generate gives the reference class through eos_token_id lists, min_new_tokens, suppress_tokens, single-token
  * bad_words_ids and sequence_bias, models/live_llava/video_head_live_llava_qwen.py:231).  For the fp32 lm_head logits l of a step the chain's score becomes
@@ -461,6 +473,9 @@ int mmd_op_step_last_plan(mmd_ctx* ctx, int* out9);
  * {can_graph, upload_state, post_row_dynamic, post_row_each_eager_step, post_cons_dynamic, post_cons_each_eager_step, host_appends_penalty, pen_key_is_value, key_sel, key_lp,
  * key_cons_gen}, a round's {n_plain, n_greedy, n_sample, any_k, any_p, any_cons_sampled} (the rest of the 11 unspecified) */
 int mmd_op_select_last_plan(mmd_ctx* ctx, int* out22);
+/* what the most recent round of this context recorded: out4 = {recording rows in the plain arg-max block, in the constrained arg-max block, in the sampled block, the largest
+ * top_n among them (-1: no row recorded)}; {0, 0, 0, -1} before the first round (tests assert that the record path ran, or did not) */
+int mmd_op_round_last_record(mmd_ctx* ctx, int* out4);
 int mmd_op_pool(mmd_ctx* ctx, const void* x, void* y, int B, int grid, int H, int mode, int stride);
 
 #ifdef __cplusplus

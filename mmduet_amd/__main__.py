@@ -50,8 +50,6 @@ def main(argv=None):
     for k, v in vars(sp.parse_known_args(sys.argv[1:] if argv is None else argv)[0]).items():
         setattr(args, k, v)
     args.output_logprobs, args.top_logprobs = args.logprobs is not None, args.logprobs or 0
-    if args.output_logprobs and args.streams_per_gpu > 1:
-        raise NotImplementedError('--logprobs: the multi-stream rounds (--streams_per_gpu > 1) record no log-probabilities')
     rank, world, local = init_distributed()
     if torch.cuda.is_available():
         torch.cuda.set_device(local)
@@ -163,6 +161,9 @@ def main(argv=None):
                     return make
 
                 def on_result(n, video, res):
+                    if args.output_logprobs:          # (as below: this file's own records)
+                        for turn, lp in zip([t for t in res['responses'] if t['role'] == 'assistant'], res.get('response_logprobs', ())):
+                            turn['logprobs'] = lp
                     rec = result_record(video['ex']['question_id'], res['responses'], video['duration'], res['debug_data'], evaluator_format=args.evaluator_format)
                     f_out.write(json.dumps(rec) + '\n')
                     f_out.flush()

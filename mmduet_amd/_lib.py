@@ -104,6 +104,8 @@ _SIGS = {
     'mmd_set_generate_constraints': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I]),
     'mmd_sampler_set_constraints': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I]),
     'mmd_generate_logprobs_read': (_I, [_VP, _VP, _VP, _VP, _VP, _I, C.POINTER(_I)]),
+    'mmd_sampler_set_logprobs': (_I, [_VP, _I]),
+    'mmd_sampler_logprobs_read': (_I, [_VP, _VP, _VP, _VP, _VP, _I, C.POINTER(_I)]),
     'mmd_prof_enable': (_I, [_VP, _I]),
     'mmd_prof_set_stride': (_I, [_VP, _I]),
     'mmd_prof_read': (_I, [_VP, _VP, _VP, _VP, _VP]),
@@ -136,6 +138,7 @@ _SIGS = {
     'mmd_op_decode_last_route': (_I, [_VP]),
     'mmd_op_step_last_plan': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_select_last_plan': (_I, [_VP, C.POINTER(_I)]),
+    'mmd_op_round_last_record': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_pool': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -171,10 +171,13 @@ struct ConstraintRow {
 __host__ __device__ inline bool cons_is_eos(const ConstraintRow& c, long long t) { for (int k = 0; k < c.n_eos; ++k) if (c.eos[k] == t) return true; return false; }
 // log-probability records (sample.hip): one per token.  lp = log-probability under the model (raw logits), slp = under the distribution the token was taken from, then the
 // top_n largest raw logits as ids (-1: the row is shorter) and their lp.  LogprobOut says where row r of a launch records: slot (dyn ? dyn->step : idx0) + r of rec[cap] (a slot
-// beyond cap is not written), for the token toks[r]; rec == null: nothing is recorded.
+// beyond cap is not written), for the token toks[r]; rec == null: nothing is recorded.  With `rows` (mmd_round_multi: every row belongs to another sampler) row r has a
+// destination of its own, in DEVICE memory: rows[r].rec[rows[r].slot] with its own top_n, nothing when rows[r].rec is null or the slot is beyond rows[r].cap; rec / cap / dyn /
+// idx0 / top_n of the LogprobOut are then unused.
 constexpr int LP_MAX_TOP = 8;
 struct LogprobRec { float lp, slp; float top_lp[LP_MAX_TOP]; int top_id[LP_MAX_TOP]; };
-struct LogprobOut { LogprobRec* rec; int cap; const StepState* dyn; int idx0; const int64_t* toks; int top_n; };
+struct LogprobRow { LogprobRec* rec; int slot, cap, top_n; };
+struct LogprobOut { LogprobRec* rec; int cap; const StepState* dyn; int idx0; const int64_t* toks; int top_n; const LogprobRow* rows = nullptr; };
 size_t sample_topkp_scratch_bytes(int V, int n, bool own_scores);          // n <= MMD_ROUND_MAX_SAMPLERS rows per launch; own_scores: the z rows live in the scratch
 hipError_t launch_sample_batch_topkp(const float* logits /*[n, V]*/, int V, int n, SampleRow* rows_dev, bool any_k, bool any_p, const unsigned long long* r_words_dev /* or null: Philox */,
                                      int64_t* toks_out_dev, float* info_out_dev /* [n,4] or null */, float* scores_out_dev /* [n,V] or null */, void* scratch, hipStream_t st,
@@ -185,8 +188,10 @@ hipError_t launch_sample_scores_unfiltered(const float* logits, int V, int n, co
                                            const ConstraintRow* cons_dev = nullptr);
 // the constrained arg-max: first maximal index of the z that launch_sample_scores_unfiltered left in `scratch` (-1: a NaN, or every z is -inf) -> rows[r].tok / .append, toks_out[r]
 hipError_t launch_argmax_scores(int V, int n, const SampleRow* rows_dev, float* scores_out_dev, void* scratch, int64_t* toks_out_dev /* or null */, hipStream_t st);
-// lp and the top_n of n <= MMD_ROUND_MAX_SAMPLERS rows; greedy: slp too, from what launch_sample_scores_unfiltered left in sample_scratch (same scores_out_dev)
-hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st);
+// lp and the top_n of n <= MMD_ROUND_MAX_SAMPLERS rows; greedy: slp too, from what launch_sample_scores_unfiltered left in sample_scratch (same scores_out_dev).  The scores
+// may have been launched over more rows than are recorded: over sw_rows rows (0: n), of which the launch's row 0 was row sw_row0
+hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st,
+                               int sw_rows = 0, int sw_row0 = 0);
 // streaming cross entropy over lm_head logit chunks (mmd_lm_nll; ops.hip): fold chunk `logits` [m, nc] (row stride ld, ld % 4 == 0; vocabulary columns [c0, c0 + nc)) into
 // state [m, 3] = (max, sum exp, label logit) -- `first`: the state starts empty -- through the one-writer partials part [m, lm_nll_splits(m, nc), 3]; then nll / lse from the state
 constexpr int LM_NLL_BLOCKS = 2048, LM_NLL_MAX_SPLITS = 256;          // blocks one chunk's reduce aims at; m * lm_nll_splits(m, nc) <= max(m, LM_NLL_BLOCKS)

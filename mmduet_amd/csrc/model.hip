@@ -126,6 +126,10 @@ struct mmd_ctx {
     hipEvent_t seg_event[8] = {};      // recorded behind a slot's upload: the pinned host slot is rewritten only once that copy has run (steps without a synchronisation may queue up)
     // mmd_round_multi (allocated at its first use): logits of the sampling rows, their gathered hidden rows, the two-stage argmax candidates, the drawn tokens
     float* round_logits = 0; void* round_hidden = 0; void* round_scratch = 0; int64_t* round_toks_dev = 0; int64_t* round_toks_host = 0;
+    // ... and, at the first round with a recording sampler: one record destination per logits row (device, pinned staging), the record kernels' scratch for a round's rows;
+    // what the most recent round recorded (mmd_op_round_last_record)
+    LogprobRow* round_lp_rows_dev = nullptr; LogprobRow* round_lp_rows_host = nullptr; void* round_lp_scratch = nullptr;
+    int round_record_last[ROUND_RECORD_FIELDS] = {0, 0, 0, -1};
     // mmd_lm_nll (allocated at its first use): one fp32 logit chunk [rows, chunk columns], the rows' (max, sum exp, label logit) and the one-writer partials of a chunk's reduce
     float* nll_ws = 0; size_t nll_ws_bytes = 0; float* nll_state = 0; float* nll_part = 0; int nll_rows = 0;
     // sampled decoding (allocated at its first use): row descriptors on the device ([0] mmd_sample_generate's, [1..] a round's) with their pinned staging, the chain's scratch
@@ -310,6 +314,7 @@ extern "C" void mmd_destroy(mmd_ctx* c) {
     if (c->step_host) hipHostFree(c->step_host);
     if (c->seg_host) hipHostFree(c->seg_host);
     if (c->round_toks_host) hipHostFree(c->round_toks_host);
+    if (c->round_lp_rows_host) hipHostFree(c->round_lp_rows_host);
     if (c->samp_rows_host) hipHostFree(c->samp_rows_host);
     if (c->cons_rows_host) hipHostFree(c->cons_rows_host);
     for (auto& ev : c->seg_event) if (ev) hipEventDestroy(ev);
@@ -1613,6 +1618,9 @@ struct mmd_sampler {
     bool sampling = false, seeded = false; float temperature = 1.f, top_p = 1.f; int top_k = 0; uint64_t seed = 0, offset = 0; uint32_t lane = 0;
     // constraints (mmd_sampler_set_constraints): the set, its table on the device (sampler-owned, uploaded synchronously), tokens returned so far in this response
     ConsSet cons; int32_t* cons_ids_dev = nullptr; float* cons_bias_dev = nullptr; int step = 0;
+    // log-probabilities (mmd_sampler_set_logprobs): the setting (-1 off), the device records of the current response (sampler-owned, sized for its max_new), how many of them
+    // the rounds have returned, and whether the response is over (EOS, or max_new tokens returned)
+    int lp_top = -1, lp_cap = 0, lp_n = 0, max_new = 0; LogprobRec* lp_rec = nullptr; bool ended = false;
 };
 
 // ---- constraints: validation and the device descriptors ------------------------------------------------------------------------------------------------------------------
@@ -1713,11 +1721,16 @@ struct SelectIO {
     const SampleBatch* batch = nullptr;          // SEL_ARGMAX over a block: the rows' lists and slots
     const int64_t* prev = nullptr; int n_prev = 0; float penalty = 1.f; const StepState* dyn = nullptr;          // SEL_ARGMAX, single: the list rides in kernel arguments
     const unsigned long long* r_words = nullptr; float* info = nullptr; float* scores = nullptr;          // the raw operator's: explicit random words, the draw's info, the z rows
+    // A round's block: only its tail [rec0, n) records.  The launches that exist for the record alone run over the tail; a draw writes sampling_logprob for every row whose
+    // LogprobRow names a destination.  SEL_ARGMAX: `rows` describes the tail's rows alone (the arg-max reads `batch`).  0: every row records (the generate calls, the operators).
+    int rec0 = 0;
 };
 static hipError_t select_enqueue(mmd_ctx* c, const SelectPlan& p, const SelectIO& io) {
     hipStream_t st = c->stream; hipError_t e = hipSuccess;
     const ConstraintRow* cons = p.needs_cons ? io.cons : nullptr;
     const LogprobOut* lp = p.record ? io.lp : nullptr;
+    const int t0 = p.record ? io.rec0 : 0, tn = io.n - t0;          // the recording tail
+    const float* tail_logits = io.logits + (size_t)t0 * io.V;
     p.fields(c->select_last);
     switch (p.kind) {
     case SEL_DRAW:          // (the draw records sampling_logprob itself)
@@ -1730,9 +1743,15 @@ static hipError_t select_enqueue(mmd_ctx* c, const SelectPlan& p, const SelectIO
     default:
         e = p.single ? launch_argmax_penalty(io.logits, io.V, io.prev, io.n_prev, io.penalty, io.toks, st, io.dyn, io.am_scratch)
                      : launch_sample_batch(io.logits, io.V, *io.batch, io.n, io.toks, io.am_scratch, st);
-        if (e == hipSuccess && p.scores_after_argmax) e = launch_sample_scores_unfiltered(io.logits, io.V, io.n, io.rows, io.scores, io.scratch, st);
+        if (e == hipSuccess && p.scores_after_argmax) e = launch_sample_scores_unfiltered(tail_logits, io.V, tn, io.rows, io.scores ? io.scores + (size_t)t0 * io.V : nullptr, io.scratch, st);
     }
-    if (e == hipSuccess && p.record) e = launch_logprob_rows(io.logits, io.V, io.n, *lp, p.record_greedy, io.scores, io.scratch, io.lp_scratch, st);
+    if (e == hipSuccess && p.record) {
+        LogprobOut tail = *lp;
+        tail.toks += t0; tail.idx0 += t0; if (tail.rows) tail.rows += t0;
+        const bool own_scores = p.kind == SEL_ARGMAX;          // the scores behind a plain arg-max ran over the tail alone; a constrained block's ran over all of its rows
+        e = launch_logprob_rows(tail_logits, io.V, tn, tail, p.record_greedy, own_scores && io.scores ? io.scores + (size_t)t0 * io.V : io.scores, io.scratch, io.lp_scratch, st,
+                                own_scores ? 0 : io.n, own_scores ? 0 : t0);
+    }
     return e;
 }
 
@@ -1755,13 +1774,29 @@ extern "C" void mmd_sampler_destroy(mmd_sampler* sp) {
     if (sp->prev_dev) hipFree(sp->prev_dev);
     if (sp->cons_ids_dev) hipFree(sp->cons_ids_dev);
     if (sp->cons_bias_dev) hipFree(sp->cons_bias_dev);
+    if (sp->lp_rec) hipFree(sp->lp_rec);
     delete sp;
+}
+// the records of a response: room for max_new of them once the sampler records.  Like the penalty list the array grows by doubling behind a drained stream
+static int sampler_lp_reserve(mmd_sampler* sp) {
+    mmd_ctx* c = sp->ctx;
+    const int need = sp->max_new > 0 ? sp->max_new : 1;
+    if (sp->lp_top < 0 || need <= sp->lp_cap) return MMD_OK;
+    int ncap = sp->lp_cap > 0 ? sp->lp_cap : 256;
+    while (ncap < need) ncap *= 2;
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (a round in flight may still write the old array)
+    if (sp->lp_rec) { hipFree(sp->lp_rec); sp->lp_rec = nullptr; sp->lp_cap = 0; }
+    if (hipMalloc((void**)&sp->lp_rec, (size_t)ncap * sizeof(LogprobRec)) != hipSuccess) FAIL(c, MMD_ENOMEM, "hipMalloc of %d log-probability records failed", ncap);
+    sp->lp_cap = ncap;
+    return MMD_OK;
 }
 extern "C" int mmd_sampler_begin(mmd_sampler* sp, int64_t eos_id, float rep_penalty, const int64_t* prev_ids_host, int n_prev, int max_new) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
     if (n_prev < 0 || max_new < 0 || (n_prev > 0 && !prev_ids_host)) FAIL(c, MMD_EINVAL, "bad sampler arguments");
     sp->eos = eos_id; sp->penalty = rep_penalty > 0.f ? rep_penalty : 0.f; sp->n_prev = 0; sp->step = 0;
+    sp->max_new = max_new; sp->lp_n = 0; sp->ended = false;
+    { const int rc = sampler_lp_reserve(sp); if (rc) return rc; }
     if (sp->penalty <= 0.f) return MMD_OK;
     const int need = n_prev + max_new + 1;          // (the slot behind the list receives every drawn token; it counts only when the token is not EOS)
     if (need > sp->prev_cap) {
@@ -1804,6 +1839,37 @@ extern "C" int mmd_sampler_set_constraints(mmd_sampler* sp, const int64_t* eos_i
     sp->cons = s;
     return MMD_OK;
 }
+static void unpack_logprobs(const LogprobRec* h, int n, int top_n, float* lp, float* slp, int64_t* top_ids, float* top_lp);
+extern "C" int mmd_sampler_set_logprobs(mmd_sampler* sp, int top_n) {
+    if (!sp) return MMD_EINVAL;
+    mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
+    if (top_n < -1 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "log-probability alternatives: -1 (off) or 0..%d, got %d", LP_MAX_TOP, top_n);
+    if (sp->step > 0 && !sp->ended) FAIL(c, MMD_EINVAL, "the response has returned %d token(s): log-probabilities are switched at a response boundary", sp->step);
+    if (top_n >= 0) { const int rc = select_refused(c, select_plan(select_rows(false, false, true, 1, false, false, c->cfg.vocab_size, nullptr))); if (rc) return rc; }
+    sp->lp_top = top_n; sp->lp_n = 0;          // (behind a finished response: its records go with the setting they were written under)
+    return sampler_lp_reserve(sp);
+}
+extern "C" int mmd_sampler_logprobs_read(mmd_sampler* sp, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out) {
+    if (!sp) return MMD_EINVAL;
+    mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
+    if (!n_out || cap_tokens < 0) FAIL(c, MMD_EINVAL, "bad mmd_sampler_logprobs_read arguments");
+    const int n = sp->lp_top >= 0 ? sp->lp_n : 0;
+    *n_out = n;
+    if (n == 0) return MMD_OK;
+    if (cap_tokens < n) FAIL(c, MMD_ERANGE, "%d records, room for %d", n, cap_tokens);
+    std::vector<LogprobRec> h((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(h.data(), sp->lp_rec, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unpack_logprobs(h.data(), n, sp->lp_top, logprob_host, sampling_logprob_host, top_ids_host, top_logprob_host);
+    return MMD_OK;
+}
+// the round's record descriptors and the record kernels' scratch for a round's rows
+static int round_record_reserve(mmd_ctx* c) {
+    if (c->round_lp_scratch) return MMD_OK;
+    int rc = dev_alloc(c, (void**)&c->round_lp_rows_dev, MMD_ROUND_MAX_SAMPLERS * sizeof(LogprobRow)); if (rc) return rc;
+    HIPCHK(c, hipHostMalloc((void**)&c->round_lp_rows_host, MMD_ROUND_MAX_SAMPLERS * sizeof(LogprobRow)));
+    return dev_alloc(c, &c->round_lp_scratch, logprob_scratch_bytes(MMD_ROUND_MAX_SAMPLERS), false);
+}
 extern "C" int mmd_sampler_lane(const mmd_sampler* sp) { return sp ? (int)sp->lane : MMD_EINVAL; }
 extern "C" int64_t mmd_sampler_offset(const mmd_sampler* sp) { return sp ? (int64_t)sp->offset : MMD_EINVAL; }
 
@@ -1827,6 +1893,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         RoundSeg& r = rsegs[j];
         r.feed = (fl & MMD_SEG_FEED) != 0; r.sample = (fl & MMD_SEG_SAMPLE) != 0; r.rows = segs[j].rows;
         if (sp) { r.sampling = sp->sampling; r.constrained = sp->cons.on; r.sampler = (int)sp->lane; r.top_k = sp->top_k; r.top_p = sp->top_p; }          // (lane: the sampler's index within its context)
+        if (sp && sp->lp_top >= 0) { r.record = true; r.lp_top = sp->lp_top; }
         if (r.feed) {
             if (n_feed >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d feed segments", MMD_ROUND_MAX_SAMPLERS);
             feed.tok[n_feed] = sp->tok_dev; feed.row[n_feed] = segs[j].row0; ++n_feed;
@@ -1837,19 +1904,28 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         }
     }
     // sampling rows: three blocks of logits rows, plain arg-max | constrained arg-max | sampled (round_blocks).  The last two have row descriptors (and constraint descriptors,
-    // empty for an unconstrained sampled row) in slots 1.. of the context's arrays, in the order of their logits rows
+    // empty for an unconstrained sampled row) in slots 1.. of the context's arrays, in the order of their logits rows.  A block's recording rows are its tail: a recording row
+    // has a LogprobRow (slot sp->step of the sampler's own records), and the plain block's tail gets row descriptors of its own behind the others -- T = 1, the penalty list at
+    // its length before this token, no token or append slot: the arg-max has written both.  (plain tail + the other two blocks <= 32 rows: the arrays' 1 + 32 slots hold them.)
     const RoundBlocks rb = round_blocks(rsegs.data(), n_segs, V);
     if (rb.rc) FAIL(c, rb.rc, "%s", rb.error);
     const int n_plain = rb.n_plain, n_greedy = rb.n_greedy, n_sample = rb.n_sample; const int* sample_seg = rb.order;
     SampleBatch sb; int32_t sample_row[MMD_ROUND_MAX_SAMPLERS]; uint64_t no_offset = 0;
-    if (n_sample > n_plain) { rc = sample_reserve(c); if (rc) return rc; }
+    const int nd = n_sample - n_plain, plain_tail = rb.rec_rows(SEL_ARGMAX), n_rec = plain_tail + rb.rec_rows(SEL_CONS_ARGMAX) + rb.rec_rows(SEL_DRAW);
+    static_assert(SELECT_ROUND_MAX_ROWS == MMD_ROUND_MAX_SAMPLERS, "the descriptor arrays hold 1 + MMD_ROUND_MAX_SAMPLERS rows");
+    if (nd > 0 || plain_tail > 0) { rc = sample_reserve(c); if (rc) return rc; }
+    if (n_rec > 0) { rc = round_record_reserve(c); if (rc) return rc; }
     for (int i = 0; i < n_sample; ++i) {
         const int j = sample_seg[i]; mmd_sampler* sp = samplers[j];
         const bool pen = sp->penalty > 0.f;
         int64_t* append = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
         sample_row[i] = segs[j].row0 + segs[j].rows - 1;
+        if (n_rec > 0) c->round_lp_rows_host[i] = sp->lp_top >= 0 ? LogprobRow{sp->lp_rec, sp->step, sp->lp_cap, sp->lp_top} : LogprobRow{nullptr, 0, 0, 0};
         if (i < n_plain) {
             sb.prev[i] = sp->prev_dev; sb.n_prev[i] = pen ? sp->n_prev : 0; sb.penalty[i] = pen ? sp->penalty : 1.f; sb.tok[i] = sp->tok_dev; sb.append[i] = append;
+            if (i >= rb.rec0[SEL_ARGMAX])
+                fill_sample_row(c->samp_rows_host[1 + nd + (i - rb.rec0[SEL_ARGMAX])], SampleArgs{1.f, 0, 1.f, 0, &no_offset}, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr,
+                                nullptr, nullptr, 0, 0);
             continue;
         }
         if (sp->cons.on) { rc = cons_reserve(c); if (rc) return rc; }
@@ -1863,6 +1939,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         }
     }
     c->select_last[SELECT_PLAN_FIELDS] = SELECT_OF_ROUND; rb.fields(c->select_last + SELECT_PLAN_FIELDS + 1);
+    rb.record_fields(c->round_record_last);
     if (n_sample && !tokens_out_host) FAIL(c, MMD_EINVAL, "sampling segments need tokens_out_host");
     if (n_feed) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_embed_feed(c->cfg.dtype, c->embed, feed, n_feed, H, V, c->l_h, st)); }
     if (n_sample && !c->round_logits) {
@@ -1891,15 +1968,30 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
             const int r0 = rb.row0(kind);
             SelectIO io{};
             io.logits = c->round_logits + (size_t)r0 * V; io.V = V; io.n = rb.rows(kind); io.toks = c->round_toks_dev + r0;
-            io.rows = p.needs_row ? c->samp_rows_dev + 1 + (r0 - n_plain) : nullptr; io.cons = p.needs_cons ? c->cons_rows_dev + 1 + (r0 - n_plain) : nullptr;
+            if (kind == SEL_ARGMAX) io.rows = p.needs_row ? c->samp_rows_dev + 1 + nd : nullptr;          // (the tail's alone)
+            else io.rows = p.needs_row ? c->samp_rows_dev + 1 + (r0 - n_plain) : nullptr;
+            io.cons = p.needs_cons ? c->cons_rows_dev + 1 + (r0 - n_plain) : nullptr;
             io.scratch = c->samp_scratch; io.am_scratch = c->round_scratch; io.batch = &sb;
+            const LogprobOut lpo{nullptr, 0, nullptr, 0, c->round_toks_dev + r0, 0, c->round_lp_rows_dev + r0};
+            if (p.record) { io.lp = &lpo; io.lp_scratch = c->round_lp_scratch; io.rec0 = rb.rec0[kind] - r0; }
             return select_enqueue(c, p, io);
         };
-        if (n_plain) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, block(SEL_ARGMAX)); }
-        if (n_sample > n_plain) {
-            const int nd = n_sample - n_plain;
-            HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev + 1, c->samp_rows_host + 1, sizeof(SampleRow) * nd, hipMemcpyHostToDevice, st));          // (the round's synchronisation frees the staging)
+        // the descriptors go to the device once, in front of the first block that reads any: the plain block only when it has a recording tail
+        bool posted = false;
+        auto post = [&]() -> int {
+            if (posted) return MMD_OK;
+            posted = true;
+            if (nd + plain_tail > 0) HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev + 1, c->samp_rows_host + 1, sizeof(SampleRow) * (nd + plain_tail), hipMemcpyHostToDevice, st));          // (the round's synchronisation frees the staging)
             if (n_greedy > n_plain || rb.any_cons_sampled) HIPCHK(c, hipMemcpyAsync(c->cons_rows_dev + 1, c->cons_rows_host + 1, sizeof(ConstraintRow) * nd, hipMemcpyHostToDevice, st));
+            if (n_rec > 0) HIPCHK(c, hipMemcpyAsync(c->round_lp_rows_dev, c->round_lp_rows_host, sizeof(LogprobRow) * n_sample, hipMemcpyHostToDevice, st));
+            return MMD_OK;
+        };
+        if (n_plain) {
+            if (plain_tail > 0) { rc = post(); if (rc) return rc; }
+            ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, block(SEL_ARGMAX));
+        }
+        if (n_sample > n_plain) {
+            rc = post(); if (rc) return rc;
             ProfScope ps(c, MMD_K_OTHER, 0, 0);
             if (n_greedy > n_plain) HIPCHK(c, block(SEL_CONS_ARGMAX));
             if (n_sample > n_greedy) HIPCHK(c, block(SEL_DRAW));
@@ -1917,8 +2009,10 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         if (i >= n_greedy) sp->offset += 1;
         if (tok < 0) FAIL(c, MMD_EDOM, "segment %d: a NaN among the logits, or every score is -inf: no token drawn", sample_seg[i]);
         sp->step += 1;
+        if (sp->lp_top >= 0) sp->lp_n += 1;
         const bool is_eos = (sp->cons.on && sp->cons.n_eos > 0) ? std::find(sp->cons.eos, sp->cons.eos + sp->cons.n_eos, tok) != sp->cons.eos + sp->cons.n_eos : tok == sp->eos;
         if (sp->penalty > 0.f && !is_eos && sp->n_prev < sp->prev_cap) sp->n_prev += 1;          // (EOS is neither fed back nor penalised: models/modeling_live.py:66-72)
+        if (is_eos || sp->step >= sp->max_new) sp->ended = true;
     }
     return MMD_OK;
 }
@@ -2525,6 +2619,7 @@ extern "C" int mmd_op_gemm_last_plan(mmd_ctx* c, int* out4) {
 // the decode steps of the most recent generate call: 0 none or eager, 1 replayed an existing captured step, 2 captured in that call, then replayed
 extern "C" int mmd_op_decode_last_route(mmd_ctx* c) { return c ? c->dec_route : MMD_EINVAL; }
 extern "C" int mmd_op_step_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < STEP_PLAN_FIELDS; ++i) out[i] = c->step_last[i]; return MMD_OK; }
+extern "C" int mmd_op_round_last_record(mmd_ctx* c, int* out4) { if (!c || !out4) return MMD_EINVAL; for (int i = 0; i < ROUND_RECORD_FIELDS; ++i) out4[i] = c->round_record_last[i]; return MMD_OK; }
 extern "C" int mmd_op_select_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < SELECT_LAST_FIELDS; ++i) out[i] = c->select_last[i]; return MMD_OK; }
 // times one GEMM shape on the context's stream with HIP events (weights packed once, outside the timed region)
 extern "C" int mmd_op_gemm_bench(mmd_ctx* c, int M, int N, int K, int epi, int variant, int iters, float* avg_ms_out, const void* Xin, const void* Win) {

@@ -14,7 +14,8 @@
 //   sample_draw_kernel     one block per row: Philox word (or the explicit one), target = mulhi64(r, Z_kept), the slice from the per-slice masses, the token from a scan
 //                          inside the slice; writes token / info, appends to the sampler's slots, advances the row's offset.
 // Log-probabilities of the token a row ended with (DESIGN.md "Log-probabilities"; the kernels are at the end of the file): the draw kernel emits z[tok] - zmax - log(Z_kept 2^-40)
-// through LogprobOut; three more kernels give the same over the RAW logits plus the top_n largest of them.
+// through LogprobOut; three more kernels give the same over the RAW logits plus the top_n largest of them.  A launch records either into one array at consecutive slots or,
+// per row, wherever the row's LogprobRow says (the rounds of several streams: every row is another sampler's).
 #include "common.h"
 
 constexpr int SMP_L12 = 2048, SMP_L3 = 1024;                                 // bins of radix levels 1, 2 and of level 3
@@ -287,6 +288,15 @@ __global__ __launch_bounds__(256) void sample_select_kernel(int V, const SampleR
     }
 }
 
+// Where row r of a launch records (null: nowhere) and how many alternatives.  Both depend on the launch's arguments and the row alone: every thread of a block gets the same.
+__device__ __forceinline__ LogprobRec* lp_dest(const LogprobOut& o, int r) {
+    if (o.rows) { const LogprobRow d = o.rows[r]; return (d.rec && d.slot >= 0 && d.slot < d.cap) ? d.rec + d.slot : nullptr; }
+    if (!o.rec) return nullptr;
+    const int ri = (o.dyn ? o.dyn->step : o.idx0) + r;
+    return ri < o.cap ? o.rec + ri : nullptr;
+}
+__device__ __forceinline__ int lp_top_of(const LogprobOut& o, int r) { return min(max(o.rows ? o.rows[r].top_n : o.top_n, 0), LP_MAX_TOP); }
+
 __global__ __launch_bounds__(256) void sample_draw_kernel(int V, int nblk, SampleRow* __restrict__ rows, SampleWs w, const unsigned long long* __restrict__ r_words,
                                                           int64_t* __restrict__ toks_out, float* __restrict__ info_out, LogprobOut lp) {
     __shared__ unsigned long long sm[256];
@@ -345,12 +355,19 @@ __global__ __launch_bounds__(256) void sample_draw_kernel(int V, int nblk, Sampl
             info_out[r * 4 + 2] = tot ? (float)((double)s_Z / (double)tot) : 0.f;
             info_out[r * 4 + 3] = nan ? 1.f : 0.f;
         }
-        if (lp.rec) {          // log-probability of the token under the distribution it was drawn from: the kept set's masses are exactly the ones the draw searched
-            const int ri = (lp.dyn ? lp.dyn->step : lp.idx0) + r;
-            if (ri < lp.cap) lp.rec[ri].slp = tok < 0 ? NAN : (float)((double)z[tok] - (double)zmax - log((double)s_Z * 0x1p-40));
-        }
+        // log-probability of the token under the distribution it was drawn from: the kept set's masses are exactly the ones the draw searched
+        LogprobRec* rec = lp_dest(lp, r);
+        if (rec) rec->slp = tok < 0 ? NAN : (float)((double)z[tok] - (double)zmax - log((double)s_Z * 0x1p-40));
         if (row.advance) rows[r].offset = row.offset + 1;
     }
+}
+
+// the chain's workspace of a launch over n rows, seen from its row r0 on (the records of a block's tail)
+static SampleWs carve_from(void* scratch, int V, int n, float* scores_out, int r0) {
+    SampleWs w = carve(scratch, V, n, scores_out);
+    w.state += r0; w.part_mass += (size_t)r0 * SMP_MAX_SLICES; w.part_max += (size_t)r0 * SMP_MAX_SLICES; w.part_nan += (size_t)r0 * SMP_MAX_SLICES;
+    w.hist_m += (size_t)r0 * SMP_HIST_BINS; w.hist_c += (size_t)r0 * SMP_HIST_BINS; w.z += (long long)r0 * w.ldz;
+    return w;
 }
 
 int sample_topkp_slices(int V) { const int s = cdiv(V, 256); return s < 1 ? 1 : (s > SMP_MAX_SLICES ? SMP_MAX_SLICES : s); }
@@ -411,10 +428,16 @@ __device__ __forceinline__ void block_best(float& v, int& i, float* s_v, int* s_
     for (int k = 1; k < 4; ++k) if (lp_better(s_v[k], s_i[k], v, i)) { v = s_v[k]; i = s_i[k]; }
 }
 
-__global__ __launch_bounds__(256) void logprob_max_top_kernel(const float* __restrict__ logits, int V, LogprobWs w, int top_n) {
+// `rows` (or null): per-row destinations; a block whose row has none returns at once, the others take their row's own top_n
+__global__ __launch_bounds__(256) void logprob_max_top_kernel(const float* __restrict__ logits, int V, LogprobWs w, int top_n, const LogprobRow* __restrict__ rows) {
     __shared__ uint32_t s_max[4], s_nan[4];
     __shared__ float s_v[4]; __shared__ int s_i[4];
     const int r = blockIdx.y;
+    if (rows) {          // (block-uniform: the descriptor of blockIdx.y)
+        const LogprobRow d = rows[r];
+        if (!d.rec || d.slot < 0 || d.slot >= d.cap) return;
+        top_n = min(max(d.top_n, 0), LP_MAX_TOP);
+    }
     const float* lg = logits + (long long)r * V;
     int beg, end; slice_of(V, blockIdx.x, gridDim.x, &beg, &end);
     uint32_t mk = 0, nn = 0;
@@ -445,9 +468,10 @@ __device__ __forceinline__ float lp_row_max(const LogprobWs& w, int r, int nblk,
     return key2f(mk);
 }
 
-__global__ __launch_bounds__(256) void logprob_mass_kernel(const float* __restrict__ logits, int V, LogprobWs w) {
+__global__ __launch_bounds__(256) void logprob_mass_kernel(const float* __restrict__ logits, int V, LogprobWs w, const LogprobRow* __restrict__ rows) {
     __shared__ unsigned long long s_m[256];
     const int r = blockIdx.y;
+    if (rows) { const LogprobRow d = rows[r]; if (!d.rec || d.slot < 0 || d.slot >= d.cap) return; }          // (before the row's partials are read: nobody wrote them)
     bool nan; const float lmax = lp_row_max(w, r, gridDim.x, &nan);
     if (nan) return;
     const float* lg = logits + (long long)r * V;
@@ -466,9 +490,9 @@ __global__ __launch_bounds__(256) void logprob_final_kernel(const float* __restr
     __shared__ float s_v[4]; __shared__ int s_i[4];
     __shared__ double s_logZ;
     const int r = blockIdx.x, t = threadIdx.x;
-    const int ri = (o.dyn ? o.dyn->step : o.idx0) + r;
-    if (ri >= o.cap) return;
-    LogprobRec* rec = o.rec + ri;
+    LogprobRec* rec = lp_dest(o, r);
+    if (!rec) return;
+    const int top_n = lp_top_of(o, r);
     const float* lg = logits + (long long)r * V;
     bool nan; const float lmax = lp_row_max(w, r, nblk, &nan);
     if (t == 0) {
@@ -476,12 +500,12 @@ __global__ __launch_bounds__(256) void logprob_final_kernel(const float* __restr
         if (!nan) for (int b = 0; b < nblk; ++b) Z += w.part_mass[r * SMP_MAX_SLICES + b];
         s_logZ = log((double)Z * 0x1p-40);
     }
-    const int nc = nblk * o.top_n;
-    for (int c = t; c < nc; c += 256) { const int g = (r * SMP_MAX_SLICES + c / o.top_n) * LP_MAX_TOP + c % o.top_n; s_cv[c] = w.cand_v[g]; s_ci[c] = w.cand_i[g]; }
+    const int nc = nblk * top_n;
+    for (int c = t; c < nc; c += 256) { const int g = (r * SMP_MAX_SLICES + c / top_n) * LP_MAX_TOP + c % top_n; s_cv[c] = w.cand_v[g]; s_ci[c] = w.cand_i[g]; }
     __syncthreads();
     const double logZ = s_logZ;
     float last_v = INFINITY; int last_i = -1;
-    for (int j = 0; j < o.top_n; ++j) {
+    for (int j = 0; j < top_n; ++j) {
         float bv = -INFINITY; int bi = LP_NONE;
         for (int c = t; c < nc; c += 256) { const float v = s_cv[c]; const int i = s_ci[c]; if (i != LP_NONE && lp_better(last_v, last_i, v, i) && lp_better(v, i, bv, bi)) { bv = v; bi = i; } }
         block_best(bv, bi, s_v, s_i);
@@ -552,15 +576,19 @@ hipError_t launch_argmax_scores(int V, int n, const SampleRow* rows_dev, float* 
     return hipGetLastError();
 }
 
-hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st) {
+hipError_t launch_logprob_rows(const float* logits, int V, int n, const LogprobOut& o, bool greedy, float* scores_out_dev, void* sample_scratch, void* lp_scratch, hipStream_t st,
+                               int sw_rows, int sw_row0) {
     if (n <= 0) return hipSuccess;
-    if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18) || o.top_n < 0 || o.top_n > LP_MAX_TOP || !o.rec || !o.toks) return hipErrorInvalidValue;
+    if (n > MMD_ROUND_MAX_SAMPLERS || V <= 0 || V > (1 << 18) || !o.toks) return hipErrorInvalidValue;
+    if (!o.rows && (o.top_n < 0 || o.top_n > LP_MAX_TOP || !o.rec)) return hipErrorInvalidValue;
+    if (sw_rows <= 0) { sw_rows = n; sw_row0 = 0; }
+    if (sw_row0 < 0 || sw_row0 + n > sw_rows || sw_rows > MMD_ROUND_MAX_SAMPLERS) return hipErrorInvalidValue;
     const LogprobWs w = carve_lp(lp_scratch, n);
-    const SampleWs sw = greedy ? carve(sample_scratch, V, n, scores_out_dev) : SampleWs{};
+    const SampleWs sw = greedy ? carve_from(sample_scratch, V, sw_rows, scores_out_dev, sw_row0) : SampleWs{};
     const int nblk = sample_topkp_slices(V);
     const dim3 grid(nblk, n), blk(256);
-    hipLaunchKernelGGL(logprob_max_top_kernel, grid, blk, 0, st, logits, V, w, o.top_n);
-    hipLaunchKernelGGL(logprob_mass_kernel, grid, blk, 0, st, logits, V, w);
+    hipLaunchKernelGGL(logprob_max_top_kernel, grid, blk, 0, st, logits, V, w, o.top_n, o.rows);
+    hipLaunchKernelGGL(logprob_mass_kernel, grid, blk, 0, st, logits, V, w, o.rows);
     hipLaunchKernelGGL(logprob_final_kernel, dim3(n), blk, 0, st, logits, V, nblk, w, o, greedy ? 1 : 0, sw);
     return hipGetLastError();
 }

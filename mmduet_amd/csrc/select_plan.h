@@ -3,7 +3,7 @@
 //   select_plan()    one block of logits rows: which kernels choose the tokens, what they read, what follows them.  select_enqueue (model.hip) launches what it says.
 //   generate_plan()  what a generate call decides once, behind its first token: captured or eager steps, which descriptors are posted when, who grows the penalty list,
 //                    the key of the captured step.
-//   round_blocks()   the sampling segments of a scheduler round ordered into its three blocks of logits rows.
+//   round_blocks()   the sampling segments of a scheduler round ordered into its three blocks of logits rows, each block's recording rows as its tail.
 // mmd_op_select_last_plan reads the answers back.
 #pragma once
 #include <stdio.h>
@@ -133,24 +133,38 @@ struct RoundSeg {
     int rows = 1;
     int sampler = -1;                  // which sampler, as an index into the caller's own array (two segments with the same sampler carry the same index)
     int top_k = 0; float top_p = 1.f;
+    bool record = false;               // the segment's sampler records log-probabilities (mmd_sampler_set_logprobs) ...
+    int lp_top = -1;                   // ... with this many alternatives
 };
 constexpr int ROUND_BLOCKS_FIELDS = 6;
+constexpr int ROUND_RECORD_FIELDS = 4;
 struct RoundBlocks {
     int rc = MMD_OK; char error[96] = {0};
-    int order[SELECT_ROUND_MAX_ROWS] = {0};          // the sampling segments in the order of their logits rows: plain arg-max | constrained arg-max | sampled, each in segment order
+    int order[SELECT_ROUND_MAX_ROWS] = {0};          // the sampling segments in the order of their logits rows: plain arg-max | constrained arg-max | sampled; inside a block the
+                                                     // rows that record nothing first, the recording ones last, each group in segment order
     int n_plain = 0, n_greedy = 0, n_sample = 0;          // rows [0, n_plain) | [n_plain, n_greedy) | [n_greedy, n_sample)
     bool any_k = false, any_p = false; // over the sampled block
     bool any_cons_sampled = false;     // a sampled row is constrained: the block's launch takes constraint descriptors (empty ones for the other rows)
     int V = 0;
+    int rec0[3] = {0, 0, 0};           // per kind: the block's recording rows are its tail [rec0[kind], row0(kind) + rows(kind)); an empty tail starts at the block's end
+    int lp_top_max = -1;               // the largest lp_top among the recording rows (-1: no row records)
     void fields(int* out) const {
         const int v[ROUND_BLOCKS_FIELDS] = {n_plain, n_greedy, n_sample, any_k, any_p, any_cons_sampled};
         for (int i = 0; i < ROUND_BLOCKS_FIELDS; ++i) out[i] = v[i];
     }
     int row0(int kind) const { return kind == SEL_ARGMAX ? 0 : kind == SEL_CONS_ARGMAX ? n_plain : n_greedy; }
     int rows(int kind) const { return kind == SEL_ARGMAX ? n_plain : kind == SEL_CONS_ARGMAX ? n_greedy - n_plain : n_sample - n_greedy; }
-    SelectPlan plan(int kind) const {  // the launches of one block: the filters any of its rows needs, constraint descriptors when any sampled row has a set
+    int rec_rows(int kind) const { return row0(kind) + rows(kind) - rec0[kind]; }
+    void record_fields(int* out) const {          // what mmd_op_round_last_record reports: recording rows per block, the largest top_n
+        const int v[ROUND_RECORD_FIELDS] = {rec_rows(SEL_ARGMAX), rec_rows(SEL_CONS_ARGMAX), rec_rows(SEL_DRAW), lp_top_max};
+        for (int i = 0; i < ROUND_RECORD_FIELDS; ++i) out[i] = v[i];
+    }
+    // the launches of one block: the filters any of its rows needs, constraint descriptors when any sampled row has a set, the record's launches (over the tail alone) when
+    // the block has a tail
+    SelectPlan plan(int kind) const {
         SelectRows r;
         r.sampled = kind == SEL_DRAW; r.constrained = kind == SEL_CONS_ARGMAX || (kind == SEL_DRAW && any_cons_sampled); r.n = rows(kind); r.V = V;
+        r.record = rec_rows(kind) > 0;
         SelectPlan p = select_plan(r);
         if (kind == SEL_DRAW) { p.any_k = any_k; p.any_p = any_p; }
         return p;
@@ -159,7 +173,7 @@ struct RoundBlocks {
 static inline int round_kind(const RoundSeg& s) { return s.sampling ? SEL_DRAW : s.constrained ? SEL_CONS_ARGMAX : SEL_ARGMAX; }
 static inline RoundBlocks round_blocks(const RoundSeg* segs, int n, int V) {
     RoundBlocks b; b.V = V;
-    int count[3] = {0, 0, 0}, seen[SELECT_ROUND_MAX_ROWS], total = 0;
+    int count[3] = {0, 0, 0}, quiet[3] = {0, 0, 0}, seen[SELECT_ROUND_MAX_ROWS], total = 0;
     for (int j = 0; j < n; ++j) {
         const RoundSeg& s = segs[j];
         if (s.feed && s.rows != 1) { b.rc = MMD_EINVAL; snprintf(b.error, sizeof(b.error), "a feed segment is one row (segment %d has %d)", j, s.rows); return b; }
@@ -167,13 +181,17 @@ static inline RoundBlocks round_blocks(const RoundSeg* segs, int n, int V) {
         if (total >= SELECT_ROUND_MAX_ROWS) { b.rc = MMD_ERANGE; snprintf(b.error, sizeof(b.error), "more than %d sampling segments", SELECT_ROUND_MAX_ROWS); return b; }
         for (int k = 0; k < total; ++k) if (seen[k] == s.sampler) { b.rc = MMD_EINVAL; snprintf(b.error, sizeof(b.error), "a sampler may appear once per round"); return b; }
         seen[total++] = s.sampler; ++count[round_kind(s)];
+        if (!s.record) ++quiet[round_kind(s)];
     }
-    int at[3] = {0, count[SEL_ARGMAX], count[SEL_ARGMAX] + count[SEL_CONS_ARGMAX]};
+    int at[3] = {0, count[SEL_ARGMAX], count[SEL_ARGMAX] + count[SEL_CONS_ARGMAX]};          // where the next row that records nothing goes ...
     b.n_plain = at[SEL_CONS_ARGMAX]; b.n_greedy = at[SEL_DRAW]; b.n_sample = total;
+    for (int k = 0; k < 3; ++k) b.rec0[k] = at[k] + quiet[k];
+    int rec_at[3] = {b.rec0[0], b.rec0[1], b.rec0[2]};          // ... and the next recording one
     for (int j = 0; j < n; ++j) {
         const RoundSeg& s = segs[j];
         if (!s.sample) continue;
-        b.order[at[round_kind(s)]++] = j;
+        if (s.record) { b.order[rec_at[round_kind(s)]++] = j; if (s.lp_top > b.lp_top_max) b.lp_top_max = s.lp_top; }
+        else b.order[at[round_kind(s)]++] = j;
         if (!s.sampling) continue;
         SelectRows r; r.sampled = true; r.V = V; r.top_k = s.top_k; r.top_p = s.top_p;
         const SelectPlan p = select_plan(r);

@@ -470,7 +470,7 @@ class LiveInferForBenchmark:
             output_ids, past_key_values = self._native_response()
         else:
             from .multistream import _ModelProxy
-            if isinstance(self.model, _ModelProxy):
+            if isinstance(self.model, _ModelProxy) and not self.model.can_record_logprobs():          # no scheduler slot, or a scheduler without the native rounds
                 raise NotImplementedError('output_logprobs: the multi-stream rounds (_ModelProxy, streams_per_gpu > 1) record no log-probabilities')
             self.model.set_generate_logprobs(self.top_logprobs)
             try:

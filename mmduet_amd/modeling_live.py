@@ -155,6 +155,35 @@ class SamplerHandle:
             check(lib().mmd_sampler_set_sampling(self.h, float(sm.get('temperature', 1.0)) if sampling else 0.0, int(sm.get('top_k', 0) or 0), float(sm.get('top_p', 1.0)),
                                                  int(sm.get('seed', 0)) & _U64), self.model._ctx, 'mmd_sampler_set_sampling')
 
+    def set_logprobs(self, top_n=-1):
+        """mmd_sampler_set_logprobs: the sampler's rows of the following rounds record per-token log-probabilities with `top_n` (0..8) alternatives; -1 or None switches
+        the recording off (the default).  At a response boundary: before `begin`, or after it and before the response's first token."""
+        top_n = -1 if top_n is None else int(top_n)
+        with self.model._lock:
+            self.model._bind_stream()
+            check(lib().mmd_sampler_set_logprobs(self.h, top_n), self.model._ctx, 'mmd_sampler_set_logprobs')
+            self._logprobs_top = top_n
+
+    def read_logprobs(self):
+        """mmd_sampler_logprobs_read: the records of the response begun by the most recent `begin`, one per token the rounds have returned so far (EOS included), as the
+        dict `last_generate_logprobs()` returns -- logprobs [n], sampling_logprobs [n], top_logprobs [n, top_n], top_logprob_ids [n, top_n], CPU tensors -- or None when
+        the sampler does not record."""
+        top = getattr(self, '_logprobs_top', -1)
+        if top < 0:
+            return None
+        with self.model._lock:
+            self.model._bind_stream()
+            n = C.c_int(0)
+            rc = lib().mmd_sampler_logprobs_read(self.h, None, None, None, None, 0, C.byref(n))          # the count alone: nothing is copied when there is no room
+            if n.value == 0:
+                check(rc, self.model._ctx, 'mmd_sampler_logprobs_read')
+            k = n.value
+            lp, slp = torch.empty(k, dtype=torch.float32), torch.empty(k, dtype=torch.float32)
+            top_lp, top_ids = torch.empty(k, top, dtype=torch.float32), torch.empty(k, top, dtype=torch.long)
+            if k:
+                check(lib().mmd_sampler_logprobs_read(self.h, _ptr(lp), _ptr(slp), _ptr(top_ids), _ptr(top_lp), k, C.byref(n)), self.model._ctx, 'mmd_sampler_logprobs_read')
+        return dict(logprobs=lp, sampling_logprobs=slp, top_logprobs=top_lp, top_logprob_ids=top_ids)
+
     @property
     def lane(self):
         """The sampler's id within its context: the Philox lane of its draws."""
@@ -954,6 +983,15 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         tail = out[ns + 1:]
         return dict(select=dict(zip(self.SELECT_PLAN_FIELDS, out[:ns])), generate=dict(zip(self.GENERATE_PLAN_FIELDS, tail)) if out[ns] == 1 else None,
                     round=dict(zip(self.ROUND_BLOCKS_FIELDS, tail)) if out[ns] == 2 else None)
+
+    ROUND_RECORD_FIELDS = ('plain', 'constrained', 'sampled', 'top_n')
+
+    def round_last_record(self):
+        """What the most recent round recorded (mmd_op_round_last_record): the recording rows of its plain arg-max, constrained arg-max and sampled blocks, and the
+        largest top_n among them (-1: no row recorded)."""
+        out = (C.c_int * len(self.ROUND_RECORD_FIELDS))()
+        check(lib().mmd_op_round_last_record(self._ctx, out), self._ctx, 'round_last_record')
+        return dict(zip(self.ROUND_RECORD_FIELDS, out))
 
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, frames=None, past_key_values=None, max_new_tokens=20, do_sample=False, temperature=1.0, top_k=50, top_p=1.0,

@@ -78,6 +78,26 @@ class _ModelProxy:
         self.__dict__['_constraints'] = constraints if constraints.on else None
         return was
 
+    def can_record_logprobs(self):
+        """Whether this slot's responses can record log-probabilities: it has a scheduler slot, and the scheduler runs the native rounds (mmd_round_multi)."""
+        return self._slot is not None and hasattr(self._real, 'round_multi') and not self._slot.sched.python_decode
+
+    def set_generate_logprobs(self, top_n=-1):
+        """The real model's call for THIS slot: the setting rides on the slot's following generate requests and the scheduler hands it to the slot's sampler beside
+        mmd_sampler_begin (the context-wide setting of the real model is not touched).  -1 or None: off, the default."""
+        top_n = -1 if top_n is None else int(top_n)
+        if not -1 <= top_n <= 8:
+            raise ValueError(f'log-probability alternatives: -1 (off) or 0..8, got {top_n}')
+        self.__dict__['_logprobs_top'] = top_n
+
+    def last_generate_logprobs(self):
+        """The records of this slot's most recent response, as the real model's `last_generate_logprobs()` returns them, or None if it did not record."""
+        return self.__dict__.get('_last_logprobs')
+
+    def _logprobs_request(self):
+        top = self.__dict__.get('_logprobs_top', -1)
+        return top if top >= 0 else None
+
     def _is_eos(self, eos_token_id):
         """EOS test of this slot's responses: the constraint set's EOS ids when it has any, else the call's own id."""
         cons = self.__dict__.get('_constraints')
@@ -97,8 +117,10 @@ class _ModelProxy:
         grow = generated_token_ids is not None and pen > 0
         cons, eos_set = self._is_eos(eos_token_id)
         gen = dict(slot=self._slot, eos=eos_token_id, eos_set=eos_set, constraints=cons, max_new=int(max_new_tokens), ids=[], penalty=pen if pen > 0 else None,
-                   prev=list(generated_token_ids) if grow else None, sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, restart=int(offset) == 0))
+                   prev=list(generated_token_ids) if grow else None, sampling=dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, restart=int(offset) == 0),
+                   logprobs=self._logprobs_request())
         r = self._slot.post(_Request('generate', inputs_embeds, past_key_values, gen=gen))
+        self.__dict__['_last_logprobs'] = r.get('logprobs')
         if grow:
             generated_token_ids.extend(t for t in r['ids'] if t not in eos_set)
         return r['ids'], r['cache'], int(offset) + len(r['ids'])
@@ -110,13 +132,16 @@ class _ModelProxy:
             # the whole response is ONE request: the scheduler advances it a token per round (mmd_round_multi samples on the device) and wakes this slot when it is complete
             cons, eos_set = self._is_eos(eos_token_id)
             gen = dict(slot=self._slot, eos=eos_token_id, eos_set=eos_set, constraints=cons, max_new=int(max_new_tokens), ids=[], penalty=repetition_penalty,
-                       prev=list(generated_token_ids) if (generated_token_ids is not None and repetition_penalty is not None) else None)
+                       prev=list(generated_token_ids) if (generated_token_ids is not None and repetition_penalty is not None) else None, logprobs=self._logprobs_request())
             r = self._slot.post(_Request('generate', inputs_embeds, past_key_values, gen=gen))
+            self.__dict__['_last_logprobs'] = r.get('logprobs')
             if generated_token_ids is not None and repetition_penalty is not None:
                 generated_token_ids.extend(t for t in r['ids'] if t not in eos_set)
             return r['ids'], r['cache']
         if self.__dict__.get('_constraints') is not None:
             raise NotImplementedError('constrained responses of several streams need the native rounds (mmd_round_multi)')
+        if self._logprobs_request() is not None:
+            raise NotImplementedError('log-probabilities of several streams need the native rounds (mmd_round_multi)')
         pen = float(repetition_penalty) if repetition_penalty is not None else 0.0
         seen = generated_token_ids if (generated_token_ids is not None and pen > 0) else None
         x, cache, ids = inputs_embeds, past_key_values, []
@@ -185,6 +210,7 @@ class _Slot(threading.Thread):
                     self.sched.results[n] = dict(responses=responses, debug_data=list(d.debug_data_list), forward_calls=d.forward_calls,
                                                  replayed_frames=d.replayed_frames, response_token_ids=list(d.response_token_ids),
                                                  generated_token_ids=[int(t) for t in d.generated_token_ids],
+                                                 response_logprobs=list(getattr(d, 'response_logprobs', ())),
                                                  final_kv_len=len(d.past_key_values) if d.past_key_values else 0)
                     if self.sched.on_result is not None:
                         self.sched.on_result(n, video, self.sched.results[n])
@@ -308,6 +334,8 @@ class MultiStreamInfer:
                     if g.get('constraints') is not None or getattr(g['sampler'], '_constraints_on', False):          # (a duck-typed sampler without constraints is called as before)
                         extra['constraints'] = g.get('constraints')
                     g['sampler'].begin(g['eos'], g['penalty'], g['prev'], g['max_new'], **extra)
+                    if g.get('logprobs') is not None or getattr(g['sampler'], '_logprobs_top', -1) >= 0:          # (a sampler that never recorded is not touched)
+                        g['sampler'].set_logprobs(g['logprobs'] if g.get('logprobs') is not None else -1)
                     segs.append(dict(x=r.x, cache=r.cache, sampler=g['sampler'], sample=True))
                 else:
                     segs.append(dict(x=None, cache=g['cache'], sampler=g['sampler'], feed=True, sample=True))
@@ -332,6 +360,11 @@ class MultiStreamInfer:
                 if o['token'] in g.get('eos_set', (g['eos'],)) or len(g['ids']) >= g['max_new']:
                     g['done'] = True
                     r.result = dict(ids=g['ids'], cache=g['cache'])
+                    if g.get('logprobs') is not None:          # the response's records cross once, now
+                        try:
+                            r.result['logprobs'] = g['sampler'].read_logprobs()
+                        except BaseException as e:
+                            r.result = e
             elif r.kind == 'forward':
                 r.result = dict(hidden=o['hidden'], cache=o['cache'])
             else:
