@@ -17,8 +17,8 @@ probabilistic bound of an fp32 summation.
 C_ACC = 3.04 is defined in tests/stress_inputs.py, next to the measurements it comes from; test_c_acc_is_four_times_the_measured_fp32_error prints the device's.
 No kernel bug was found by these cases.
 
-Out of scope: the tower's fp16 GEMM epilogues past 65504.  mmd_op_gemm runs in the context dtype only (the fp16 GEMMs are set inside the tower's own
-forward), and a new entry point is not tests work."""
+Not here: the tower's fp16 GEMM epilogues past 65504.  mmd_op_gemm runs in the context dtype only (the fp16 GEMMs are set inside the tower's own forward);
+tests/test_gpu_tower_stress.py reaches them through the tower itself (half_range: an fc2 output at 45 056, half_overflow: past 65 520, where fp16 is inf)."""
 import math, zlib
 import pytest
 import torch
