@@ -467,6 +467,10 @@ int mmd_op_decode_last_route(mmd_ctx* ctx);
  * mean): out9 = {schedule (0 tile, 1 fused slabs, 2 decode chain), rope_fused, chunk_rope, sparse_last, run0, run_n, run_all (the batched decode attention's run of segments),
  * down_slab_norm, mlp_pm} */
 int mmd_op_step_last_plan(mmd_ctx* ctx, int* out9);
+/* the schedule the most recent vision-tower run of this context took (tower_plan() of mmduet_amd/csrc/tower_plan.h): out12 = {element type (0 fp32, 1 bf16, 2 IEEE half),
+ * residual form (0 epilogue add, 1 fp32 stream, 2 epilogue add in half), embed form (0 add rows, 1 class token, 2 fp32 stream), sparse_last, pout, U, compact_rows,
+ * proj_compact, proj_gather, mlp_pm, mlp_pm_last, final_convert}.  mmd_vit_debug_tap refuses exactly when sparse_last is set. */
+int mmd_op_tower_last_plan(mmd_ctx* ctx, int* out12);
 /* the plan the most recent token selection of this context was launched from (select_plan() of mmduet_amd/csrc/select_plan.h; after a generate call whose steps replayed a
  * captured step: the plan that step was captured from): out22 = {kind (0 arg-max, 1 constrained arg-max, 2 draw), single, any_k, any_p, needs_row, needs_cons, record,
  * scores_after_argmax, record_greedy, advance}, then whose selection it was -- 0 a raw operator, 1 a generate call, 2 a round -- and that caller's own plan: a generate call's

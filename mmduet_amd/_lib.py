@@ -137,6 +137,7 @@ _SIGS = {
     'mmd_op_attention_last_form': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_decode_last_route': (_I, [_VP]),
     'mmd_op_step_last_plan': (_I, [_VP, C.POINTER(_I)]),
+    'mmd_op_tower_last_plan': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_select_last_plan': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_round_last_record': (_I, [_VP, C.POINTER(_I)]),
     'mmd_op_pool': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I]),

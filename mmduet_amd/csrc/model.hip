@@ -8,6 +8,7 @@
 //   fast_greedy_generate (models/modeling_live.py:51-77) -> mmd_greedy_generate
 #include "common.h"
 #include "step_plan.h"
+#include "tower_plan.h"
 #include "select_plan.h"
 #include <algorithm>
 #include <cfloat>
@@ -113,13 +114,10 @@ struct mmd_ctx {
     int step_last[STEP_PLAN_FIELDS] = {0};          // the plan of the most recent LLM step of THIS context (mmd_op_step_last_plan)
     // the SelectPlan the most recent token selection launched from, then whose it was (SELECT_OF_*) and that caller's GeneratePlan / RoundBlocks (mmd_op_select_last_plan)
     int select_last[SELECT_LAST_FIELDS] = {0};
-    bool gemm_half = false;            // the GEMMs issued right now belong to the fp16 vision tower (cfg.tower_f16): IEEE-half operands
     int tower_ring_flags = -1, tower_ring_blocks = 0;   // mmd_set_tower_share: persistent-grid cap of the tower's ring GEMMs beside a response's decoding
     int hid_compact = 0;               // > 0: l_hid holds that many compact rows (in the order of the `need` list) instead of all S rows of the step
     bool full_tower = false;           // mmd_vit_set_full_tower(1): the last encoder layer runs on ALL tokens (feature extraction, debug taps); default: on the tokens the bilinear pool reads
-    bool last_sparse = false;          // the most recent vit_tower ran its last layer on the pooled rows only (v_h then holds no full output: the debug taps refuse)
-    bool tower_compact = false;        // the tower's output of the current batch is the compact [B * (2 out)^2, C] block in v_col (set by vit_tower, consumed by connector_pool)
-    bool full_projector = false;       // set while mmd_vit_debug_tap(stage 1) recomputes the projector over ALL tokens (the shipped path runs it on the tokens the bilinear pool reads)
+    TowerPlan tower_last;              // the plan of the most recent tower run of THIS context (mmd_op_tower_last_plan): the projector behind it and the debug taps read it
     void* rope_tab = 0;                // (cos, sin) of a decode step's positions (launch_rope_table), read by the attention kernel's fused q/k/v preparation
     float* chain_ssq = 0;              // GemvChain scratch: per-row, per-n-tile sums of squares
     StepState* seg_dev = nullptr; StepState* seg_host = nullptr; int seg_slot = 0;          // per-stream (context, capacity, arena) of a step's batched decode attention: 8 slots of 64, rotated per step
@@ -237,12 +235,13 @@ static GemmArgs gemm_args(mmd_ctx* c, const void* X, int64_t ldx, const void* W,
     if (tower && c->tower_ring_flags >= 0) { a.ring_flags = c->tower_ring_flags; a.ring_max_blocks = c->tower_ring_blocks; }
     return a;
 }
+// dt: the element type of the operands: the context's (< 0), or the tower plan's -- MMD_F16 inside the fp16 vision tower (tower_gemm)
 static int gemm(mmd_ctx* c, const void* X, int64_t ldx, const void* W, int64_t ldw, const void* bias, const void* R, int64_t ldr, void* Y,
                 int64_t ldy, int M, int N, int K, int epi, int out_f32 = 0, int variant = GEMM_AUTO, const void* Wp = nullptr, bool tower = false,
-                const void* Wp8 = nullptr, const float* wscale = nullptr, const GemvChain* chain = nullptr, int* ring_slabs_out = nullptr, int pm = 0) {
+                const void* Wp8 = nullptr, const float* wscale = nullptr, const GemvChain* chain = nullptr, int* ring_slabs_out = nullptr, int pm = 0, int dt = -1) {
     GemmArgs a = gemm_args(c, X, ldx, W, ldw, bias, R, ldr, Y, ldy, M, N, K, epi, out_f32, variant, Wp, tower, Wp8, wscale);
-    a.chain = chain; a.ring_slabs_out = ring_slabs_out; a.x_pm = pm & 1; a.y_pm = (pm >> 1) & 1;          // pm: 1 = X is piece-major, 2 = Y becomes piece-major (gemm_pair_pm)
-    const int dt = c->gemm_half ? MMD_F16 : c->cfg.dtype;          // gemm_half: inside the fp16 vision tower (vit_tower sets it)
+    a.chain = chain; a.ring_slabs_out = ring_slabs_out; a.x_pm = pm & 1; a.y_pm = (pm >> 1) & 1;          // pm: 1 = X is piece-major, 2 = Y becomes piece-major (gemm_pair_pm, TowerPlan::mlp_pm)
+    if (dt < 0) dt = c->cfg.dtype;
     const GemmPlan pl = gemm_plan_for(dt, a);          // the profiler class is that of the kernel that runs
     double e = (double)es(c);
     double bytes = (double)M * K * e + (double)N * K * ((Wp8 && M <= 64) ? 1.0 : e) + (double)M * (epi == EPI_SWIGLU ? N / 2 : N) * (out_f32 ? 4.0 : e);
@@ -251,15 +250,15 @@ static int gemm(mmd_ctx* c, const void* X, int64_t ldx, const void* W, int64_t l
     return MMD_OK;
 }
 
-// May the intermediate between a producer GEMM (X1 [M,K1] -> T [M,N1], epilogue epi1) and its ONLY consumer (T -> [M,N2]) live in the ring kernel's piece-major layout?
-// Yes when the automatic dispatch runs BOTH on gemm_ringx_kernel (gemm_ring_auto asks the planner about the very arguments gemm() will launch with).
-static bool gemm_pair_pm(mmd_ctx* c, bool tower, const void* X1, int64_t ldx1, const void* W1p, const void* b1, int N1w, int K1, int epi1, void* T, int64_t ldt,
+// mmd_op_gemm_pair: may the intermediate between a producer GEMM (X1 [M,K1] -> T [M,N1], epilogue epi1) and its ONLY consumer (T -> [M,N2]) live in the ring kernel's
+// piece-major layout?  Yes when the automatic dispatch runs BOTH on gemm_ringx_kernel (gemm_ring_auto asks the planner about the very arguments gemm() will launch with).
+// (The LLM step and the tower ask the same of gemm_plan() inside their own plans: step_plan.h, tower_plan.h.)
+static bool gemm_pair_pm(mmd_ctx* c, const void* X1, int64_t ldx1, const void* W1p, const void* b1, int N1w, int K1, int epi1, void* T, int64_t ldt,
                          const void* W2p, int N2, const void* R2, int64_t ldr2, void* Y2, int64_t ldy2, int epi2, int M) {
     if (c->sw.no_pm) return false;
-    const int dt = c->gemm_half ? MMD_F16 : c->cfg.dtype;
-    const GemmArgs a = gemm_args(c, X1, ldx1, nullptr, 0, b1, nullptr, 0, T, ldt, M, N1w, K1, epi1, 0, GEMM_AUTO, W1p, tower);
-    const GemmArgs b = gemm_args(c, T, ldt, nullptr, 0, nullptr, R2, ldr2, Y2, ldy2, M, N2, (int)ldt, epi2, 0, GEMM_AUTO, W2p, tower);
-    return gemm_ring_auto(dt, a, true) && gemm_ring_auto(dt, b);          // (the producer on the PLAIN ring: its split-K form writes row-major through splitk_reduce -- ADVICE r05)
+    const GemmArgs a = gemm_args(c, X1, ldx1, nullptr, 0, b1, nullptr, 0, T, ldt, M, N1w, K1, epi1, 0, GEMM_AUTO, W1p, false);
+    const GemmArgs b = gemm_args(c, T, ldt, nullptr, 0, nullptr, R2, ldr2, Y2, ldy2, M, N2, (int)ldt, epi2, 0, GEMM_AUTO, W2p, false);
+    return gemm_ring_auto(c->cfg.dtype, a, true) && gemm_ring_auto(c->cfg.dtype, b);          // (the producer on the PLAIN ring: its split-K form writes row-major through splitk_reduce -- ADVICE r05)
 }
 
 // ---- create / destroy ------------------------------------------------------------------------------------------------
@@ -658,149 +657,149 @@ static int alloc_workspaces(mmd_ctx* c) {
 #define NEED_FINAL(c) do { if (!(c)) return MMD_EINVAL; if (!(c)->finalized) FAIL(c, MMD_EINVAL, "weights not finalized"); hipSetDevice((c)->device); } while (0)
 
 // ---- vision ----------------------------------------------------------------------------------------------------------
-static int connector_pool(mmd_ctx* c, const void* feats, int B, void* out);
+static int connector_pool(mmd_ctx* c, const void* feats, int B, void* out, TowerProjectorPlan rows);
 static int ensure_preprocess_tables(mmd_ctx* c, int T, int R);
-// the tower: patch-embed (+ class token, + pre-LN for CLIP) -> encoder layers -> optional post_layernorm; result [B * vit_seq, C] in c->v_h
-static int vit_tower(mmd_ctx* c, const void* px, int B, bool col_ready = false, bool for_pool = false) {
-    const mmd_config& g = c->cfg; hipStream_t st = c->stream;
-    // tower_f16: every tower tensor is IEEE half (the reference's autocast); pixel_values arrive in the model dtype (bf16) and become half in the im2col pass,
-    // the tower's output is rounded to bf16 at the end (SigLipVisionTower returns hidden_states[-1].to(images.dtype) [3P-recalled])
-    const int dt = g.tower_f16 ? MMD_F16 : g.dtype;
-    struct HalfScope { mmd_ctx* c; HalfScope(mmd_ctx* c_, bool on) : c(c_) { c->gemm_half = on; } ~HalfScope() { c->gemm_half = false; } } half_scope(c, g.tower_f16 != 0);
-    if (B > g.max_vit_batch) FAIL(c, MMD_ERANGE, "vit batch %d exceeds max_vit_batch %d", B, g.max_vit_batch);
-    const int C = g.vit_hidden, T = c->vit_tokens, TS = c->vit_seq, M = B * TS, hd = C / g.vit_heads;
-    if (!col_ready) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_im2col(g.tower_f16 ? MMD_F16 + 1 : dt, px, B, g.vit_image, g.vit_patch, c->vit_grid, c->vit_kpad, c->v_col, st)); }
-    // tower_f16 == 1: the residual stream is fp32, as under autocast (`fp16 + model-dtype` and `fp32 + fp16` promote; LayerNorm returns fp32): the linears write their
-    // fp16 result (bias inside, one rounding) to v_xn and resid32_layernorm_kernel folds it into v_h32 and emits the next linear's input.  2: fp16 residual stream
-    // (the round-3 form: the sum is rounded to fp16 after every sublayer)
-    const bool r32 = g.tower_f16 == 1;
-    void* patch_out = g.vit_class_token ? c->v_patch : (r32 ? c->v_xn : c->v_h);
-    int rc = gemm(c, c->v_col, c->vit_kpad, c->patch_w, c->vit_kpad, c->patch_b, nullptr, 0, patch_out, C, B * T, C, c->vit_kpad, EPI_NONE, 0, GEMM_AUTO, c->patch_w_p, true); if (rc) return rc;
-    if (r32) {          // h32 = float(patch fp16) + float(position table); layer 0's LayerNorm 1 in the same pass
+
+// what tower_plan() (tower_plan.h) needs to know of this context
+static TowerModel tower_model(const mmd_ctx* c) {
+    const mmd_config& g = c->cfg; TowerModel m;
+    m.dtype = g.dtype; m.tower_f16 = g.tower_f16; m.C = g.vit_hidden; m.heads = g.vit_heads; m.ipad = c->vit_ipad; m.grid = c->vit_grid; m.tokens = c->vit_tokens; m.seq = c->vit_seq;
+    m.layers = g.vit_layers; m.pool_mode = g.pool_mode; m.pool_stride = g.pool_stride; m.class_token = g.vit_class_token != 0; m.pre_ln = g.vit_pre_layernorm != 0;
+    m.post_ln = g.vit_post_layernorm != 0; m.act = g.vit_act; m.vision_only = g.vision_only != 0; m.max_batch = g.max_vit_batch; m.splitk_ws_bytes = c->v_splitk_bytes;
+    m.fc1_p = !c->VL.empty() && c->VL[0].w1_p; m.fc2_p = !c->VL.empty() && c->VL[0].w2_p;
+    return m;
+}
+// Validate the batch, evaluate the plan ONCE and store it: tower_run, the projector behind it and the debug taps launch (or refuse) what c->tower_last says.
+static int tower_begin(mmd_ctx* c, int B, bool for_pool) {
+    TowerShape s; s.B = B; s.for_pool = for_pool; s.full_tower = c->full_tower; s.ring_flags = c->tower_ring_flags; s.ring_max_blocks = c->tower_ring_blocks;
+    const TowerPlan p = tower_plan(tower_model(c), s, c->sw.no_pm, gemm_tuning());
+    if (p.rc) FAIL(c, p.rc, "%s", p.error);
+    c->tower_last = p;
+    return MMD_OK;
+}
+// a tower GEMM as every part launches it: X [M,K] -> Y [M,N] in the plan's element type (every tower tensor is IEEE half under tower_f16, the reference's autocast), weights [N,K]
+// row-major (W; null where only the packed copy Wp was kept), the side stream's split-K scratch and ring cap; a residual R has Y's row stride
+static int tower_gemm(mmd_ctx* c, const void* X, int64_t ldx, const void* W, const void* Wp, const void* bias, const void* R, void* Y, int64_t ldy, int M, int N, int K, int epi, int pm = 0) {
+    return gemm(c, X, ldx, W, K, bias, R, R ? ldy : 0, Y, ldy, M, N, K, epi, 0, GEMM_AUTO, Wp, true, nullptr, nullptr, nullptr, nullptr, pm, c->tower_last.dt);
+}
+
+// patch embed and the stream's start, from the im2col matrix in v_col: patch GEMM, the embed form of the plan, CLIP's pre_layrnorm
+static int tower_embed(mmd_ctx* c, const TowerPlan& p, int B) {
+    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int C = g.vit_hidden, T = c->vit_tokens, M = B * c->vit_seq;
+    void* patch_out = p.embed == TOWER_EMBED_CLS ? c->v_patch : (p.embed == TOWER_EMBED_F32 ? c->v_xn : c->v_h);
+    int rc = tower_gemm(c, c->v_col, c->vit_kpad, c->patch_w, c->patch_w_p, c->patch_b, nullptr, patch_out, C, B * T, C, c->vit_kpad, EPI_NONE); if (rc) return rc;
+    if (p.embed == TOWER_EMBED_F32) {          // h32 = float(patch fp16) + float(position table); layer 0's LayerNorm 1 in the same pass (no layer: the cast to the model dtype)
+        const VitLayer* L0 = g.vit_layers > 0 ? &c->VL[0] : nullptr;
         ProfScope ps(c, MMD_K_NORM_ROPE, 12.0 * M * C, 0);
-        if (g.vit_layers > 0) { HIPCHK(c, launch_resid32_layernorm(c->v_xn, c->v_h32, c->pos_emb, T, c->VL[0].ln1w, c->VL[0].ln1b, c->v_xn, nullptr, M, C, g.vit_ln_eps, st)); }
-        else { HIPCHK(c, launch_resid32_layernorm(c->v_xn, c->v_h32, c->pos_emb, T, nullptr, nullptr, nullptr, c->v_h, M, C, g.vit_ln_eps, st)); }
-    } else if (g.vit_class_token) {
-        ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_assemble_cls(dt, c->v_patch, c->cls_emb, c->pos_emb, B, T, C, c->v_h, st));
+        HIPCHK(c, launch_resid32_layernorm(c->v_xn, c->v_h32, c->pos_emb, T, L0 ? L0->ln1w : nullptr, L0 ? L0->ln1b : nullptr, L0 ? c->v_xn : nullptr, L0 ? nullptr : c->v_h, M, C, g.vit_ln_eps, st));
     } else {
-        ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_add_rows(dt, c->v_h, c->pos_emb, M, C, T, st));
+        ProfScope ps(c, MMD_K_OTHER, 0, 0);
+        if (p.embed == TOWER_EMBED_CLS) { HIPCHK(c, launch_assemble_cls(p.dt, c->v_patch, c->cls_emb, c->pos_emb, B, T, C, c->v_h, st)); }
+        else { HIPCHK(c, launch_add_rows(p.dt, c->v_h, c->pos_emb, M, C, T, st)); }
     }
-    if (g.vit_pre_layernorm) { HIPCHK(c, launch_layernorm(dt, c->v_h, c->pre_w, c->pre_b, c->v_h, M, C, g.vit_ln_eps, st)); }
-    // The bilinear pool behind the projector reads (2 out)^2 = 196 of a frame's 729 tokens, and everything after the LAST layer's K / V is row-wise: that layer's
-    // queries, o_proj, LayerNorm, MLP (and the projector) run on those rows alone.  K and V still come from all tokens.  Same values into the same arithmetic;
-    // callers that want the tower's full output (feature extraction, debug taps) switch it off with mmd_vit_set_full_tower.
-    const int pout = (c->vit_grid + g.pool_stride - 1) / g.pool_stride, U = 4 * pout * pout;
-    // (the half forms of the kernels exist for M > 64 GEMMs and S >= 64 attention only: a compact block below that keeps the full last layer -- ADVICE r03)
-    const bool sparse_last = for_pool && !c->full_tower && !c->full_projector && g.pool_mode == MMD_POOL_BILINEAR && U < T && TS == T && !g.vit_post_layernorm &&
-                             g.vit_act != 1 && g.vit_layers > 0 && !g.vision_only && (!g.tower_f16 || (U >= 64 && B * U > 64));
-    c->last_sparse = sparse_last;
-    c->tower_compact = false;
+    if (g.vit_pre_layernorm) { HIPCHK(c, launch_layernorm(p.dt, c->v_h, c->pre_w, c->pre_b, c->v_h, M, C, g.vit_ln_eps, st)); }
+    return MMD_OK;
+}
+
+// one layer's attention: S query rows per frame at q (row stride ldq, a frame's rows contiguous) over all vit_seq keys of the frame in v_qkv -> v_attn [B * S, C].  Every token's
+// own queries in place (q = v_qkv, ldq = 3 C, S = vit_seq) or the sparse last layer's compact block (ldq = C, S = U)
+static int tower_attention(mmd_ctx* c, int dt, const void* q, int64_t ldq, int S, int B) {
+    const mmd_config& g = c->cfg; const int C = g.vit_hidden, TS = c->vit_seq, hd = C / g.vit_heads;
+    AttnArgs a; memset(&a, 0, sizeof(a));
+    a.q = q; a.ldq = ldq; a.K = (char*)c->v_qkv + (size_t)C * es(c); a.V = (char*)c->v_qkv + (size_t)2 * C * es(c);
+    a.k_hs = hd; a.k_ts = 3 * C; a.v_hs = hd; a.v_ts = 3 * C; a.out = c->v_attn; a.ldo = C;
+    a.S = S; a.nh = g.vit_heads; a.nkv = g.vit_heads; a.d = hd; a.n_ctx = TS - S; a.causal = 0;          // S query rows over all TS keys
+    a.batch = B; a.q_bstride = (int64_t)S * ldq; a.kv_bstride = (int64_t)TS * 3 * C; a.o_bstride = (int64_t)S * C;
+    a.ws = c->v_attn_ws; a.ws_bytes = c->v_attn_bytes; a.variant = 0;
+    ProfScope ps(c, MMD_K_ATTN_VIT, 2.0 * (B * TS + B * S) * C * es(c), 4.0 * B * (double)S * TS * C);
+    HIPCHK(c, launch_attention(dt, a, c->stream));
+    return MMD_OK;
+}
+
+// One layer's tail -- o_proj, LayerNorm 2, fc1 + GELU, fc2, residual -- over `rows` rows of the residual stream: all tokens, or the compact block of the sparse last layer (their
+// attention output is in v_attn).  pm: fc1's output is piece-major (its only reader is fc2).  One function per residual form (TowerPlan::resid).
+// TOWER_RESID_EPI, and TOWER_RESID_F16 which is the same in half: o_proj and fc2 add the stream h in their epilogue
+static int tower_tail_epi(mmd_ctx* c, const TowerPlan& p, const VitLayer& L, int rows, void* h, bool pm) {
+    const mmd_config& g = c->cfg; const int C = g.vit_hidden, IP = c->vit_ipad; const bool quick = g.vit_act == 1;
+    int rc = tower_gemm(c, c->v_attn, C, L.wo, L.wo_p, L.bo, h, h, C, rows, C, C, EPI_RESID); if (rc) return rc;
+    { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * rows * C * es(c), 0); HIPCHK(c, launch_layernorm(p.dt, h, L.ln2w, L.ln2b, c->v_xn, rows, C, g.vit_ln_eps, c->stream)); }
+    // CLIP quick_gelu: plain fc1, then x * sigmoid(1.702 x) on the storage-rounded output (secondary path: not fused, never piece-major)
+    rc = tower_gemm(c, c->v_xn, C, L.w1, L.w1_p, L.b1, nullptr, c->v_mlp, IP, rows, IP, C, quick ? EPI_NONE : EPI_GELU_TANH, pm ? 2 : 0); if (rc) return rc;
+    if (quick) { HIPCHK(c, launch_quick_gelu(p.dt, c->v_mlp, (int64_t)rows * IP, c->stream)); }
+    return tower_gemm(c, c->v_mlp, IP, L.w2, L.w2_p, L.b2, h, h, C, rows, C, IP, EPI_RESID, pm ? 1 : 0);
+}
+// TOWER_RESID_F32: the linears write their fp16 result to v_xn, resid32_layernorm folds it into the fp32 stream h32 and emits what follows: LayerNorm 2 behind o_proj; behind fc2 the
+// NEXT layer's LayerNorm 1, or after the last layer the stream in the model dtype at cast_out (hidden_states[-1].to(bf16); cast_bytes: that pass's bytes per element, for the profiler)
+static int tower_tail_f32(mmd_ctx* c, const VitLayer& L, int rows, float* h32, bool pm, const VitLayer* next, void* cast_out, double cast_bytes) {
+    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int C = g.vit_hidden, IP = c->vit_ipad;
+    int rc = tower_gemm(c, c->v_attn, C, L.wo, L.wo_p, L.bo, nullptr, c->v_xn, C, rows, C, C, EPI_NONE); if (rc) return rc;
+    { ProfScope ps(c, MMD_K_NORM_ROPE, 12.0 * rows * C, 0); HIPCHK(c, launch_resid32_layernorm(c->v_xn, h32, nullptr, 1, L.ln2w, L.ln2b, c->v_xn, nullptr, rows, C, g.vit_ln_eps, st)); }
+    rc = tower_gemm(c, c->v_xn, C, L.w1, L.w1_p, L.b1, nullptr, c->v_mlp, IP, rows, IP, C, EPI_GELU_TANH, pm ? 2 : 0); if (rc) return rc;
+    rc = tower_gemm(c, c->v_mlp, IP, L.w2, L.w2_p, L.b2, nullptr, c->v_xn, C, rows, C, IP, EPI_NONE, pm ? 1 : 0); if (rc) return rc;
+    ProfScope ps(c, MMD_K_NORM_ROPE, (next ? 12.0 : cast_bytes) * rows * C, 0);
+    HIPCHK(c, launch_resid32_layernorm(c->v_xn, h32, nullptr, 1, next ? next->ln1w : nullptr, next ? next->ln1b : nullptr, next ? c->v_xn : nullptr, next ? nullptr : cast_out, rows, C, g.vit_ln_eps, st));
+    return MMD_OK;
+}
+
+// the tower, as c->tower_last (tower_begin) says: patch-embed (+ class token, + pre-LN for CLIP) -> encoder layers -> optional post_layernorm.  Result in the model dtype:
+// [B * vit_seq, C] in v_h, or with sparse_last the rows the pool reads, [B * U, C], in v_col.  px == null: the im2col matrix is in v_col already.
+static int tower_run(mmd_ctx* c, const void* px, int B) {
+    const mmd_config& g = c->cfg; hipStream_t st = c->stream; const TowerPlan& p = c->tower_last;
+    const int dt = p.dt, C = g.vit_hidden, TS = c->vit_seq, M = B * TS, Mc = p.compact_rows;
+    const bool r32 = p.resid == TOWER_RESID_F32;
+    const int dt_copy = dt == MMD_F32 ? MMD_F32 : MMD_BF16;          // row gathers only move elements: 2-byte ones as bf16
+    if (px) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_im2col(dt == MMD_F16 ? MMD_F16 + 1 : dt, px, B, g.vit_image, g.vit_patch, c->vit_grid, c->vit_kpad, c->v_col, st)); }
+    int rc = tower_embed(c, p, B); if (rc) return rc;
+    // the sparse last layer's compact blocks: queries in v_mlp (free until fc1), the residual stream -- then the tower's output -- in v_col (the im2col matrix is dead since the
+    // patch GEMM), the fp32 stream behind the full one's rows in v_h32
+    void* const qc = c->v_mlp; void* const hc = c->v_col; float* const hc32 = r32 ? c->v_h32 + c->v_h32_rows * C : nullptr;
     for (int i = 0; i < g.vit_layers; ++i) {
-        VitLayer& L = c->VL[i];
+        const VitLayer& L = c->VL[i];
+        const bool compact = p.sparse_last && i + 1 == g.vit_layers;
         if (!r32) { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * M * C * es(c), 0); HIPCHK(c, launch_layernorm(dt, c->v_h, L.ln1w, L.ln1b, c->v_xn, M, C, g.vit_ln_eps, st)); }
-        rc = gemm(c, c->v_xn, C, L.wqkv, C, L.bqkv, nullptr, 0, c->v_qkv, 3 * C, M, 3 * C, C, EPI_NONE, 0, GEMM_AUTO, L.wqkv_p, true); if (rc) return rc;
-        if (sparse_last && i + 1 == g.vit_layers) {
-            const int Mc = B * U;
-            void* qc = c->v_mlp; void* hc = c->v_col;          // compact queries / residual stream (v_mlp is free until fc1, the im2col matrix is dead since the patch GEMM)
-            { ProfScope ps(c, MMD_K_OTHER, 0, 0);
-              HIPCHK(c, launch_gather_pool_rows(dt == MMD_F32 ? MMD_F32 : MMD_BF16, c->v_qkv, qc, B, c->vit_grid, C, pout, st, 3 * C));
-              if (r32) { HIPCHK(c, launch_gather_pool_rows(MMD_F32, c->v_h32, c->v_h32 + c->v_h32_rows * C, B, c->vit_grid, C, pout, st, C)); }
-              else { HIPCHK(c, launch_gather_pool_rows(dt == MMD_F32 ? MMD_F32 : MMD_BF16, c->v_h, hc, B, c->vit_grid, C, pout, st, C)); } }
-            {
-                AttnArgs a; memset(&a, 0, sizeof(a));
-                a.q = qc; a.ldq = C; a.K = (char*)c->v_qkv + (size_t)C * es(c); a.V = (char*)c->v_qkv + (size_t)2 * C * es(c);
-                a.k_hs = hd; a.k_ts = 3 * C; a.v_hs = hd; a.v_ts = 3 * C; a.out = c->v_attn; a.ldo = C;
-                a.S = U; a.nh = g.vit_heads; a.nkv = g.vit_heads; a.d = hd; a.n_ctx = TS - U; a.causal = 0;          // U query rows over all TS keys
-                a.batch = B; a.q_bstride = (int64_t)U * C; a.kv_bstride = (int64_t)TS * 3 * C; a.o_bstride = (int64_t)U * C;
-                a.ws = c->v_attn_ws; a.ws_bytes = c->v_attn_bytes; a.variant = 0;
-                ProfScope ps(c, MMD_K_ATTN_VIT, 2.0 * (M + Mc) * C * es(c), 4.0 * B * (double)U * TS * C);
-                HIPCHK(c, launch_attention(dt, a, st));
-            }
-            if (r32) {
-                float* hc32 = c->v_h32 + c->v_h32_rows * C;
-                rc = gemm(c, c->v_attn, C, L.wo, C, L.bo, nullptr, 0, c->v_xn, C, Mc, C, C, EPI_NONE, 0, GEMM_AUTO, L.wo_p, true); if (rc) return rc;
-                { ProfScope ps(c, MMD_K_NORM_ROPE, 12.0 * Mc * C, 0); HIPCHK(c, launch_resid32_layernorm(c->v_xn, hc32, nullptr, 1, L.ln2w, L.ln2b, c->v_xn, nullptr, Mc, C, g.vit_ln_eps, st)); }
-                const bool pm = gemm_pair_pm(c, true, c->v_xn, C, L.w1_p, L.b1, c->vit_ipad, C, EPI_GELU_TANH, c->v_mlp, c->vit_ipad, L.w2_p, C, nullptr, 0, c->v_xn, C, EPI_NONE, Mc);
-                rc = gemm(c, c->v_xn, C, L.w1, C, L.b1, nullptr, 0, c->v_mlp, c->vit_ipad, Mc, c->vit_ipad, C, EPI_GELU_TANH, 0, GEMM_AUTO, L.w1_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 2 : 0); if (rc) return rc;
-                rc = gemm(c, c->v_mlp, c->vit_ipad, L.w2, c->vit_ipad, L.b2, nullptr, 0, c->v_xn, C, Mc, C, c->vit_ipad, EPI_NONE, 0, GEMM_AUTO, L.w2_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 1 : 0); if (rc) return rc;
-                { ProfScope ps(c, MMD_K_NORM_ROPE, 8.0 * Mc * C, 0); HIPCHK(c, launch_resid32_layernorm(c->v_xn, hc32, nullptr, 1, nullptr, nullptr, nullptr, hc, Mc, C, g.vit_ln_eps, st)); }          // -> bf16 features
-                c->tower_compact = true;
-                c->last_vit_B = B;
-                return MMD_OK;
-            }
-            rc = gemm(c, c->v_attn, C, L.wo, C, L.bo, hc, C, hc, C, Mc, C, C, EPI_RESID, 0, GEMM_AUTO, L.wo_p, true); if (rc) return rc;
-            { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * Mc * C * es(c), 0); HIPCHK(c, launch_layernorm(dt, hc, L.ln2w, L.ln2b, c->v_xn, Mc, C, g.vit_ln_eps, st)); }
-            const bool pm = gemm_pair_pm(c, true, c->v_xn, C, L.w1_p, L.b1, c->vit_ipad, C, EPI_GELU_TANH, c->v_mlp, c->vit_ipad, L.w2_p, C, hc, C, hc, C, EPI_RESID, Mc);
-            rc = gemm(c, c->v_xn, C, L.w1, C, L.b1, nullptr, 0, c->v_mlp, c->vit_ipad, Mc, c->vit_ipad, C, EPI_GELU_TANH, 0, GEMM_AUTO, L.w1_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 2 : 0); if (rc) return rc;
-            rc = gemm(c, c->v_mlp, c->vit_ipad, L.w2, c->vit_ipad, L.b2, hc, C, hc, C, Mc, C, c->vit_ipad, EPI_RESID, 0, GEMM_AUTO, L.w2_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 1 : 0); if (rc) return rc;
-            if (g.tower_f16) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_convert(hc, MMD_F16, hc, MMD_BF16, (int64_t)Mc * C, st)); }
-            c->tower_compact = true;
-            c->last_vit_B = B;
-            return MMD_OK;
+        rc = tower_gemm(c, c->v_xn, C, L.wqkv, L.wqkv_p, L.bqkv, nullptr, c->v_qkv, 3 * C, M, 3 * C, C, EPI_NONE); if (rc) return rc;          // K and V always come from all tokens
+        if (compact) {
+            ProfScope ps(c, MMD_K_OTHER, 0, 0);
+            HIPCHK(c, launch_gather_pool_rows(dt_copy, c->v_qkv, qc, B, c->vit_grid, C, p.pout, st, 3 * C));
+            if (r32) { HIPCHK(c, launch_gather_pool_rows(MMD_F32, c->v_h32, hc32, B, c->vit_grid, C, p.pout, st, C)); }
+            else { HIPCHK(c, launch_gather_pool_rows(dt_copy, c->v_h, hc, B, c->vit_grid, C, p.pout, st, C)); }
         }
-        {
-            AttnArgs a; memset(&a, 0, sizeof(a));
-            a.q = c->v_qkv; a.ldq = 3 * C; a.K = (char*)c->v_qkv + (size_t)C * es(c); a.V = (char*)c->v_qkv + (size_t)2 * C * es(c);
-            a.k_hs = hd; a.k_ts = 3 * C; a.v_hs = hd; a.v_ts = 3 * C; a.out = c->v_attn; a.ldo = C;
-            a.S = TS; a.nh = g.vit_heads; a.nkv = g.vit_heads; a.d = hd; a.n_ctx = 0; a.causal = 0;
-            a.batch = B; a.q_bstride = (int64_t)TS * 3 * C; a.kv_bstride = (int64_t)TS * 3 * C; a.o_bstride = (int64_t)TS * C;
-            a.ws = c->v_attn_ws; a.ws_bytes = c->v_attn_bytes; a.variant = 0;
-            ProfScope ps(c, MMD_K_ATTN_VIT, 4.0 * M * C * es(c), 4.0 * B * (double)TS * TS * C);
-            HIPCHK(c, launch_attention(dt, a, st));
-        }
-        if (r32) {
-            rc = gemm(c, c->v_attn, C, L.wo, C, L.bo, nullptr, 0, c->v_xn, C, M, C, C, EPI_NONE, 0, GEMM_AUTO, L.wo_p, true); if (rc) return rc;
-            { ProfScope ps(c, MMD_K_NORM_ROPE, 12.0 * M * C, 0); HIPCHK(c, launch_resid32_layernorm(c->v_xn, c->v_h32, nullptr, 1, L.ln2w, L.ln2b, c->v_xn, nullptr, M, C, g.vit_ln_eps, st)); }
-            const bool pm = gemm_pair_pm(c, true, c->v_xn, C, L.w1_p, L.b1, c->vit_ipad, C, EPI_GELU_TANH, c->v_mlp, c->vit_ipad, L.w2_p, C, nullptr, 0, c->v_xn, C, EPI_NONE, M);
-            rc = gemm(c, c->v_xn, C, L.w1, C, L.b1, nullptr, 0, c->v_mlp, c->vit_ipad, M, c->vit_ipad, C, EPI_GELU_TANH, 0, GEMM_AUTO, L.w1_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 2 : 0); if (rc) return rc;
-            rc = gemm(c, c->v_mlp, c->vit_ipad, L.w2, c->vit_ipad, L.b2, nullptr, 0, c->v_xn, C, M, C, c->vit_ipad, EPI_NONE, 0, GEMM_AUTO, L.w2_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 1 : 0); if (rc) return rc;
-            ProfScope ps(c, MMD_K_NORM_ROPE, 12.0 * M * C, 0);
-            if (i + 1 < g.vit_layers) { HIPCHK(c, launch_resid32_layernorm(c->v_xn, c->v_h32, nullptr, 1, c->VL[i + 1].ln1w, c->VL[i + 1].ln1b, c->v_xn, nullptr, M, C, g.vit_ln_eps, st)); }
-            else { HIPCHK(c, launch_resid32_layernorm(c->v_xn, c->v_h32, nullptr, 1, nullptr, nullptr, nullptr, c->v_h, M, C, g.vit_ln_eps, st)); }          // hidden_states[-1].to(bf16)
-            continue;
-        }
-        rc = gemm(c, c->v_attn, C, L.wo, C, L.bo, c->v_h, C, c->v_h, C, M, C, C, EPI_RESID, 0, GEMM_AUTO, L.wo_p, true); if (rc) return rc;
-        { ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * M * C * es(c), 0); HIPCHK(c, launch_layernorm(dt, c->v_h, L.ln2w, L.ln2b, c->v_xn, M, C, g.vit_ln_eps, st)); }
-        bool pm = false;          // fc1's output in the ring kernel's piece-major layout (its only reader is fc2)
-        if (g.vit_act == 1) {      // CLIP quick_gelu: plain fc1, then x * sigmoid(1.702 x) on the storage-rounded output (secondary path: not fused)
-            rc = gemm(c, c->v_xn, C, L.w1, C, L.b1, nullptr, 0, c->v_mlp, c->vit_ipad, M, c->vit_ipad, C, EPI_NONE, 0, GEMM_AUTO, L.w1_p, true); if (rc) return rc;
-            HIPCHK(c, launch_quick_gelu(dt, c->v_mlp, (int64_t)M * c->vit_ipad, st));
-        } else {
-            pm = gemm_pair_pm(c, true, c->v_xn, C, L.w1_p, L.b1, c->vit_ipad, C, EPI_GELU_TANH, c->v_mlp, c->vit_ipad, L.w2_p, C, c->v_h, C, c->v_h, C, EPI_RESID, M);
-            rc = gemm(c, c->v_xn, C, L.w1, C, L.b1, nullptr, 0, c->v_mlp, c->vit_ipad, M, c->vit_ipad, C, EPI_GELU_TANH, 0, GEMM_AUTO, L.w1_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 2 : 0); if (rc) return rc;
-        }
-        rc = gemm(c, c->v_mlp, c->vit_ipad, L.w2, c->vit_ipad, L.b2, c->v_h, C, c->v_h, C, M, C, c->vit_ipad, EPI_RESID, 0, GEMM_AUTO, L.w2_p, true, nullptr, nullptr, nullptr, nullptr, pm ? 1 : 0); if (rc) return rc;
+        rc = compact ? tower_attention(c, dt, qc, C, p.U, B) : tower_attention(c, dt, c->v_qkv, 3 * C, TS, B); if (rc) return rc;
+        const int rows = compact ? Mc : M; const bool pm = compact ? p.mlp_pm_last : p.mlp_pm;
+        if (r32) rc = tower_tail_f32(c, L, rows, compact ? hc32 : c->v_h32, pm, i + 1 < g.vit_layers ? &c->VL[i + 1] : nullptr, compact ? hc : c->v_h, compact ? 8.0 : 12.0);
+        else rc = tower_tail_epi(c, p, L, rows, compact ? hc : c->v_h, pm);
+        if (rc) return rc;
     }
-    if (g.vit_post_layernorm) { HIPCHK(c, launch_layernorm(dt, c->v_h, c->post_w, c->post_b, c->v_h, M, C, g.vit_ln_eps, st)); }
-    if (g.tower_f16 && !r32) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_convert(c->v_h, MMD_F16, c->v_h, MMD_BF16, (int64_t)M * C, st)); }          // in place, elementwise
+    if (g.vit_post_layernorm) { HIPCHK(c, launch_layernorm(dt, c->v_h, c->post_w, c->post_b, c->v_h, M, C, g.vit_ln_eps, st)); }          // (never with sparse_last)
+    if (p.final_convert) {          // the tower's output is rounded to bf16 at the end (SigLipVisionTower returns hidden_states[-1].to(images.dtype) [3P-recalled]): in place, elementwise
+        void* y = p.sparse_last ? hc : c->v_h;
+        ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_convert(y, MMD_F16, y, MMD_BF16, (int64_t)(p.sparse_last ? Mc : M) * C, st));
+    }
     c->last_vit_B = B;
     return MMD_OK;
 }
 
-extern "C" int mmd_vit_encode(mmd_ctx* c, const void* px, int B, void* out) {
+// Both encode entry points: checks, the plan, the im2col matrix -- from pixel_values px inside tower_run, or here straight from uint8 frames [B,3,R,R] (SURVEY.md section 8 f1:
+// image_processor.preprocess (test/inference.py:203) and the patch-embed load are one pass, the normalised pixels go from the Pillow-exact resampler directly into the im2col
+// matrix of the patch GEMM; no pixel_values tensor exists; bit-identical to mmd_preprocess_frames + mmd_vit_encode) -- the tower, then projector + pool on the rows the plan says
+static int vit_encode(mmd_ctx* c, const void* px, const uint8_t* frames, int B, int R, void* out) {
     NEED_FINAL(c);
     if (B <= 0) return MMD_OK;
+    if (!px && (!frames || !out)) return MMD_EINVAL;
     if (c->cfg.vision_only) FAIL(c, MMD_EINVAL, "vision-only context: use mmd_vision_tower");
-    int rc = vit_tower(c, px, B, false, true); if (rc) return rc;
-    return connector_pool(c, c->tower_compact ? c->v_col : c->v_h, B, out);
+    int rc = tower_begin(c, B, true); if (rc) return rc;
+    const TowerPlan& p = c->tower_last;
+    if (!px) {
+        rc = ensure_preprocess_tables(c, B, R); if (rc) return rc;
+        ProfScope ps(c, MMD_K_OTHER, 0, 0);
+        HIPCHK(c, launch_preprocess_im2col(p.dt, frames, B, R, c->cfg.vit_image, c->pp_coef, c->pp_bounds, c->pp_ksize, c->pp_tmp, c->cfg.vit_patch, c->vit_grid, c->vit_kpad, c->v_col, c->stream));
+    }
+    rc = tower_run(c, px, B); if (rc) return rc;
+    return connector_pool(c, p.sparse_last ? c->v_col : c->v_h, B, out, TowerProjectorPlan{p.proj_compact, p.proj_gather, p.pout});
 }
-
-// visual_embed straight from uint8 frames: image_processor.preprocess (test/inference.py:203) and the patch-embed load are one
-// pass -- the normalised pixels go from the Pillow-exact resampler directly into the im2col matrix of the patch GEMM; no pixel_values tensor exists.
-// frames uint8 [B,3,R,R] (device) -> out [B*frame_num_tokens, hidden]; bit-identical to mmd_preprocess_frames + mmd_vit_encode.
-extern "C" int mmd_vit_encode_frames(mmd_ctx* c, const uint8_t* frames, int B, int R, void* out) {
-    NEED_FINAL(c);
-    if (B <= 0) return MMD_OK;
-    if (!frames || !out) return MMD_EINVAL;
-    if (c->cfg.vision_only) FAIL(c, MMD_EINVAL, "vision-only context: use mmd_vision_tower");
-    if (B > c->cfg.max_vit_batch) FAIL(c, MMD_ERANGE, "vit batch %d exceeds max_vit_batch %d", B, c->cfg.max_vit_batch);
-    int rc = ensure_preprocess_tables(c, B, R); if (rc) return rc;
-    { ProfScope ps(c, MMD_K_OTHER, 0, 0);
-      HIPCHK(c, launch_preprocess_im2col(c->cfg.tower_f16 ? MMD_F16 : c->cfg.dtype, frames, B, R, c->cfg.vit_image, c->pp_coef, c->pp_bounds, c->pp_ksize, c->pp_tmp, c->cfg.vit_patch, c->vit_grid,
-                                         c->vit_kpad, c->v_col, c->stream)); }
-    rc = vit_tower(c, nullptr, B, true, true); if (rc) return rc;
-    return connector_pool(c, c->tower_compact ? c->v_col : c->v_h, B, out);
-}
+extern "C" int mmd_vit_encode(mmd_ctx* c, const void* px, int B, void* out) { return vit_encode(c, px, nullptr, B, 0, out); }
+// frames uint8 [B,3,R,R] (device) -> out [B*frame_num_tokens, hidden]
+extern "C" int mmd_vit_encode_frames(mmd_ctx* c, const uint8_t* frames, int B, int R, void* out) { return vit_encode(c, nullptr, frames, B, R, out); }
 
 // ---- secondary encoder path (models/vision_live.py) -------------------------------------------------------------------------------------
 extern "C" int mmd_normalize_frames(mmd_ctx* c, const void* frames, int src_kind, int B, int R, const float* mean, const float* sd, float rescale, void* out) {
@@ -813,7 +812,8 @@ extern "C" int mmd_vision_tower(mmd_ctx* c, const void* px, int B, void* out) {
     NEED_FINAL(c);
     if (B <= 0) return MMD_OK;
     if (!px || !out) return MMD_EINVAL;
-    int rc = vit_tower(c, px, B); if (rc) return rc;
+    int rc = tower_begin(c, B, false); if (rc) return rc;          // (not for the pool: every token's output, never the sparse last layer)
+    rc = tower_run(c, px, B); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(out, c->v_h, (size_t)B * c->vit_seq * c->cfg.vit_hidden * es(c), hipMemcpyDeviceToDevice, c->stream));
     return MMD_OK;
 }
@@ -857,25 +857,17 @@ extern "C" int mmd_vision_pool_head(mmd_ctx* c, const void* feats, int B, void* 
 }
 
 // second half of LiveMixin.visual_embed (models/modeling_live.py:30-33): mm_projector (Linear, GELU(erf), Linear) -> post_projector_pooling
-static int connector_pool(mmd_ctx* c, const void* feats, int B, void* out) {
+// rows (tower_plan.h): `compact` -- the projector runs on the rows the bilinear pool reads alone; `gather` -- feats holds every token and those rows are gathered here (else the
+// tower's sparse last layer already left exactly them in feats)
+static int connector_pool(mmd_ctx* c, const void* feats, int B, void* out, TowerProjectorPlan rows) {
     const mmd_config& g = c->cfg; const int dt = g.dtype; hipStream_t st = c->stream;
-    const int C = g.vit_hidden, H = g.hidden_size, M = B * c->vit_tokens;
-    // bilinear pooling reads (2 out)^2 tokens of each frame: run the (row-wise) projector on those alone -- 196 of 729 rows at the shipped sizes.  The class token, if
-    // any, is not among the grid tokens the pool reads (vit_seq > vit_tokens): `feats` rows are then indexed per frame by vit_tokens as before.
-    const int pout = (c->vit_grid + g.pool_stride - 1) / g.pool_stride;
-    if (g.pool_mode == MMD_POOL_BILINEAR && !c->full_projector && 4 * pout * pout < c->vit_tokens && c->vit_seq == c->vit_tokens) {
-        const int Mc = B * 4 * pout * pout;
-        const void* fc = feats;
-        if (c->tower_compact && feats == c->v_col) c->tower_compact = false;          // the tower already left exactly these rows (consumed once)
-        else { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_gather_pool_rows(dt, feats, c->v_xn, B, c->vit_grid, C, pout, st)); fc = c->v_xn; }
-        int rc = gemm(c, fc, C, c->p0w, C, c->p0b, nullptr, 0, c->v_p1, H, Mc, H, C, EPI_GELU_ERF, 0, GEMM_AUTO, c->p0w_p, true); if (rc) return rc;
-        rc = gemm(c, c->v_p1, H, c->p2w, H, c->p2b, nullptr, 0, c->v_p2, H, Mc, H, H, EPI_NONE, 0, GEMM_AUTO, c->p2w_p, true); if (rc) return rc;
-        { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_pool_compact_bilinear(dt, c->v_p2, out, B, c->vit_grid, H, pout, st)); }
-        return MMD_OK;
-    }
+    const int C = g.vit_hidden, H = g.hidden_size, pout = rows.pout, M = rows.compact ? B * TOWER_POOL_TAPS * pout * pout : B * c->vit_tokens;
+    if (rows.gather) { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_gather_pool_rows(dt, feats, c->v_xn, B, c->vit_grid, C, pout, st)); feats = c->v_xn; }
     int rc = gemm(c, feats, C, c->p0w, C, c->p0b, nullptr, 0, c->v_p1, H, M, H, C, EPI_GELU_ERF, 0, GEMM_AUTO, c->p0w_p, true); if (rc) return rc;
     rc = gemm(c, c->v_p1, H, c->p2w, H, c->p2b, nullptr, 0, c->v_p2, H, M, H, H, EPI_NONE, 0, GEMM_AUTO, c->p2w_p, true); if (rc) return rc;
-    { ProfScope ps(c, MMD_K_OTHER, 0, 0); HIPCHK(c, launch_pool(dt, c->v_p2, out, B, c->vit_grid, H, g.pool_mode, g.pool_stride, st)); }
+    ProfScope ps(c, MMD_K_OTHER, 0, 0);
+    if (rows.compact) { HIPCHK(c, launch_pool_compact_bilinear(dt, c->v_p2, out, B, c->vit_grid, H, pout, st)); }
+    else { HIPCHK(c, launch_pool(dt, c->v_p2, out, B, c->vit_grid, H, g.pool_mode, g.pool_stride, st)); }
     return MMD_OK;
 }
 
@@ -886,7 +878,7 @@ extern "C" int mmd_connector_pool(mmd_ctx* c, const void* tower_features, int B,
     if (B <= 0) return MMD_OK;
     if (B > c->cfg.max_vit_batch) FAIL(c, MMD_ERANGE, "feature batch %d exceeds max_vit_batch %d", B, c->cfg.max_vit_batch);
     if (!tower_features || !out) return MMD_EINVAL;
-    return connector_pool(c, tower_features, B, out);
+    return connector_pool(c, tower_features, B, out, tower_projector_plan(tower_model(c), false));
 }
 
 // feature extraction (vision_encode's [B, tokens, C]) and the debug taps need the tower's output for ALL tokens: on = the last layer is not restricted to the rows the pool reads
@@ -899,7 +891,7 @@ extern "C" int mmd_vit_get_full_tower(const mmd_ctx* c) { return c ? (c->full_to
 
 extern "C" int mmd_vit_debug_tap(mmd_ctx* c, int stage, void* out, int64_t out_elems) {
     NEED_FINAL(c);
-    if (c->last_sparse)          // only when the last encode really ran sparse (post_layernorm / class-token towers / U >= T never do): v_h holds no full output then
+    if (c->tower_last.sparse_last)          // only when the last encode really ran sparse (post_layernorm / class-token towers / U >= T never do): v_h holds no full output then
         FAIL(c, MMD_EINVAL, "mmd_vit_debug_tap needs mmd_vit_set_full_tower(ctx, 1) before the encode call (the default path computes the last layer for the pooled tokens only)");
     int64_t M = (int64_t)c->last_vit_B * c->vit_seq;
     int64_t n = M * (stage == 0 ? c->cfg.vit_hidden : c->cfg.hidden_size);
@@ -907,9 +899,7 @@ extern "C" int mmd_vit_debug_tap(mmd_ctx* c, int stage, void* out, int64_t out_e
     if (stage == 1 && c->last_vit_B > 0) {
         // the shipped path runs the projector on the tokens the bilinear pool reads; the tap wants connector() of ALL tokens: recompute it from the tower output
         // still sitting in v_h (debug entry point; the pooled result goes to a scratch row block of v_xn and is dropped)
-        c->full_projector = true;
-        const int rc = connector_pool(c, c->v_h, c->last_vit_B, c->v_xn);
-        c->full_projector = false;
+        const int rc = connector_pool(c, c->v_h, c->last_vit_B, c->v_xn, tower_projector_plan(tower_model(c), true));
         if (rc) return rc;
     }
     HIPCHK(c, hipMemcpyAsync(out, stage == 0 ? c->v_h : c->v_p2, (size_t)n * es(c), hipMemcpyDeviceToDevice, c->stream));
@@ -2602,7 +2592,7 @@ extern "C" int mmd_op_gemm_pair(mmd_ctx* c, const void* X, const void* W1, const
     void *W1p = nullptr, *W2p = nullptr, *mid = nullptr; int rc;
     if ((rc = make_packed(c, W1, N1, K1, &W1p)) || (rc = make_packed(c, W2, N2, T, &W2p)) || (rc = dev_alloc(c, &mid, (size_t)round_up(M, 16) * T * es(c)))) return rc;
     const int epi2 = R ? EPI_RESID : EPI_NONE;
-    const bool pm = piece_major && gemm_pair_pm(c, false, X, K1, W1p, b1, N1, K1, epi1, mid, T, W2p, N2, R, N2, Y, N2, epi2, M);
+    const bool pm = piece_major && gemm_pair_pm(c, X, K1, W1p, b1, N1, K1, epi1, mid, T, W2p, N2, R, N2, Y, N2, epi2, M);
     if (used_pm_out) *used_pm_out = pm ? 1 : 0;
     rc = gemm(c, X, K1, W1, K1, b1, nullptr, 0, mid, T, M, N1, K1, epi1, 0, GEMM_AUTO, W1p, false, nullptr, nullptr, nullptr, nullptr, pm ? 2 : 0);
     if (!rc) rc = gemm(c, mid, T, W2, T, nullptr, R, N2, Y, N2, M, N2, T, epi2, 0, GEMM_AUTO, W2p, false, nullptr, nullptr, nullptr, nullptr, pm ? 1 : 0);
@@ -2619,6 +2609,7 @@ extern "C" int mmd_op_gemm_last_plan(mmd_ctx* c, int* out4) {
 // the decode steps of the most recent generate call: 0 none or eager, 1 replayed an existing captured step, 2 captured in that call, then replayed
 extern "C" int mmd_op_decode_last_route(mmd_ctx* c) { return c ? c->dec_route : MMD_EINVAL; }
 extern "C" int mmd_op_step_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < STEP_PLAN_FIELDS; ++i) out[i] = c->step_last[i]; return MMD_OK; }
+extern "C" int mmd_op_tower_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; c->tower_last.fields(out); return MMD_OK; }
 extern "C" int mmd_op_round_last_record(mmd_ctx* c, int* out4) { if (!c || !out4) return MMD_EINVAL; for (int i = 0; i < ROUND_RECORD_FIELDS; ++i) out4[i] = c->round_record_last[i]; return MMD_OK; }
 extern "C" int mmd_op_select_last_plan(mmd_ctx* c, int* out) { if (!c || !out) return MMD_EINVAL; for (int i = 0; i < SELECT_LAST_FIELDS; ++i) out[i] = c->select_last[i]; return MMD_OK; }
 // times one GEMM shape on the context's stream with HIP events (weights packed once, outside the timed region)

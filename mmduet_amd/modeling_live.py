@@ -969,6 +969,15 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         check(lib().mmd_op_step_last_plan(self._ctx, out), self._ctx, 'step_last_plan')
         return dict(zip(self.STEP_PLAN_FIELDS, out))
 
+    TOWER_PLAN_FIELDS = ('dt', 'resid', 'embed', 'sparse_last', 'pout', 'U', 'compact_rows', 'proj_compact', 'proj_gather', 'mlp_pm', 'mlp_pm_last', 'final_convert')
+
+    def tower_last_plan(self):
+        """The schedule the most recent vision-tower run took (mmd_op_tower_last_plan): a dict over TOWER_PLAN_FIELDS; dt 0 fp32, 1 bf16, 2 IEEE half; resid 0 the GEMM
+        epilogue adds, 1 fp32 residual stream, 2 epilogue add in half; embed 0 add rows, 1 class token, 2 fp32 stream.  vit_debug_tap refuses exactly when sparse_last is set."""
+        out = (C.c_int * len(self.TOWER_PLAN_FIELDS))()
+        check(lib().mmd_op_tower_last_plan(self._ctx, out), self._ctx, 'tower_last_plan')
+        return dict(zip(self.TOWER_PLAN_FIELDS, out))
+
     SELECT_PLAN_FIELDS = ('kind', 'single', 'any_k', 'any_p', 'needs_row', 'needs_cons', 'record', 'scores_after_argmax', 'record_greedy', 'advance')
     GENERATE_PLAN_FIELDS = ('can_graph', 'upload_state', 'post_row_dynamic', 'post_row_each_eager_step', 'post_cons_dynamic', 'post_cons_each_eager_step', 'host_appends_penalty',
                             'pen_key_is_value', 'key_sel', 'key_lp', 'key_cons_gen')
