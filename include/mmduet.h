@@ -169,6 +169,24 @@ int mmd_kv_unstash(mmd_stream* s);
 int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to);
 int64_t mmd_kv_position(const mmd_stream* s);             /* RoPE position of the next token written: mmd_kv_len + tokens dropped (-1: null stream) */
 int mmd_stream_reset(mmd_stream* s);                      /* LiveInferForBenchmark.reset (test/inference.py:169-183: past_key_values = None): length 0, position 0, arena kept */
+/* Snapshots: take a stream's context out of its arena, put one in, hold one twice (no reference counterpart: the reference's DynamicCache is a list of torch tensors that
+ * callers clone or torch.save themselves).  The CANONICAL FORM is K, V [num_layers][num_kv_heads][n][head_dim] in the context's dtype, token-major for BOTH (keys rotated as
+ * they were written; V un-transposed out of the arena's 64-token blocks): it does not depend on the arena's capacity, row pitch or blocking.  The canonical buffers are device
+ * pointers, 16-byte aligned.  All four calls are enqueued on the context's stream without synchronising it (growing an arena maps pages on the host, as a step does).
+ * mmd_kv_export: tokens [from, to) of every (layer, kv head) row -> K_out / V_out [layers, nkv, to - from, d].  MMD_ERANGE unless 0 <= from <= to <= mmd_kv_len; from == to
+ *   enqueues nothing.  Allowed while a stash is held (it only reads).
+ * mmd_kv_import: n canonical tokens are appended at slots [len, len + n) and the length grows by n; the arena is grown first, as by a step.  Only those slots are written: in a
+ *   V block shared with older tokens the older tokens' bytes are untouched, and slots at or above the new length keep the finite values they had.  MMD_EINVAL while a stash is
+ *   held, MMD_ERANGE for n < 0.  The position offset is left alone: the appended tokens keep the rotation they carry, mmd_kv_set_position says where the next one goes.
+ * mmd_kv_set_position: the RoPE position of the next token written becomes `position` (mmd_kv_position returns it; the offset is position - len).  MMD_ERANGE if position < len.
+ *   Nothing else is checked: the call is accepted while a stash is held, and a position below that of tokens already written (they keep their rotation) is the caller's to avoid.
+ * mmd_kv_fork: dst becomes tokens [0, n) of src, with src's position offset: a device-to-device copy in arena form between the two arenas, which may differ in capacity and row
+ *   pitch; dst is grown first.  V travels in whole 64-token blocks, so slots >= n of dst hold unspecified finite values.  src is not changed in any byte.  MMD_ERANGE unless
+ *   0 <= n <= mmd_kv_len(src); MMD_EINVAL when dst == src, when the streams belong to different contexts, or while dst holds a stash. */
+int mmd_kv_export(mmd_stream* s, int64_t from, int64_t to, void* K_out, void* V_out);
+int mmd_kv_import(mmd_stream* s, const void* K_in, const void* V_in, int64_t n);
+int mmd_kv_set_position(mmd_stream* s, int64_t position);
+int mmd_kv_fork(mmd_stream* dst, const mmd_stream* src, int64_t n);
 int mmd_kv_debug_set_len(mmd_stream* s, int64_t n);       /* measurement aid: mark n slots live without computing them */
 
 /* replaces VideoHeadLiveLlavaQwenForCausalLM.forward body (models/live_llava/video_head_live_llava_qwen.py:141) ==

@@ -6,10 +6,10 @@ The arithmetic lives in mmduet_amd/csrc (libmmduet_hip.so, C ABI in include/mmdu
 """
 from .arguments_live import LiveTrainingArguments, LiveTestArguments, get_args_class, parse_args
 from .configuration_live import VideoHeadLiveLlavaQwenConfig
-from .modeling_live import (VideoHeadLiveLlavaQwenForCausalLM, VideoHeadCausalLMOutputWithPast, KVCacheHandle,
+from .modeling_live import (VideoHeadLiveLlavaQwenForCausalLM, VideoHeadCausalLMOutputWithPast, KVCacheHandle, KVSnapshot,
                             build_live, build_model_and_tokenizer, fast_greedy_generate)
 from .tokenization_live import build_live_tokenizer_and_update_config
 
 __all__ = ['LiveTrainingArguments', 'LiveTestArguments', 'get_args_class', 'parse_args', 'VideoHeadLiveLlavaQwenConfig',
-           'VideoHeadLiveLlavaQwenForCausalLM', 'VideoHeadCausalLMOutputWithPast', 'KVCacheHandle', 'build_live',
+           'VideoHeadLiveLlavaQwenForCausalLM', 'VideoHeadCausalLMOutputWithPast', 'KVCacheHandle', 'KVSnapshot', 'build_live',
            'build_model_and_tokenizer', 'fast_greedy_generate', 'build_live_tokenizer_and_update_config']

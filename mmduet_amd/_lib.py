@@ -73,6 +73,10 @@ _SIGS = {
     'mmd_kv_unstash': (_I, [_VP]),
     'mmd_kv_drop': (_I, [_VP, _I64, _I64]),
     'mmd_kv_position': (_I64, [_VP]),
+    'mmd_kv_export': (_I, [_VP, _I64, _I64, _VP, _VP]),
+    'mmd_kv_import': (_I, [_VP, _VP, _VP, _I64]),
+    'mmd_kv_set_position': (_I, [_VP, _I64]),
+    'mmd_kv_fork': (_I, [_VP, _VP, _I64]),
     'mmd_comm_unique_id': (_I, [_VP]),
     'mmd_comm_create': (_I, [_VP, _I, _I, _I, _VP, C.POINTER(_VP)]),
     'mmd_comm_destroy': (None, [_VP]),

@@ -1228,6 +1228,67 @@ extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) {
 }
 extern "C" int64_t mmd_kv_position(const mmd_stream* s) { return s ? s->len + s->pos_off : -1; }          // the RoPE position the next token gets
 
+// ---- snapshots: take a context out of its arena, put one in, hold one twice (DESIGN.md section 5 "Snapshots") -----------------------------------------------
+// The canonical form K, V [layers][kv heads][n][d] is token-major for both and has the context's dtype: nothing in it depends on the arena's capacity, pitch or
+// V blocking.  launch_kv_canon converts; a fork stays in arena form (the stash's strided copy between two pitches).
+static int kv_canon_check(mmd_ctx* c, const char* what, const void* K, const void* V) {
+    const size_t tok = (size_t)c->cfg.head_dim * es(c);
+    if (!K || !V) FAIL(c, MMD_EINVAL, "%s: a canonical buffer is missing", what);
+    if ((((uintptr_t)K | (uintptr_t)V) & 15) != 0) FAIL(c, MMD_EINVAL, "%s: the canonical buffers must be 16-byte aligned", what);
+    if (tok % 16 != 0 || tok > 1024 || (size_t)c->cfg.num_layers * c->cfg.num_kv_heads > 65535) FAIL(c, MMD_EINVAL, "%s: head_dim %d x %zu bytes (a multiple of 16, at most 1 KiB) or %d x %d rows not supported", what, c->cfg.head_dim, es(c), c->cfg.num_layers, c->cfg.num_kv_heads);
+    return MMD_OK;
+}
+extern "C" int mmd_kv_export(mmd_stream* s, int64_t from, int64_t to, void* K_out, void* V_out) {
+    if (!s) return MMD_EINVAL;
+    mmd_ctx* c = s->ctx;
+    if (from < 0 || to < from || to > s->len) FAIL(c, MMD_ERANGE, "kv_export [%lld, %lld) outside the context (%lld tokens)", (long long)from, (long long)to, (long long)s->len);
+    if (from == to) return MMD_OK;
+    int rc = kv_canon_check(c, "kv_export", K_out, V_out); if (rc) return rc;
+    hipSetDevice(c->device);
+    const size_t tok = (size_t)c->cfg.head_dim * es(c);
+    HIPCHK(c, launch_kv_canon(c->cfg.dtype, 0, s->K, s->V, c->cfg.num_layers * c->cfg.num_kv_heads, (int64_t)((size_t)s->cap * tok), c->cfg.head_dim, from, to - from, K_out, V_out, c->stream));
+    return MMD_OK;
+}
+extern "C" int mmd_kv_import(mmd_stream* s, const void* K_in, const void* V_in, int64_t n) {
+    if (!s) return MMD_EINVAL;
+    mmd_ctx* c = s->ctx;
+    if (n < 0) FAIL(c, MMD_ERANGE, "kv_import of %lld tokens", (long long)n);
+    if (s->stash_from >= 0) FAIL(c, MMD_EINVAL, "kv_import while tokens [%lld, %lld) are stashed (unstash or drop the stash first)", (long long)s->stash_from, (long long)s->stash_to);
+    if (n == 0) return MMD_OK;
+    int rc = kv_canon_check(c, "kv_import", K_in, V_in); if (rc) return rc;
+    hipSetDevice(c->device);
+    rc = kv_reserve(c, s, s->len + n); if (rc) return rc;
+    const size_t tok = (size_t)c->cfg.head_dim * es(c);
+    HIPCHK(c, launch_kv_canon(c->cfg.dtype, 1, s->K, s->V, c->cfg.num_layers * c->cfg.num_kv_heads, (int64_t)((size_t)s->cap * tok), c->cfg.head_dim, s->len, n, (void*)K_in, (void*)V_in, c->stream));
+    s->len += n;
+    return MMD_OK;
+}
+extern "C" int mmd_kv_set_position(mmd_stream* s, int64_t position) {
+    if (!s) return MMD_EINVAL;
+    if (position < s->len) FAIL(s->ctx, MMD_ERANGE, "kv_set_position(%lld) below the context's %lld tokens", (long long)position, (long long)s->len);
+    s->pos_off = position - s->len;
+    return MMD_OK;
+}
+extern "C" int mmd_kv_fork(mmd_stream* dst, const mmd_stream* src, int64_t n) {
+    if (!dst || !src) return MMD_EINVAL;
+    mmd_ctx* c = dst->ctx;
+    if (src->ctx != c) FAIL(c, MMD_EINVAL, "kv_fork: the two streams belong to different contexts");
+    if (dst == src) FAIL(c, MMD_EINVAL, "kv_fork: a stream cannot be forked onto itself");
+    if (dst->stash_from >= 0) FAIL(c, MMD_EINVAL, "kv_fork onto a stream whose tokens [%lld, %lld) are stashed", (long long)dst->stash_from, (long long)dst->stash_to);
+    if (n < 0 || n > src->len) FAIL(c, MMD_ERANGE, "kv_fork of %lld tokens from a context of %lld", (long long)n, (long long)src->len);
+    hipSetDevice(c->device);
+    int rc = kv_reserve(c, dst, n); if (rc) return rc;
+    const size_t tok = (size_t)c->cfg.head_dim * es(c), rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads;
+    const size_t wk = (size_t)n * tok, wv = (size_t)((n + 63) >> 6) * 64 * tok;          // V in whole blocks, like the stash: slots [n, block end) of dst get src's (finite) bytes
+    if (wv / 4 > 0x7fffffff) FAIL(c, MMD_EINVAL, "kv_fork: %lld tokens are more than one copy launch takes", (long long)n);
+    if (n) {
+        HIPCHK(c, launch_copy_rows(MMD_F32, src->K, (int64_t)((size_t)src->cap * tok / 4), dst->K, (int64_t)((size_t)dst->cap * tok / 4), (int)rows, (int)(wk / 4), c->stream));
+        HIPCHK(c, launch_copy_rows(MMD_F32, src->V, (int64_t)((size_t)src->cap * tok / 4), dst->V, (int64_t)((size_t)dst->cap * tok / 4), (int)rows, (int)(wv / 4), c->stream));
+    }
+    dst->len = n; dst->pos_off = src->pos_off;
+    return MMD_OK;
+}
+
 // measurement aid (tools/kv_growth_sweep.py): declare the first n slots of the arena live without computing them, to time a
 // step at a given context length (the slots hold zeros / stale data -- numerically meaningless, same memory traffic)
 extern "C" int mmd_kv_debug_set_len(mmd_stream* s, int64_t n) {

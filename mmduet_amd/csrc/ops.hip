@@ -1097,6 +1097,130 @@ hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_b
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// mmd_kv_export / mmd_kv_import: the arena <-> the canonical form K, V [rows][n][d] (token-major for both, rows = layers x kv heads), bit for bit.  Tokens
+// [t0, t0 + n) of every arena row are gathered into the canonical rows, or n canonical tokens are scattered into slots [t0, t0 + n).
+//   K: the tokens are one contiguous span on both sides.  Blocks x < kseg copy KVC_SEG bytes of it each, 16 bytes per lane, all loads before the first store.
+//   V: block x - kseg owns ONE 64-token block of the arena row, [d][64] = 64 d ES contiguous bytes (16 KB at d = 128 in bf16).  The canonical rows of the block's
+//   tokens are contiguous too, so both sides move in 16-byte units of consecutive lanes; the transposition happens in LDS.  The LDS image is token-major, 16-byte
+//   slots [64][d / VEC], slot q of token t stored at slot (q + t / VEC) % (d / VEC) of its row: the VEC element stores of an arena group (one per token, the same
+//   dims) and the lanes next to it (the next token group, or the next dim) then spread over the banks instead of all landing d ES bytes apart on one.
+//   gather: the whole arena block is read (a block that holds a live token is mapped to its end), only the tokens in [t0, t0 + n) are written.
+//   scatter: only canonical tokens inside the span are read; an arena group of VEC tokens that lies inside the span is one 16-byte store, the group that holds an
+//   end of the span is stored element by element inside the span only -- the older tokens below t0 and the slots at or above t0 + n keep their bytes.
+// grid (kseg + V blocks, rows); the row pitch is the (virtual) arena's, every offset is 64-bit.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int KVC_THREADS = 256, KVC_U = 4, KVC_SEG = KVC_THREADS * KVC_U * 16;
+extern __shared__ __attribute__((aligned(16))) unsigned char kvc_lds[];
+template <int ES, bool SCATTER>
+__global__ __launch_bounds__(KVC_THREADS) void kv_canon_kernel(char* __restrict__ Ka, char* __restrict__ Va, long long pitch, char* __restrict__ Kc, char* __restrict__ Vc,
+                                                                int d, long long t0, long long n, int kseg) {
+    constexpr int VEC = 16 / ES, CPL = 64 / VEC;          // elements per 16 bytes, 16-byte groups per 64-token line of the arena
+    typedef typename std::conditional<ES == 2, unsigned short, unsigned>::type elem_t;
+    union Pack { u32x4_t v; elem_t e[VEC]; };
+    const int tid = threadIdx.x;
+    const long long tokb = (long long)d * ES, row = blockIdx.y;
+    if ((int)blockIdx.x < kseg) {
+        const long long span = n * tokb, seg0 = (long long)blockIdx.x * KVC_SEG;
+        char* a = Ka + row * pitch + t0 * tokb;
+        char* c = Kc + row * span;
+        const char* src = SCATTER ? c : a;
+        char* dst = SCATTER ? a : c;
+        u32x4_t r[KVC_U];
+#pragma unroll
+        for (int u = 0; u < KVC_U; ++u) {
+            const long long off = seg0 + (long long)(u * KVC_THREADS + tid) * 16;
+            if (off < span) r[u] = *reinterpret_cast<const u32x4_t*>(src + off);
+        }
+#pragma unroll
+        for (int u = 0; u < KVC_U; ++u) {
+            const long long off = seg0 + (long long)(u * KVC_THREADS + tid) * 16;
+            if (off < span) *reinterpret_cast<u32x4_t*>(dst + off) = r[u];
+        }
+        return;
+    }
+    const int SL = d / VEC, nvec = 64 * SL;               // 16-byte slots per token, per block
+    const long long blk = (t0 >> 6) + ((int)blockIdx.x - kseg), tb = blk << 6, t1 = t0 + n;
+    char* a = Va + row * pitch + blk * 64 * tokb;          // the arena block [d][64]
+    char* c = Vc + row * n * tokb;                         // canonical row: token t at (t - t0) * tokb
+    elem_t* le = reinterpret_cast<elem_t*>(kvc_lds);
+    u32x4_t* lv = reinterpret_cast<u32x4_t*>(kvc_lds);
+    if (!SCATTER) {
+        for (int i0 = 0; i0 < nvec; i0 += KVC_THREADS * KVC_U) {
+            Pack r[KVC_U];
+#pragma unroll
+            for (int u = 0; u < KVC_U; ++u) {
+                const int i = i0 + u * KVC_THREADS + tid;
+                if (i < nvec) r[u].v = *reinterpret_cast<const u32x4_t*>(a + (long long)i * 16);
+            }
+#pragma unroll
+            for (int u = 0; u < KVC_U; ++u) {
+                const int i = i0 + u * KVC_THREADS + tid;
+                if (i >= nvec) continue;
+                const int e = i / CPL, g = i % CPL, slot = (e / VEC + g) % SL;
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) le[((g * VEC + k) * SL + slot) * VEC + e % VEC] = r[u].e[k];
+            }
+        }
+        __syncthreads();
+        for (int j = tid; j < nvec; j += KVC_THREADS) {
+            const int t = j / SL, q = j % SL;
+            const long long tt = tb + t;
+            if (tt < t0 || tt >= t1) continue;
+            *reinterpret_cast<u32x4_t*>(c + (tt - t0) * tokb + q * 16) = lv[t * SL + (q + t / VEC) % SL];
+        }
+    } else {
+        for (int j0 = 0; j0 < nvec; j0 += KVC_THREADS * KVC_U) {
+            u32x4_t r[KVC_U];          // (an r[u] that was not loaded -- its token lies outside the span -- is not written to LDS either, and the LDS slots nobody wrote are never stored)
+#pragma unroll
+            for (int u = 0; u < KVC_U; ++u) {
+                const int j = j0 + u * KVC_THREADS + tid;
+                const long long tt = tb + j / SL;
+                if (j < nvec && tt >= t0 && tt < t1) r[u] = *reinterpret_cast<const u32x4_t*>(c + (tt - t0) * tokb + (j % SL) * 16);
+            }
+#pragma unroll
+            for (int u = 0; u < KVC_U; ++u) {
+                const int j = j0 + u * KVC_THREADS + tid;
+                const int t = j / SL, q = j % SL;
+                const long long tt = tb + t;
+                if (j < nvec && tt >= t0 && tt < t1) lv[t * SL + (q + t / VEC) % SL] = r[u];
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < nvec; i += KVC_THREADS) {
+            const int e = i / CPL, g = i % CPL, slot = (e / VEC + g) % SL;
+            const long long tg = tb + g * VEC;             // first token of the arena group
+            if (tg + VEC <= t0 || tg >= t1) continue;
+            Pack o;
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) o.e[k] = le[((g * VEC + k) * SL + slot) * VEC + e % VEC];          // (tokens outside the span: LDS bytes nobody wrote, never stored)
+            char* dst = a + (long long)i * 16;
+            if (tg >= t0 && tg + VEC <= t1) *reinterpret_cast<u32x4_t*>(dst) = o.v;
+            else {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) if (tg + k >= t0 && tg + k < t1) reinterpret_cast<elem_t*>(dst)[k] = o.e[k];
+            }
+        }
+    }
+}
+hipError_t launch_kv_canon(int dtype, int scatter, void* K_arena, void* V_arena, int rows, int64_t pitch_bytes, int d, int64_t t0, int64_t n, void* K_canon, void* V_canon,
+                           hipStream_t st) {
+    if (t0 < 0 || n < 0) return hipErrorInvalidValue;
+    if (n == 0 || rows <= 0) return hipSuccess;
+    const int es = (int)dtype_size(dtype);
+    const size_t lds = (size_t)64 * d * es;
+    if (d <= 0 || (d * es) % 16 != 0 || (pitch_bytes % 16) != 0 || rows > 65535 || lds > 64 * 1024) return hipErrorInvalidValue;
+    if ((((uintptr_t)K_arena | (uintptr_t)V_arena | (uintptr_t)K_canon | (uintptr_t)V_canon) & 15) != 0) return hipErrorInvalidValue;
+    const int64_t kseg = (n * d * es + KVC_SEG - 1) / KVC_SEG, nvb = ((t0 + n + 63) >> 6) - (t0 >> 6);
+    if (kseg + nvb > 0x7fffffff) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(kseg + nvb), rows), block(KVC_THREADS);
+#define KVC(ES_, SC_) hipLaunchKernelGGL((kv_canon_kernel<ES_, SC_>), grid, block, lds, st, (char*)K_arena, (char*)V_arena, (long long)pitch_bytes, (char*)K_canon, (char*)V_canon, d, (long long)t0, (long long)n, (int)kseg)
+    if (es == 4) { if (scatter) KVC(4, true); else KVC(4, false); }
+    else { if (scatter) KVC(2, true); else KVC(2, false); }
+#undef KVC
+    return hipGetLastError();
+}
+
 // out rows: [a 0..15, b 0..15, a 16..31, b 16..31, ...]  (gate/up interleave for the SwiGLU epilogue)
 template <typename T>
 __global__ void interleave16_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, int rows, int cols) {

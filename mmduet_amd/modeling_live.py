@@ -101,6 +101,73 @@ class KVCacheHandle:
         return self.length
 
 
+_MMD2TORCH = {MMD_F32: torch.float32, MMD_BF16: torch.bfloat16}
+_SNAPSHOT_FORMAT = 1
+
+
+def snapshot_chunks(n, token_bytes, staging_bytes):
+    """Token ranges [(a, b), ...] that cover [0, n) exactly once, each small enough that its K and V (`token_bytes` per token together) fit in `staging_bytes`;
+    a budget below one token's bytes gives one token per chunk."""
+    n, per = int(n), max(1, int(staging_bytes) // max(1, int(token_bytes)))
+    return [(a, min(a + per, n)) for a in range(0, n, per)]
+
+
+class KVSnapshot:
+    """A stream's KV context outside any arena (DESIGN.md section 5 "Snapshots"): host tensors K, V [layers, kv_heads, n, head_dim] in the canonical, token-major form,
+    the rotary position the next token gets, the dtype, and a fingerprint of the model geometry the keys were rotated for (layers, kv heads, head_dim, rope inv_freq).
+    Not in it: the repetition-penalty list, sampler state and driver fields -- they remain the caller's."""
+    FIELDS = ('layers', 'kv_heads', 'head_dim')
+
+    def __init__(self, K, V, position, dtype, layers, kv_heads, head_dim, inv_freq):
+        self.K, self.V, self.position, self.dtype = K, V, int(position), dtype
+        self.layers, self.kv_heads, self.head_dim = int(layers), int(kv_heads), int(head_dim)
+        self.inv_freq = inv_freq.detach().to('cpu', torch.float32).contiguous()
+        want = (self.layers, self.kv_heads, K.shape[2] if K.ndim == 4 else -1, self.head_dim)
+        for name, t in (('K', K), ('V', V)):
+            if tuple(t.shape) != want or t.dtype != dtype:
+                raise ValueError(f'KVSnapshot.{name}: shape {tuple(t.shape)} / {t.dtype}, expected [layers, kv_heads, n, head_dim] = {want[:2]} x n x {want[3]} in {dtype}')
+        if self.position < self.length:
+            raise ValueError(f'KVSnapshot.position {self.position} below its {self.length} tokens')
+
+    @property
+    def length(self):
+        return int(self.K.shape[2])
+
+    def __len__(self):
+        return self.length
+
+    def state_dict(self):
+        """plain tensors and ints: torch.save / torch.load round-trip it"""
+        return {'format': _SNAPSHOT_FORMAT, 'K': self.K, 'V': self.V, 'position': self.position, 'dtype': _TORCH2MMD[self.dtype], 'layers': self.layers,
+                'kv_heads': self.kv_heads, 'head_dim': self.head_dim, 'inv_freq': self.inv_freq}
+
+    @classmethod
+    def from_state_dict(cls, d):
+        if d.get('format') != _SNAPSHOT_FORMAT:
+            raise ValueError(f"KVSnapshot: format {d.get('format')!r}, this package reads format {_SNAPSHOT_FORMAT}")
+        if d['dtype'] not in _MMD2TORCH:
+            raise ValueError(f"KVSnapshot: unknown dtype code {d['dtype']!r}")
+        return cls(d['K'], d['V'], d['position'], _MMD2TORCH[d['dtype']], d['layers'], d['kv_heads'], d['head_dim'], d['inv_freq'])
+
+    def save(self, path):
+        torch.save(self.state_dict(), path)
+
+    @classmethod
+    def load(cls, path):
+        return cls.from_state_dict(torch.load(path, map_location='cpu'))
+
+    def check_against(self, dtype, layers, kv_heads, head_dim, inv_freq):
+        """ValueError naming the first field in which this snapshot differs from a model's geometry (kv_load)"""
+        if self.dtype != dtype:
+            raise ValueError(f'KVSnapshot mismatch in dtype: the snapshot holds {self.dtype}, the model runs {dtype}')
+        for name, mine, theirs in zip(self.FIELDS, (self.layers, self.kv_heads, self.head_dim), (layers, kv_heads, head_dim)):
+            if mine != int(theirs):
+                raise ValueError(f'KVSnapshot mismatch in {name}: the snapshot has {mine}, the model {int(theirs)}')
+        other = inv_freq.detach().to('cpu', torch.float32)
+        if other.shape != self.inv_freq.shape or not torch.equal(other.view(torch.int32), self.inv_freq.view(torch.int32)):
+            raise ValueError('KVSnapshot mismatch in inv_freq: the keys were rotated with another rope table')
+
+
 _U64 = (1 << 64) - 1
 # generate() arguments that ask for something this package does not build: the value that means "off" is accepted, anything else raises
 _GENERATE_OFF = {'num_beams': 1, 'num_beam_groups': 1, 'num_return_sequences': 1, 'min_p': None, 'typical_p': 1.0, 'penalty_alpha': None, 'epsilon_cutoff': 0.0, 'eta_cutoff': 0.0,
@@ -384,6 +451,7 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         d = config.head_dim
         inv = (1.0 / (float(config.rope_theta) ** (torch.arange(0, d, 2, dtype=torch.float) / d))).contiguous()
         check(L.mmd_set_rope_inv_freq(self._ctx, C.c_void_p(inv.data_ptr()), d // 2), self._ctx, 'mmd_set_rope_inv_freq')
+        self._rope_inv_freq = inv          # part of a KVSnapshot's fingerprint: stored keys carry this rotation
 
     # ---- lifecycle ----------------------------------------------------------------------------------------------
     def release_pooled_arenas(self):
@@ -629,6 +697,82 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         with self._lock:
             h = handle.arena.h
             return handle.length + int(lib().mmd_kv_position(h)) - int(lib().mmd_kv_len(h))
+
+    # ---- snapshots (DESIGN.md section 5 "Snapshots") ----------------------------------------------------------------------
+    def _kv_geometry(self):
+        c = self.config
+        return c.num_hidden_layers, c.num_key_value_heads, c.head_dim
+
+    def _kv_source(self, cache, what):
+        """-> (arena or None, length) of the context `cache` denotes; a stale or foreign handle raises"""
+        if cache is None or (isinstance(cache, KVCacheHandle) and cache.arena is None):
+            return None, 0
+        if not isinstance(cache, KVCacheHandle) or cache.arena.model is not self:
+            raise TypeError(f'{what}: the cache must be a KVCacheHandle produced by this model (or None)')
+        if cache.stale:
+            raise RuntimeError('stale KV handle')
+        return cache.arena, cache.length
+
+    def _snapshot_arena(self, n):
+        """The arena kv_load / kv_fork write into (the lock is held).  The stream is bound BEFORE the arena is made: a newly created arena queues the zero-fill of its
+        pages on the context's stream, and the copy that follows must be behind it on the same stream."""
+        self._bind_stream()
+        return _KVArena(self, max(n, self.kv_initial_tokens))
+
+    def kv_save(self, cache: KVCacheHandle, pin: bool = True, staging_bytes: int = 256 << 20) -> KVSnapshot:
+        """The whole context `cache` denotes, [0, len(cache)), as a KVSnapshot in host memory (pinned when `pin`).  The arena is exported in chunks of tokens whose
+        device staging buffers stay within `staging_bytes`; the arena and every handle of it stay as they are."""
+        arena, n = self._kv_source(cache, 'kv_save')
+        layers, nkv, d = self._kv_geometry()
+        K = torch.empty(layers, nkv, n, d, dtype=self.dtype, pin_memory=bool(pin) and n > 0)
+        V = torch.empty_like(K, pin_memory=bool(pin) and n > 0)
+        position = 0
+        if arena is not None:
+            token_bytes = 2 * layers * nkv * d * K.element_size()
+            chunks = snapshot_chunks(n, token_bytes, staging_bytes)
+            with self._lock:
+                position = n + int(lib().mmd_kv_position(arena.h)) - int(lib().mmd_kv_len(arena.h))
+                if n:
+                    self._bind_stream()
+                    m = max(b - a for a, b in chunks)
+                    sk = torch.empty(layers * nkv * m * d, dtype=self.dtype, device=self.device)
+                    sv = torch.empty_like(sk)
+                    for a, b in chunks:
+                        ck, cv = (s[:layers * nkv * (b - a) * d].view(layers, nkv, b - a, d) for s in (sk, sv))
+                        check(lib().mmd_kv_export(arena.h, a, b, _ptr(ck), _ptr(cv)), self._ctx, 'mmd_kv_export')
+                        K[:, :, a:b].copy_(ck)          # (blocking: the staging buffers are reused by the next chunk)
+                        V[:, :, a:b].copy_(cv)
+        return KVSnapshot(K, V, position, self.dtype, layers, nkv, d, self._rope_inv_freq)
+
+    def kv_load(self, snapshot: KVSnapshot, staging_bytes: int = 256 << 20) -> KVCacheHandle:
+        """A handle on a fresh arena holding the snapshot's context; `kv_position` of it is the snapshot's.  The snapshot may come from another model instance,
+        process or device; a dtype or fingerprint mismatch raises ValueError naming the field."""
+        layers, nkv, d = self._kv_geometry()
+        snapshot.check_against(self.dtype, layers, nkv, d, self._rope_inv_freq)
+        n = snapshot.length
+        with self._lock:
+            arena = self._snapshot_arena(n)
+            if n:
+                chunks = snapshot_chunks(n, 2 * layers * nkv * d * snapshot.K.element_size(), staging_bytes)
+                m = max(b - a for a, b in chunks)
+                sk = torch.empty(layers * nkv * m * d, dtype=self.dtype, device=self.device)
+                sv = torch.empty_like(sk)
+                for a, b in chunks:
+                    ck, cv = (s[:layers * nkv * (b - a) * d].view(layers, nkv, b - a, d) for s in (sk, sv))
+                    ck.copy_(snapshot.K[:, :, a:b]); cv.copy_(snapshot.V[:, :, a:b])
+                    check(lib().mmd_kv_import(arena.h, _ptr(ck), _ptr(cv), b - a), self._ctx, 'mmd_kv_import')
+            check(lib().mmd_kv_set_position(arena.h, snapshot.position), self._ctx, 'mmd_kv_set_position')
+        return KVCacheHandle(arena, n)
+
+    def kv_fork(self, cache: KVCacheHandle) -> KVCacheHandle:
+        """A handle on a fresh arena holding `cache`'s context (device copy, stream-ordered).  `cache` and every other handle of its arena stay valid, and nothing done
+        to either arena afterwards -- steps, truncate, drop, stash -- is visible in the other."""
+        src, n = self._kv_source(cache, 'kv_fork')
+        with self._lock:
+            arena = self._snapshot_arena(n)
+            if src is not None:
+                check(lib().mmd_kv_fork(arena.h, src.h, n), self._ctx, 'mmd_kv_fork')
+        return KVCacheHandle(arena, n)
 
     def new_cache(self, initial_tokens=None):
         return KVCacheHandle(_KVArena(self, initial_tokens or self.kv_initial_tokens), 0)
