@@ -6,7 +6,8 @@ A row is (name, reach, layout, dtype, S, nh, nkv, d, n_ctx, causal, variant, ove
   * reach -- 'op': mmd_op_attention builds exactly these AttnArgs (the GPU test runs the row);  'host': host-only.  mmd_op_attention hands the kernels row-major K / V
     and transposes V only for the forced variants 3, 5 and 6, so it reaches the GQA-128 forms through those variants alone: the AUTOMATIC choices over the arena (the
     w1 rule, the chunk rule), the graph-replayed and slab-fed decode forms, the tower's fused-qkv layout, other workspaces than 128 MB, form 9 and every rejection are
-    host-only rows.  On the device those are covered by the model-level tests of tests/test_gpu_production.py; the tower rows (tower_d72, tower_d72_pooled_queries,
+    host-only rows.  On the device those are covered by the model-level tests of tests/test_gpu_production.py (benign data) and of tests/test_gpu_llm_stress.py (a sink
+    key, q / k biases of 50 .. 60, outlier channels and saturated gates over live contexts: forms 4, 5, 8 and 9, the graph-replayed and the slab-fed decode); the tower rows (tower_d72, tower_d72_pooled_queries,
     tower_d72_f16, tower_d72_f32: the fused [tokens, 3C] layout, batch strides, 196 gathered query rows over 729 keys) also by tests/test_gpu_tower_stress.py, on
     peaked scores (three register keys at +30 .. +80) and outlier channels, in the fp32, bf16 and both fp16 towers.
   * layout -- which caller's AttnArgs build_args() builds: 'op' mmd_op_attention (K / V [nkv, cap, d], cap = n_ctx + S rounded up to 64, 128 MB of workspace);  'arena' the

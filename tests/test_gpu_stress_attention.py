@@ -22,8 +22,8 @@ bf16 ulp (exact in the reference), and variants 3, 5 and 6 agree with each other
 
 Forms (mmd_op_attention_last_form, asserted per case): 1 one wave per row, 2 16-row MFMA, 3 decode ring / 64-row, 4 two-slot 128-row and 256-row
 phase-split, 5 attn_gqa128_w1_kernel, 6 register-staged row-major (d = 64, and d = 72 with MMDUET_VIT_ATTN_RING=0), 7 attn_d72_ring_kernel,
-8 attn_gqa128_chunk_kernel + combine.  Form 9 (several streams' decode rows in one launch) is reachable only through mmd_round_multi:
-no case here reaches it; a model-level stream on sink-structured weights is the follow-up that would.
+8 attn_gqa128_chunk_kernel + combine.  Form 9 (several streams' decode rows in one launch) is reachable only through mmd_round_multi /
+multi_step: no case here reaches it; tests/test_gpu_llm_stress.py does, at model level on sink-structured and large-bias weights over live contexts.
 
 Measured errors are recorded under stress_attn_<form>_<pattern>_S.._n.. (_record of tests/test_gpu_production.py).  On an MI355X, largest max|o - ref| / max(1, max|ref|) over
 the shapes of each variant (sink, last_hot and first_row_only: exactly 0 on every form):
