@@ -10,6 +10,7 @@
 #include "step_plan.h"
 #include "tower_plan.h"
 #include "select_plan.h"
+#include "kv_plan.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -1041,12 +1042,15 @@ extern "C" int mmd_embed_tokens(mmd_ctx* c, const int64_t* ids, int k, void* out
     return MMD_OK;
 }
 
-static size_t kv_layer_elems(const mmd_ctx* c, int64_t cap) { return (size_t)c->cfg.num_kv_heads * cap * c->cfg.head_dim; }
+// ---- the stream KV arena: kv_plan.h states its geometry, what every operation on it checks, launches and leaves behind, and the capacities growth tries; the code here makes
+// the runtime calls
+static KvGeom kv_geom(const mmd_ctx* c) { KvGeom g; g.layers = c->cfg.num_layers; g.kv_heads = c->cfg.num_kv_heads; g.head_dim = c->cfg.head_dim; g.elem_bytes = (int)es(c); return g; }
+static KvState kv_state(const mmd_stream* s) { KvState k; k.len = s->len; k.pos_off = s->pos_off; k.cap = s->cap; k.mapped = s->mapped; k.stash_from = s->stash_from; k.stash_to = s->stash_to; return k; }
 
 // Map physical pages behind tokens [s->mapped, upto) of every (layer, kv head) row of K and V (whole chunks).
 static int vmm_map_upto(mmd_ctx* c, mmd_stream* s, int64_t upto) {
-    const size_t e = es(c), tok_bytes = (size_t)c->cfg.head_dim * e;
-    const size_t rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads, row_stride = (size_t)s->cap * tok_bytes;
+    const KvGeom g = kv_geom(c);
+    const size_t tok_bytes = g.tok_bytes(), rows = g.rows(), row_stride = g.pitch_bytes(s->cap);
     hipMemAllocationProp prop = {};
     prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = c->device;
     hipMemAccessDesc acc = {};
@@ -1076,7 +1080,6 @@ static int vmm_map_upto(mmd_ctx* c, mmd_stream* s, int64_t upto) {
                 s->handles.push_back(h); s->maps.push_back({at, cb});
                 er = hipMemSetAccess(at, cb, &acc, 1);
                 if (er != hipSuccess) { undo(); FAIL(c, MMD_EHIP, "KV arena: hipMemSetAccess failed: %s", hipGetErrorString(er)); }
-                // key tiles may cover slots beyond the live length (their P is masked to 0): keep those slots finite
                 HIPCHK(c, hipMemsetAsync(at, 0, cb, c->stream));
             }
         s->mapped += s->chunk_tokens;
@@ -1095,28 +1098,24 @@ static void vmm_release(mmd_stream* s) {
 extern "C" int mmd_stream_create(mmd_ctx* c, int64_t initial_tokens, mmd_stream** out) {
     if (!c || !out) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (initial_tokens < 256) initial_tokens = 256;
-    initial_tokens = round_up(initial_tokens, 64);
+    initial_tokens = kv_initial_tokens(initial_tokens);
     mmd_stream* s = new mmd_stream();
     s->ctx = c; s->len = 0;
-    const size_t e = es(c), tok_bytes = (size_t)c->cfg.head_dim * e;
-    const size_t rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads;
-    // --- virtual-memory arena: reserve the row stride once (default 4 Mi tokens = the HBM limit of the 7B model), back it on demand
+    const KvGeom g = kv_geom(c);
+    // --- virtual-memory arena: reserve the row stride once, back it on demand
     const char* nv = getenv("MMDUET_KV_NO_VMM");
     if (!(nv && nv[0] == '1')) {
         hipMemAllocationProp prop = {};
         prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = c->device;
         size_t gran = 0;
         if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) == hipSuccess && gran > 0) {
-            int64_t ct = 64; while (((size_t)ct * tok_bytes) % gran != 0) ct += 64;          // chunk = whole 64-token V blocks and whole pages
-            while ((size_t)ct * tok_bytes < ((size_t)2 << 20)) ct *= 2;                         // at least 2 MiB per row and step
+            const int64_t ct = kv_vmm_chunk_tokens(g.tok_bytes(), gran);
             const char* ev = getenv("MMDUET_KV_VIRTUAL_TOKENS");
-            int64_t vcap = ev ? atoll(ev) : ((int64_t)4 << 20);
-            if (vcap < initial_tokens) vcap = initial_tokens;
-            vcap = round_up(vcap, ct);
-            // (a halved reservation is rounded to whole chunks again: the row stride must stay a multiple of the allocation granularity)
-            for (; vcap >= round_up(initial_tokens, ct); vcap = vcap > round_up(initial_tokens, ct) ? std::max((int64_t)round_up(vcap / 2, ct), (int64_t)round_up(initial_tokens, ct)) : 0) {
-                const size_t va = rows * (size_t)vcap * tok_bytes;
+            int64_t tries[KV_MAX_RESERVATIONS];
+            const int n_tries = kv_vmm_reservations(initial_tokens, ev ? atoll(ev) : KV_VIRTUAL_TOKENS_DEFAULT, ct, tries);
+            for (int t = 0; t < n_tries; ++t) {
+                const int64_t vcap = tries[t];
+                const size_t va = g.arena_bytes(vcap);
                 void *K = nullptr, *V = nullptr;
                 if (hipMemAddressReserve(&K, va, gran, nullptr, 0) == hipSuccess && hipMemAddressReserve(&V, va, gran, nullptr, 0) == hipSuccess) {
                     s->vmm = true; s->K = K; s->V = V; s->cap = vcap; s->chunk_tokens = ct; s->va_bytes = va; s->mapped = 0;
@@ -1124,7 +1123,6 @@ extern "C" int mmd_stream_create(mmd_ctx* c, int64_t initial_tokens, mmd_stream*
                 }
                 if (K) hipMemAddressFree(K, va);
                 (void)hipGetLastError();
-                if (vcap == round_up(initial_tokens, ct)) break;
             }
         }
         (void)hipGetLastError();
@@ -1137,10 +1135,9 @@ extern "C" int mmd_stream_create(mmd_ctx* c, int64_t initial_tokens, mmd_stream*
     }
     // --- fallback: plain allocation, growth by reallocation + copy
     s->cap = initial_tokens; s->mapped = initial_tokens;
-    size_t bytes = kv_layer_elems(c, s->cap) * c->cfg.num_layers * es(c);
+    size_t bytes = g.arena_bytes(s->cap);
     hipError_t e1 = hipMalloc(&s->K, bytes), e2 = hipMalloc(&s->V, bytes);
     if (e1 != hipSuccess || e2 != hipSuccess) { if (s->K) hipFree(s->K); if (s->V) hipFree(s->V); delete s; FAIL(c, MMD_ENOMEM, "KV arena of %lld tokens (%zu bytes x2) does not fit", (long long)initial_tokens, bytes); }
-    // key tiles may cover slots beyond the live length (their P is masked to 0): keep those slots finite
     hipMemsetAsync(s->K, 0, bytes, c->stream); hipMemsetAsync(s->V, 0, bytes, c->stream);
     *out = s;
     return MMD_OK;
@@ -1153,182 +1150,19 @@ extern "C" void mmd_stream_destroy(mmd_stream* s) {
     if (s->stash_k) { hipFree(s->stash_k); hipFree(s->stash_v); }
     delete s;
 }
-extern "C" int64_t mmd_kv_len(const mmd_stream* s) { return s ? s->len : -1; }
-extern "C" int64_t mmd_kv_capacity(const mmd_stream* s) { return s ? s->mapped : -1; }          // tokens with memory behind them
-extern "C" int64_t mmd_kv_stride(const mmd_stream* s) { return s ? s->cap : -1; }                // row stride in tokens (= reserved virtual capacity)
-extern "C" int mmd_kv_truncate(mmd_stream* s, int64_t n) {
-    if (!s) return MMD_EINVAL;
-    if (n < 0 || n > s->len) FAIL(s->ctx, MMD_ERANGE, "kv_truncate(%lld) outside [0, %lld]", (long long)n, (long long)s->len);
-    s->len = n;
-    if (n < s->stash_from) s->stash_from = s->stash_to = -1;          // the context a stash continued no longer exists
-    return MMD_OK;
-}
-
-static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need);
-// Set the KV of tokens [from, to) aside and bring it back later: lets a caller roll the arena back to `from`, run something that overwrites those slots
-// (a response whose turn is NOT kept in the context, remove_assistant_turns, test/inference.py:265-269) and then continue with the frames it had
-// already encoded behind `from` instead of recomputing them.  K rows are copied as they are; V travels in whole 64-token blocks (its layout), which
-// also carry -- unchanged -- the slots just below `from`.
-extern "C" int mmd_kv_stash(mmd_stream* s, int64_t from, int64_t to) {
-    if (!s) return MMD_EINVAL;
-    mmd_ctx* c = s->ctx;
-    if (from < 0 || to < from || to > s->len) FAIL(c, MMD_ERANGE, "kv_stash [%lld, %lld) outside the context (%lld tokens)", (long long)from, (long long)to, (long long)s->len);
-    hipSetDevice(c->device);
-    const size_t e = es(c), tok = (size_t)c->cfg.head_dim * e, rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads, pitch = (size_t)s->cap * tok;
-    const int64_t b0 = from >> 6, b1 = (to + 63) >> 6;
-    const size_t wk = (size_t)(to - from) * tok, wv = (size_t)(b1 - b0) * 64 * tok;
-    if (rows * std::max(wk, wv) > s->stash_bytes) {
-        if (s->stash_k) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(s->stash_k); hipFree(s->stash_v); s->stash_k = s->stash_v = nullptr; }
-        s->stash_bytes = rows * std::max(wk, wv);
-        if (hipMalloc(&s->stash_k, s->stash_bytes) != hipSuccess || hipMalloc(&s->stash_v, s->stash_bytes) != hipSuccess) { s->stash_bytes = 0; FAIL(c, MMD_ENOMEM, "kv_stash: no memory for %zu bytes x2", rows * std::max(wk, wv)); }
-    }
-    // (strided copy kernel: hipMemcpy2D rejects the GiB-scale row pitch of the virtual-memory arena)
-    if (wk) HIPCHK(c, launch_copy_rows(MMD_F32, (const char*)s->K + (size_t)from * tok, (int64_t)(pitch / 4), s->stash_k, (int64_t)(wk / 4), (int)rows, (int)(wk / 4), c->stream));
-    if (wv) HIPCHK(c, launch_copy_rows(MMD_F32, (const char*)s->V + (size_t)b0 * 64 * tok, (int64_t)(pitch / 4), s->stash_v, (int64_t)(wv / 4), (int)rows, (int)(wv / 4), c->stream));
-    s->stash_from = from; s->stash_to = to;
-    return MMD_OK;
-}
-extern "C" int mmd_kv_unstash(mmd_stream* s) {
-    if (!s) return MMD_EINVAL;
-    mmd_ctx* c = s->ctx;
-    if (s->stash_from < 0) FAIL(c, MMD_EINVAL, "kv_unstash without a (still valid) stash");
-    // the stash continues the context [0, from): the arena must stand exactly there (tokens >= from are overwritten, tokens of the V blocks just below `from`
-    // come back with their stash-time values, so nothing below `from` may have changed either -- a truncate below `from` or a reset drops the stash)
-    if (s->len != s->stash_from) FAIL(c, MMD_EINVAL, "kv_unstash: the arena holds %lld tokens, the stash continues a context of %lld (truncate to it first)", (long long)s->len, (long long)s->stash_from);
-    hipSetDevice(c->device);
-    const int64_t from = s->stash_from, to = s->stash_to;
-    int rc = kv_reserve(c, s, to); if (rc) return rc;
-    const size_t e = es(c), tok = (size_t)c->cfg.head_dim * e, rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads, pitch = (size_t)s->cap * tok;
-    const int64_t b0 = from >> 6, b1 = (to + 63) >> 6;
-    const size_t wk = (size_t)(to - from) * tok, wv = (size_t)(b1 - b0) * 64 * tok;
-    if (wk) HIPCHK(c, launch_copy_rows(MMD_F32, s->stash_k, (int64_t)(wk / 4), (char*)s->K + (size_t)from * tok, (int64_t)(pitch / 4), (int)rows, (int)(wk / 4), c->stream));
-    if (wv) HIPCHK(c, launch_copy_rows(MMD_F32, s->stash_v, (int64_t)(wv / 4), (char*)s->V + (size_t)b0 * 64 * tok, (int64_t)(pitch / 4), (int)rows, (int)(wv / 4), c->stream));
-    s->len = to; s->stash_from = s->stash_to = -1;
-    return MMD_OK;
-}
-
-extern "C" int mmd_stream_reset(mmd_stream* s) { if (!s) return MMD_EINVAL; s->len = 0; s->pos_off = 0; s->stash_from = s->stash_to = -1; return MMD_OK; }
-
-// Sliding context window: slots [from, to) leave every layer's arena, the tokens behind them move down bit for bit (keys keep the rotation they were written
-// with) and the stream goes on counting RoPE positions where it was: position = slot + pos_off.  One launch on the context's stream (launch_kv_drop), no
-// host synchronisation; pages stay mapped; slots at or above the new length hold unspecified bits.
-extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) {
-    if (!s) return MMD_EINVAL;
-    mmd_ctx* c = s->ctx;
-    if (from < 0 || to < from || to > s->len) FAIL(c, MMD_ERANGE, "kv_drop [%lld, %lld) outside the context (%lld tokens)", (long long)from, (long long)to, (long long)s->len);
-    if (s->stash_from >= 0) FAIL(c, MMD_EINVAL, "kv_drop while tokens [%lld, %lld) are stashed (unstash or drop the stash first)", (long long)s->stash_from, (long long)s->stash_to);
-    if (from == to) return MMD_OK;
-    if (to < s->len) {
-        hipSetDevice(c->device);
-        const size_t tok = (size_t)c->cfg.head_dim * es(c);
-        HIPCHK(c, launch_kv_drop(c->cfg.dtype, s->K, s->V, c->cfg.num_layers * c->cfg.num_kv_heads, (int64_t)((size_t)s->cap * tok), c->cfg.head_dim, from, to, s->len, c->stream));
-    }
-    s->len -= to - from; s->pos_off += to - from;
-    return MMD_OK;
-}
-extern "C" int64_t mmd_kv_position(const mmd_stream* s) { return s ? s->len + s->pos_off : -1; }          // the RoPE position the next token gets
-
-// ---- snapshots: take a context out of its arena, put one in, hold one twice (DESIGN.md section 5 "Snapshots") -----------------------------------------------
-// The canonical form K, V [layers][kv heads][n][d] is token-major for both and has the context's dtype: nothing in it depends on the arena's capacity, pitch or
-// V blocking.  launch_kv_canon converts; a fork stays in arena form (the stash's strided copy between two pitches).
-static int kv_canon_check(mmd_ctx* c, const char* what, const void* K, const void* V) {
-    const size_t tok = (size_t)c->cfg.head_dim * es(c);
-    if (!K || !V) FAIL(c, MMD_EINVAL, "%s: a canonical buffer is missing", what);
-    if ((((uintptr_t)K | (uintptr_t)V) & 15) != 0) FAIL(c, MMD_EINVAL, "%s: the canonical buffers must be 16-byte aligned", what);
-    if (tok % 16 != 0 || tok > 1024 || (size_t)c->cfg.num_layers * c->cfg.num_kv_heads > 65535) FAIL(c, MMD_EINVAL, "%s: head_dim %d x %zu bytes (a multiple of 16, at most 1 KiB) or %d x %d rows not supported", what, c->cfg.head_dim, es(c), c->cfg.num_layers, c->cfg.num_kv_heads);
-    return MMD_OK;
-}
-extern "C" int mmd_kv_export(mmd_stream* s, int64_t from, int64_t to, void* K_out, void* V_out) {
-    if (!s) return MMD_EINVAL;
-    mmd_ctx* c = s->ctx;
-    if (from < 0 || to < from || to > s->len) FAIL(c, MMD_ERANGE, "kv_export [%lld, %lld) outside the context (%lld tokens)", (long long)from, (long long)to, (long long)s->len);
-    if (from == to) return MMD_OK;
-    int rc = kv_canon_check(c, "kv_export", K_out, V_out); if (rc) return rc;
-    hipSetDevice(c->device);
-    const size_t tok = (size_t)c->cfg.head_dim * es(c);
-    HIPCHK(c, launch_kv_canon(c->cfg.dtype, 0, s->K, s->V, c->cfg.num_layers * c->cfg.num_kv_heads, (int64_t)((size_t)s->cap * tok), c->cfg.head_dim, from, to - from, K_out, V_out, c->stream));
-    return MMD_OK;
-}
-extern "C" int mmd_kv_import(mmd_stream* s, const void* K_in, const void* V_in, int64_t n) {
-    if (!s) return MMD_EINVAL;
-    mmd_ctx* c = s->ctx;
-    if (n < 0) FAIL(c, MMD_ERANGE, "kv_import of %lld tokens", (long long)n);
-    if (s->stash_from >= 0) FAIL(c, MMD_EINVAL, "kv_import while tokens [%lld, %lld) are stashed (unstash or drop the stash first)", (long long)s->stash_from, (long long)s->stash_to);
-    if (n == 0) return MMD_OK;
-    int rc = kv_canon_check(c, "kv_import", K_in, V_in); if (rc) return rc;
-    hipSetDevice(c->device);
-    rc = kv_reserve(c, s, s->len + n); if (rc) return rc;
-    const size_t tok = (size_t)c->cfg.head_dim * es(c);
-    HIPCHK(c, launch_kv_canon(c->cfg.dtype, 1, s->K, s->V, c->cfg.num_layers * c->cfg.num_kv_heads, (int64_t)((size_t)s->cap * tok), c->cfg.head_dim, s->len, n, (void*)K_in, (void*)V_in, c->stream));
-    s->len += n;
-    return MMD_OK;
-}
-extern "C" int mmd_kv_set_position(mmd_stream* s, int64_t position) {
-    if (!s) return MMD_EINVAL;
-    if (position < s->len) FAIL(s->ctx, MMD_ERANGE, "kv_set_position(%lld) below the context's %lld tokens", (long long)position, (long long)s->len);
-    s->pos_off = position - s->len;
-    return MMD_OK;
-}
-extern "C" int mmd_kv_fork(mmd_stream* dst, const mmd_stream* src, int64_t n) {
-    if (!dst || !src) return MMD_EINVAL;
-    mmd_ctx* c = dst->ctx;
-    if (src->ctx != c) FAIL(c, MMD_EINVAL, "kv_fork: the two streams belong to different contexts");
-    if (dst == src) FAIL(c, MMD_EINVAL, "kv_fork: a stream cannot be forked onto itself");
-    if (dst->stash_from >= 0) FAIL(c, MMD_EINVAL, "kv_fork onto a stream whose tokens [%lld, %lld) are stashed", (long long)dst->stash_from, (long long)dst->stash_to);
-    if (n < 0 || n > src->len) FAIL(c, MMD_ERANGE, "kv_fork of %lld tokens from a context of %lld", (long long)n, (long long)src->len);
-    hipSetDevice(c->device);
-    int rc = kv_reserve(c, dst, n); if (rc) return rc;
-    const size_t tok = (size_t)c->cfg.head_dim * es(c), rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads;
-    const size_t wk = (size_t)n * tok, wv = (size_t)((n + 63) >> 6) * 64 * tok;          // V in whole blocks, like the stash: slots [n, block end) of dst get src's (finite) bytes
-    if (wv / 4 > 0x7fffffff) FAIL(c, MMD_EINVAL, "kv_fork: %lld tokens are more than one copy launch takes", (long long)n);
-    if (n) {
-        HIPCHK(c, launch_copy_rows(MMD_F32, src->K, (int64_t)((size_t)src->cap * tok / 4), dst->K, (int64_t)((size_t)dst->cap * tok / 4), (int)rows, (int)(wk / 4), c->stream));
-        HIPCHK(c, launch_copy_rows(MMD_F32, src->V, (int64_t)((size_t)src->cap * tok / 4), dst->V, (int64_t)((size_t)dst->cap * tok / 4), (int)rows, (int)(wv / 4), c->stream));
-    }
-    dst->len = n; dst->pos_off = src->pos_off;
-    return MMD_OK;
-}
-
-// measurement aid (tools/kv_growth_sweep.py): declare the first n slots of the arena live without computing them, to time a
-// step at a given context length (the slots hold zeros / stale data -- numerically meaningless, same memory traffic)
-extern "C" int mmd_kv_debug_set_len(mmd_stream* s, int64_t n) {
-    if (!s || n < 0) return MMD_EINVAL;
-    hipSetDevice(s->ctx->device);
-    int rc = kv_reserve(s->ctx, s, n); if (rc) return rc;
-    s->len = n;
-    return MMD_OK;
-}
-
-// test aid (tests/test_gpu_kv_arena.py): the first n tokens of one layer as the arena stores them -- K_out [nkv, n, d], V_out [nkv, n / 64, d, 64] (device, context dtype).
-// Nothing is un-transposed and no address beyond token n of a row is touched (the row stride may be virtual).  Synchronises the stream.
-extern "C" int mmd_kv_debug_read(mmd_stream* s, int layer, int64_t n, void* K_out, void* V_out) {
-    if (!s) return MMD_EINVAL;
-    mmd_ctx* c = s->ctx;
-    if (!K_out || !V_out || layer < 0 || layer >= c->cfg.num_layers) FAIL(c, MMD_EINVAL, "kv_debug_read: layer %d of %d, or an output buffer missing", layer, c->cfg.num_layers);
-    if (n < 0 || (n % 64) != 0 || n > s->mapped) FAIL(c, MMD_EINVAL, "kv_debug_read: n = %lld must be a multiple of 64 within the %lld tokens backed by memory", (long long)n, (long long)s->mapped);
-    hipSetDevice(c->device);
-    const size_t e = es(c), tok = (size_t)c->cfg.head_dim * e, le = kv_layer_elems(c, s->cap) * e;
-    const int64_t pitch = (int64_t)((size_t)s->cap * tok / 4), w = (int64_t)((size_t)n * tok / 4);          // in 4-byte units, like the stash copies
-    if (w > 0x7fffffff / c->cfg.num_kv_heads) FAIL(c, MMD_EINVAL, "kv_debug_read: %lld tokens are more than one copy launch takes", (long long)n);
-    HIPCHK(c, launch_copy_rows(MMD_F32, (const char*)s->K + (size_t)layer * le, pitch, K_out, w, c->cfg.num_kv_heads, (int)w, c->stream));
-    HIPCHK(c, launch_copy_rows(MMD_F32, (const char*)s->V + (size_t)layer * le, pitch, V_out, w, c->cfg.num_kv_heads, (int)w, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return MMD_OK;
-}
 
 static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need) {
     if (need <= s->mapped) return MMD_OK;
     if (s->vmm) return vmm_map_upto(c, s, need);            // growth = more pages behind the same addresses: no copy, no second arena
-    int64_t ncap = s->cap * 2; while (ncap < need) ncap *= 2;
-    size_t e = es(c);
-    size_t bytes = kv_layer_elems(c, ncap) * c->cfg.num_layers * e;
+    const KvGeom g = kv_geom(c);
+    int64_t ncap = kv_grow_doubled(s->cap, need);
+    size_t bytes = g.arena_bytes(ncap);
     void *nK = nullptr, *nV = nullptr;
     if (hipMalloc(&nK, bytes) != hipSuccess || hipMalloc(&nV, bytes) != hipSuccess) {
-        // doubling does not fit next to the old arena: fall back to the exact need (+1/8 headroom)
         if (nK) { hipFree(nK); nK = nullptr; }
         (void)hipGetLastError();
-        ncap = round_up(need + need / 8, 64);
-        bytes = kv_layer_elems(c, ncap) * c->cfg.num_layers * e;
+        ncap = kv_grow_exact(need);
+        bytes = g.arena_bytes(ncap);
         if (hipMalloc(&nK, bytes) != hipSuccess || hipMalloc(&nV, bytes) != hipSuccess) {
             if (nK) hipFree(nK);
             (void)hipGetLastError();
@@ -1336,15 +1170,88 @@ static int kv_reserve(mmd_ctx* c, mmd_stream* s, int64_t need) {
         }
     }
     hipMemsetAsync(nK, 0, bytes, c->stream); hipMemsetAsync(nV, 0, bytes, c->stream);
-    size_t rows = (size_t)c->cfg.num_layers * c->cfg.num_kv_heads;
-    size_t w = (size_t)round_up(s->len, 64) * c->cfg.head_dim * e;        // V is stored in whole 64-token blocks
+    const size_t w = kv_grow_copy_bytes(g, s->len);
     if (w) {
-        HIPCHK(c, hipMemcpy2DAsync(nK, (size_t)ncap * c->cfg.head_dim * e, s->K, (size_t)s->cap * c->cfg.head_dim * e, w, rows, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpy2DAsync(nV, (size_t)ncap * c->cfg.head_dim * e, s->V, (size_t)s->cap * c->cfg.head_dim * e, w, rows, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(nK, g.pitch_bytes(ncap), s->K, g.pitch_bytes(s->cap), w, g.rows(), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(nV, g.pitch_bytes(ncap), s->V, g.pitch_bytes(s->cap), w, g.rows(), hipMemcpyDeviceToDevice, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     hipFree(s->K); hipFree(s->V);
     s->K = nK; s->V = nV; s->cap = ncap; s->mapped = ncap;
+    return MMD_OK;
+}
+
+static int kv_bufs(const void* K, const void* V) { return !K || !V ? KV_BUF_MISSING : (((uintptr_t)K | (uintptr_t)V) & 15) != 0 ? KV_BUF_MISALIGNED : KV_BUF_OK; }
+// the K and V launch_copy_rows pair of a plan's spans, between the arena (K, V) and the other side (Ko, Vo)
+static int kv_copy_pair(mmd_ctx* c, const KvPlan& p, char* K, char* V, void* Ko, void* Vo) {
+    if (p.launch == KV_ROWS_OUT) {
+        HIPCHK(c, launch_copy_rows(MMD_F32, K + p.k_off, p.pitch4, Ko, p.k_other4, p.copy_rows, (int)p.k_cols, c->stream));
+        HIPCHK(c, launch_copy_rows(MMD_F32, V + p.v_off, p.pitch4, Vo, p.v_other4, p.copy_rows, (int)p.v_cols, c->stream));
+    } else {
+        HIPCHK(c, launch_copy_rows(MMD_F32, Ko, p.k_other4, K + p.k_off, p.pitch4, p.copy_rows, (int)p.k_cols, c->stream));
+        HIPCHK(c, launch_copy_rows(MMD_F32, Vo, p.v_other4, V + p.v_off, p.pitch4, p.copy_rows, (int)p.v_cols, c->stream));
+    }
+    return MMD_OK;
+}
+// One operation on s's arena as kv_plan states it: refused, or -- in this order -- memory behind the tokens it needs, the stash buffers, the launches, the bookkeeping.
+// Ko / Vo: the side of the launches that is not s's arena -- the caller's buffers, a fork's source arena, nullptr for the stash buffers
+static int kv_run(mmd_stream* s, int op, int64_t a = 0, int64_t b = 0, const mmd_stream* src = nullptr, const void* Ko = nullptr, const void* Vo = nullptr) {
+    mmd_ctx* c = s->ctx; const KvGeom g = kv_geom(c);
+    KvState from; if (src) from = kv_state(src);
+    auto plan = [&]() { return kv_plan(op, g, kv_state(s), a, b, src ? &from : nullptr, kv_bufs(Ko, Vo)); };
+    KvPlan p = plan();
+    if (p.rc != MMD_OK) FAIL(c, p.rc, "%s", p.error);
+    if (p.nothing) return MMD_OK;
+    if (p.reserve || p.stash_bytes || p.launch != KV_LAUNCH_NONE) hipSetDevice(c->device);
+    if (p.reserve) {
+        int rc = kv_reserve(c, s, p.reserve); if (rc) return rc;
+        p = plan();          // (the fallback arena grows into another row stride)
+    }
+    if (p.stash_bytes > s->stash_bytes) {
+        if (s->stash_k) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(s->stash_k); hipFree(s->stash_v); s->stash_k = s->stash_v = nullptr; }
+        s->stash_bytes = p.stash_bytes;
+        if (hipMalloc(&s->stash_k, s->stash_bytes) != hipSuccess || hipMalloc(&s->stash_v, s->stash_bytes) != hipSuccess) { s->stash_bytes = 0; FAIL(c, MMD_ENOMEM, "kv_stash: no memory for %zu bytes x2", p.stash_bytes); }
+    }
+    if (!Ko) { Ko = s->stash_k; Vo = s->stash_v; }
+    const int rows = (int)g.rows();
+    switch (p.launch) {
+    case KV_ROWS_OUT: case KV_ROWS_IN: { int rc = kv_copy_pair(c, p, (char*)s->K, (char*)s->V, (void*)Ko, (void*)Vo); if (rc) return rc; break; }
+    case KV_LAUNCH_DROP: HIPCHK(c, launch_kv_drop(c->cfg.dtype, s->K, s->V, rows, p.pitch_bytes, g.head_dim, p.t0, p.t1, s->len, c->stream)); break;
+    case KV_CANON_GATHER: case KV_CANON_SCATTER:
+        HIPCHK(c, launch_kv_canon(c->cfg.dtype, p.launch == KV_CANON_SCATTER ? 1 : 0, s->K, s->V, rows, p.pitch_bytes, g.head_dim, p.t0, p.t1, (void*)Ko, (void*)Vo, c->stream)); break;
+    default: break;
+    }
+    s->len = p.after.len; s->pos_off = p.after.pos_off; s->stash_from = p.after.stash_from; s->stash_to = p.after.stash_to;
+    return MMD_OK;
+}
+
+extern "C" int64_t mmd_kv_len(const mmd_stream* s) { return s ? s->len : -1; }
+extern "C" int64_t mmd_kv_capacity(const mmd_stream* s) { return s ? s->mapped : -1; }          // tokens with memory behind them
+extern "C" int64_t mmd_kv_stride(const mmd_stream* s) { return s ? s->cap : -1; }                // row stride in tokens (= reserved virtual capacity)
+extern "C" int64_t mmd_kv_position(const mmd_stream* s) { return s ? s->len + s->pos_off : -1; }          // the RoPE position the next token gets
+extern "C" int mmd_kv_truncate(mmd_stream* s, int64_t n) { return s ? kv_run(s, KV_TRUNCATE, n) : MMD_EINVAL; }
+extern "C" int mmd_stream_reset(mmd_stream* s) { return s ? kv_run(s, KV_RESET) : MMD_EINVAL; }
+extern "C" int mmd_kv_stash(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_STASH, from, to) : MMD_EINVAL; }
+extern "C" int mmd_kv_unstash(mmd_stream* s) { return s ? kv_run(s, KV_UNSTASH) : MMD_EINVAL; }
+extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_DROP, from, to) : MMD_EINVAL; }
+// snapshots (DESIGN.md section 5 "Snapshots")
+extern "C" int mmd_kv_export(mmd_stream* s, int64_t from, int64_t to, void* K_out, void* V_out) { return s ? kv_run(s, KV_EXPORT, from, to, nullptr, K_out, V_out) : MMD_EINVAL; }
+extern "C" int mmd_kv_import(mmd_stream* s, const void* K_in, const void* V_in, int64_t n) { return s ? kv_run(s, KV_IMPORT, n, 0, nullptr, K_in, V_in) : MMD_EINVAL; }
+extern "C" int mmd_kv_set_position(mmd_stream* s, int64_t position) { return s ? kv_run(s, KV_SET_POSITION, position) : MMD_EINVAL; }
+extern "C" int mmd_kv_fork(mmd_stream* dst, const mmd_stream* src, int64_t n) {
+    if (!dst || !src) return MMD_EINVAL;
+    mmd_ctx* c = dst->ctx;
+    // (these two compare pointers, so they stand here, in front of kv_plan's checks as they always did)
+    if (src->ctx != c) FAIL(c, MMD_EINVAL, "kv_fork: the two streams belong to different contexts");
+    if (dst == src) FAIL(c, MMD_EINVAL, "kv_fork: a stream cannot be forked onto itself");
+    return kv_run(dst, KV_FORK, n, 0, src, src->K, src->V);
+}
+extern "C" int mmd_kv_debug_set_len(mmd_stream* s, int64_t n) { return s && n >= 0 ? kv_run(s, KV_DEBUG_SET_LEN, n) : MMD_EINVAL; }
+// (synchronises the stream)
+extern "C" int mmd_kv_debug_read(mmd_stream* s, int layer, int64_t n, void* K_out, void* V_out) {
+    if (!s) return MMD_EINVAL;
+    int rc = kv_run(s, KV_DEBUG_READ, layer, n, nullptr, K_out, V_out); if (rc) return rc;
+    HIPCHK(s->ctx, hipStreamSynchronize(s->ctx->stream));
     return MMD_OK;
 }
 
@@ -1415,8 +1322,8 @@ static int layer_qkv(StepRun& r, int i, int* splits) {
     ProfScope ps(c, MMD_K_NORM_ROPE, 2.0 * S * c->qkv_w * e, 0);
     for (int j = 0; j < r.nseg; ++j) {
         const StepSeg& sg = r.segs[j]; mmd_stream* sj = sg.s;
-        const size_t le = kv_layer_elems(c, sj->cap);
-        void* q = (char*)c->l_q + (size_t)sg.row0 * nh * d * e; void* K = (char*)sj->K + (size_t)i * le * e; void* V = (char*)sj->V + (size_t)i * le * e;
+        const size_t lb = kv_geom(c).layer_bytes(sj->cap);
+        void* q = (char*)c->l_q + (size_t)sg.row0 * nh * d * e; void* K = (char*)sj->K + (size_t)i * lb; void* V = (char*)sj->V + (size_t)i * lb;
         if (r.p.schedule != STEP_TILE)
             HIPCHK(c, launch_slab_rope_append(c->splitk_ws + (size_t)sg.row0 * c->qkv_w, *splits, L.bqkv, sg.rows, nh, nkv, d, c->inv_freq, sj->len, q, K, V, sj->cap, st, r.dyn, i, S, sj->pos_off));
         else if (r.p.chunk_rope)          // vectorised form over the step's (cos, sin) table (built once, before the layer loop)
@@ -1456,10 +1363,10 @@ static int layer_attention(const StepRun& r, int i, int splits) {
     for (int j = 0; j < r.nseg; ++j) {
         if (j >= run0 && j < run0 + run_n) continue;
         mmd_stream* sj = r.segs[j].s;
-        const size_t le = kv_layer_elems(c, sj->cap);
+        const size_t lb = kv_geom(c).layer_bytes(sj->cap);
         const int Sj = r.segs[j].rows; const int64_t nj = sj->len;
         AttnArgs a = attn_args(r, i, r.segs[j].row0, Sj, splits);
-        a.K = (char*)sj->K + (size_t)i * le * e; a.V = (char*)sj->V + (size_t)i * le * e;
+        a.K = (char*)sj->K + (size_t)i * lb; a.V = (char*)sj->V + (size_t)i * lb;
         a.k_hs = sj->cap * d; a.v_hs = sj->cap * d; a.n_ctx = nj;
         a.dyn = r.dyn; a.dyn_splits = 64;
         double kvb = 2.0 * (double)(nj + Sj) * nkv * d * e;
