@@ -1720,7 +1720,11 @@ extern "C" int mmd_sampler_create(mmd_ctx* c, mmd_sampler** out) {
     if (!sp) FAIL(c, MMD_ENOMEM, "out of host memory");
     sp->ctx = c; sp->lane = c->n_samplers++;
     if (hipMalloc((void**)&sp->tok_dev, 64) != hipSuccess) { delete sp; FAIL(c, MMD_ENOMEM, "hipMalloc of a sampler failed"); }
-    hipMemsetAsync(sp->tok_dev, 0, 64, c->stream);
+    // the slot is zeroed before the call returns: c->stream is whatever stream the context was last bound to -- possibly the tower's side stream with batches queued on
+    // it -- while the rounds that write and read the slot run on the caller's stream; a fill still pending there would wipe a drawn token before the next round feeds it
+    hipError_t e = hipMemsetAsync(sp->tok_dev, 0, 64, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { hipFree(sp->tok_dev); delete sp; FAIL(c, MMD_EHIP, "zeroing a sampler failed: %s", hipGetErrorString(e)); }
     *out = sp;
     return MMD_OK;
 }

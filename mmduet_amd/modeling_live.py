@@ -42,6 +42,7 @@ class _KVArena:
     def __init__(self, model, initial_tokens):
         self.model = model
         self.handles = weakref.WeakSet()
+        model._bind_stream()          # a new arena's zero-fill is stream-ordered: on the caller's stream, where the steps that write the arena follow (not on the tower's side stream, if that was bound last)
         pool = model.__dict__.setdefault('_arena_pool', [])
         for i, h in enumerate(pool):
             if lib().mmd_kv_capacity(h) >= int(initial_tokens):
@@ -196,6 +197,7 @@ class SamplerHandle:
         self.model = model
         h = C.c_void_p()
         with model._lock:
+            model._bind_stream()          # (the sampler's slot is zeroed on the bound stream: the caller's, not the tower's side stream if that was bound last)
             check(lib().mmd_sampler_create(model._ctx, C.byref(h)), model._ctx, 'mmd_sampler_create')
         self.h = h.value
 

@@ -50,6 +50,33 @@ def hip_model(tag, dtype=torch.float32, weights=None, **cfg_over):
     return m, cfgd, w
 
 
+def _build(llm_layers, vit_layers, dtype, vocab=2048, max_vit_batch=35, max_step_tokens=1536, seed=3, tower_dtype=None, weight_dtype=None):
+    """True-width model (7B decoder widths, so400m tower widths) with a few layers: (HIP model, oracle weights dict on the device in `dtype`-rounded fp32, oracle config)."""
+    from oracle import duet_oracle as O
+    from mmduet_amd.configuration_live import VideoHeadLiveLlavaQwenConfig
+    from mmduet_amd.modeling_live import VideoHeadLiveLlavaQwenForCausalLM
+    from mmduet_amd.weights import synthetic_weights
+    pcfg = VideoHeadLiveLlavaQwenConfig(vocab_size=vocab, num_hidden_layers=llm_layers, vit_num_hidden_layers=vit_layers + 1, vit_layers_removed=1,
+                                        frame_num_tokens=49, frame_resolution=384, v_placeholder='<image>')
+    ocfg = O.OracleConfig(vocab_size=vocab, num_hidden_layers=llm_layers, vit_layers=vit_layers)
+    if tower_dtype:
+        pcfg.tower_dtype = tower_dtype
+    if weight_dtype:
+        pcfg.weight_dtype = weight_dtype
+    m = VideoHeadLiveLlavaQwenForCausalLM(pcfg, torch_dtype=dtype, max_vit_batch=max_vit_batch, max_step_tokens=max_step_tokens, kv_initial_tokens=4096)
+    w = {}
+    for name, t in synthetic_weights(pcfg, seed=seed, device=m.device, dtype=dtype, scale='unit'):
+        m.load_tensor(name, t)
+        w[name] = t
+    m.finalize()
+    return m, w, ocfg
+
+
+def _oracle(w, ocfg, dtype):
+    from oracle import duet_oracle as O
+    return O.OracleModel(ocfg, {k: v.to(dtype) for k, v in w.items()})
+
+
 def stream_cases():
     return json.load(open(os.path.join(GOLDEN, 'cfgA_streams.json')))
 

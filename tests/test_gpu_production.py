@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 from oracle import duet_oracle as O
 from conftest import ROOT
 from parity_common import rel_err as _rel_err, ref_attention as _ref_attention_gpu, ref_attention_rows as _ref_attention_rows
+from helpers import _build, _oracle          # the true-width builders, shared with tests/test_gpu_tower_beside_llm.py
 
 RESULTS = {}
 
@@ -487,31 +488,6 @@ def test_attention_over_a_million_keys(ops, S, variant, form):
 
 
 # ---- true-width models ---------------------------------------------------------------------------------------------------------------
-def _build(llm_layers, vit_layers, dtype, vocab=2048, max_vit_batch=35, max_step_tokens=1536, seed=3, tower_dtype=None, weight_dtype=None):
-    """(HIP model, oracle weights dict on the device in `dtype`-rounded fp32, oracle config)."""
-    from mmduet_amd.configuration_live import VideoHeadLiveLlavaQwenConfig
-    from mmduet_amd.modeling_live import VideoHeadLiveLlavaQwenForCausalLM
-    from mmduet_amd.weights import synthetic_weights
-    pcfg = VideoHeadLiveLlavaQwenConfig(vocab_size=vocab, num_hidden_layers=llm_layers, vit_num_hidden_layers=vit_layers + 1, vit_layers_removed=1,
-                                        frame_num_tokens=49, frame_resolution=384, v_placeholder='<image>')
-    ocfg = O.OracleConfig(vocab_size=vocab, num_hidden_layers=llm_layers, vit_layers=vit_layers)
-    if tower_dtype:
-        pcfg.tower_dtype = tower_dtype
-    if weight_dtype:
-        pcfg.weight_dtype = weight_dtype
-    m = VideoHeadLiveLlavaQwenForCausalLM(pcfg, torch_dtype=dtype, max_vit_batch=max_vit_batch, max_step_tokens=max_step_tokens, kv_initial_tokens=4096)
-    w = {}
-    for name, t in synthetic_weights(pcfg, seed=seed, device=m.device, dtype=dtype, scale='unit'):
-        m.load_tensor(name, t)
-        w[name] = t
-    m.finalize()
-    return m, w, ocfg
-
-
-def _oracle(w, ocfg, dtype):
-    return O.OracleModel(ocfg, {k: v.to(dtype) for k, v in w.items()})
-
-
 @pytest.fixture(scope='module')
 def width2():
     """true widths, 2 tower layers + 2 decoder layers, bf16"""
@@ -574,7 +550,7 @@ def test_vit_ring_attention_equals_register_staged_kernel():
     code = r'''
 import os, sys, json, hashlib, torch
 sys.path.insert(0, os.environ["MMD_ROOT"]); sys.path.insert(0, os.path.join(os.environ["MMD_ROOT"], "tests"))
-from test_gpu_production import _build
+from helpers import _build
 res = {}
 for tower in ("fp16", "bf16"):
     m, w, ocfg = _build(1, 2, torch.bfloat16, max_vit_batch=35, max_step_tokens=64, tower_dtype=tower)

@@ -4,7 +4,7 @@ next call); which result does every fa call return?   tower_graph_probe.py [B] [
 import sys, os
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
 import torch
-from test_gpu_production import _build
+from helpers import _build
 m, w, o = _build(2, 2, torch.bfloat16)
 g = torch.Generator(device=m.device).manual_seed(21)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 35

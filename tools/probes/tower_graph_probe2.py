@@ -3,7 +3,7 @@
 import sys, os
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
 import torch
-from test_gpu_production import _build
+from helpers import _build
 sync = len(sys.argv) > 1 and sys.argv[1] == 'sync'
 pre = len(sys.argv) > 2
 m, w, o = _build(2, 2, torch.bfloat16)
