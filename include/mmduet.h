@@ -167,6 +167,13 @@ int mmd_kv_unstash(mmd_stream* s);
  * mapped; slots at or above the new length are unspecified.  from == to enqueues nothing, to == length is a truncate that keeps the position.
  * MMD_ERANGE unless 0 <= from <= to <= length, MMD_EINVAL while a stash is held.  mmd_kv_truncate leaves the position offset alone, mmd_stream_reset zeroes it. */
 int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to);
+/* The same with SHIFTED positions (DESIGN.md section 5 "Shifted positions"): positions are counted inside the arena.  V and the bookkeeping of the length are those of
+ * mmd_kv_drop; the keys of tokens [to, len) arrive in [from, len - (to - from)) turned back by to - from positions -- dims (e, e + head_dim/2) by the angle
+ * (float)(to - from) * inv_freq[e], cos / sin in fp32 and not rounded to the context dtype, fp32 products and sums, one rounding to the context dtype -- so that slot t holds
+ * the key of position t + offset again: mmd_kv_len and mmd_kv_position BOTH shrink by to - from, the offset earlier plain drops left stays.  Keys in [0, from) are not
+ * written.  One launch, no host synchronisation.  Refusals as mmd_kv_drop, and MMD_EINVAL (with a message) unless the context is bf16 or fp32 with an even head_dim whose
+ * half is a multiple of 16 bytes.  A refused call changes nothing. */
+int mmd_kv_drop_shift(mmd_stream* s, int64_t from, int64_t to);
 int64_t mmd_kv_position(const mmd_stream* s);             /* RoPE position of the next token written: mmd_kv_len + tokens dropped (-1: null stream) */
 int mmd_stream_reset(mmd_stream* s);                      /* LiveInferForBenchmark.reset (test/inference.py:169-183: past_key_values = None): length 0, position 0, arena kept */
 /* Snapshots: take a stream's context out of its arena, put one in, hold one twice (no reference counterpart: the reference's DynamicCache is a list of torch tensors that

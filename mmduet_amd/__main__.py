@@ -24,13 +24,8 @@ import numpy as np
 import torch
 
 
-def main(argv=None):
-    from .arguments_live import parse_args
-    from .inference import LiveInferForBenchmark
-    from .results import result_record
-    from .distributed import init_distributed, shard_indices, shard_shape, gather_scores, gather_responses
-    from .prefetch import ClipPrefetcher, pin
-    args = parse_args('test', argv)
+def cli_extra_args(argv):
+    """The flags of this CLI alone, parsed out of `argv` (everything else is left to the arguments dataclass) -> Namespace"""
     # sampled responses: flags of this CLI alone (the arguments dataclass keeps the reference's schema and skips what it does not know); the drivers read them off `args`
     import argparse
     sp = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
@@ -47,7 +42,21 @@ def main(argv=None):
     # sliding context window (DESIGN.md "Context window"): at most N tokens of context (0 = off), the first M kept for good (default: what the stream's first forward encoded)
     sp.add_argument('--context_window', type=int, default=0)
     sp.add_argument('--context_sink', type=int, default=None)
-    for k, v in vars(sp.parse_known_args(sys.argv[1:] if argv is None else argv)[0]).items():
+    # ... positions counted on ('kept', the default) or inside the window ('shifted': every drop turns the retained keys back, DESIGN.md "Shifted positions"); drops rounded
+    # up to a multiple of N tokens (0 = off)
+    sp.add_argument('--context_positions', choices=('kept', 'shifted'), default='kept')
+    sp.add_argument('--context_drop_quantum', type=int, default=0)
+    return sp.parse_known_args(argv)[0]
+
+
+def main(argv=None):
+    from .arguments_live import parse_args
+    from .inference import LiveInferForBenchmark
+    from .results import result_record
+    from .distributed import init_distributed, shard_indices, shard_shape, gather_scores, gather_responses
+    from .prefetch import ClipPrefetcher, pin
+    args = parse_args('test', argv)
+    for k, v in vars(cli_extra_args(sys.argv[1:] if argv is None else argv)).items():
         setattr(args, k, v)
     args.output_logprobs, args.top_logprobs = args.logprobs is not None, args.logprobs or 0
     rank, world, local = init_distributed()

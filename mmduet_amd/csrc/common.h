@@ -133,6 +133,8 @@ hipError_t launch_rope_append(int dtype, const void* qkv, int S, int nh, int nkv
                               void* Kc, void* Vc, int64_t cap, int v_transposed, hipStream_t st, int64_t pos_off = 0);          // slot pos0 + s, RoPE position pos0 + pos_off + s
 // mmd_kv_drop: in every one of `rows` (layer, kv head) rows of `pitch_bytes`, tokens [to, len) of K (rows of tok_bytes) and of V (transposed 64-token blocks) move down to [from, ...)
 hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, hipStream_t st);
+// mmd_kv_drop_shift: the same move, the keys that arrive in [from, len - (to - from)) turned back by to - from positions (pairs (e, e + d/2), angle (float)(to - from) * inv_freq[e])
+hipError_t launch_kv_drop_shift(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, const float* inv_freq_dev, hipStream_t st);
 // mmd_kv_export / mmd_kv_import: tokens [t0, t0 + n) of every one of `rows` arena rows (K rows of tokens, V in transposed 64-token blocks) <-> the canonical form
 // K_canon, V_canon [rows][n][d], token-major for both.  scatter = 0: arena -> canonical; 1: canonical -> arena slots [t0, t0 + n), no other slot's bytes written.
 // All four pointers 16-byte aligned, d * element size a multiple of 16 and at most 1 KiB.

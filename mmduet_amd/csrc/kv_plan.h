@@ -1,7 +1,7 @@
 // kv_plan.h -- the stream KV arena's geometry, its span operations and its growth, and nothing else.  Pure host functions: no GPU header, no runtime call, no environment;
 // they compile with the host C++17 compiler alone (tests/test_kv_plan_host.py runs the table of tests/kv_plan_cases.py through them without a GPU).
 //   KvGeom       the only place the token <-> byte conversions and the V block size are written
-//   kv_plan()    one operation on a stream's arena: refused (code and message), nothing to do, or what must have memory behind it, what is launched over which spans and the
+//   kv_plan()    one operation on a stream's arena (KV_DROP in two forms: flags): refused (code and message), nothing to do, or what must have memory behind it, what is launched over which spans and the
 //                bookkeeping the stream has afterwards.  kv_run (model.hip) does what it says, in that order.
 //   kv_vmm_*, kv_grow_*   the capacities growth tries: the chunk of the virtual-memory arena, the virtual reservations of mmd_stream_create, the fallback arena's reallocation
 #pragma once
@@ -50,7 +50,9 @@ enum { KV_LAUNCH_NONE = 0,
        KV_ROWS_IN,                     // ... into it
        KV_LAUNCH_DROP,                 // launch_kv_drop(t0, t1, len)
        KV_CANON_GATHER,                // launch_kv_canon: tokens [t0, t0 + t1) out of the arena into the canonical form ...
-       KV_CANON_SCATTER };             // ... out of the canonical form into the arena
+       KV_CANON_SCATTER,               // ... out of the canonical form into the arena
+       KV_LAUNCH_DROP_SHIFT };         // launch_kv_drop_shift(t0, t1, len): KV_DROP with KV_F_SHIFT
+enum { KV_F_SHIFT = 1 };               // kv_plan's flags.  KV_F_SHIFT (KV_DROP only): the keys behind the span are turned back by the span's length and the position shrinks with the length
 constexpr int64_t KV_COPY_MAX_COLS = 0x7fffffff;          // launch_copy_rows takes a row's width as an int of 4-byte units
 struct KvPlan {
     int rc = MMD_OK; char error[256] = {0};          // rc != MMD_OK: refused with this message
@@ -63,8 +65,8 @@ struct KvPlan {
     // and v_other4.  Widths (k_cols, v_cols) and pitches are in the 4-byte units launch_copy_rows takes.
     size_t k_off = 0, k_bytes = 0, v_off = 0, v_bytes = 0;
     int64_t k_cols = 0, v_cols = 0, pitch4 = 0, k_other4 = 0, v_other4 = 0; int copy_rows = 0;
-    int64_t t0 = 0, t1 = 0;            // KV_LAUNCH_DROP: from, to.  KV_CANON_*: the first slot, the token count
-    int64_t pitch_bytes = 0;           // KV_LAUNCH_DROP, KV_CANON_*: the arena's row pitch
+    int64_t t0 = 0, t1 = 0;            // KV_LAUNCH_DROP, KV_LAUNCH_DROP_SHIFT: from, to.  KV_CANON_*: the first slot, the token count
+    int64_t pitch_bytes = 0;           // KV_LAUNCH_DROP, KV_LAUNCH_DROP_SHIFT, KV_CANON_*: the arena's row pitch
     KvState after;                     // the stream's bookkeeping once the launches are queued (cap and mapped are kv_reserve's to change)
 };
 #define KV_REFUSE(code, ...) do { p.rc = (code); snprintf(p.error, sizeof(p.error), __VA_ARGS__); return p; } while (0)
@@ -86,7 +88,8 @@ static inline bool kv_plan_rows(KvPlan& p, const char* what, const KvGeom& g, in
     return false;
 }
 // s: the stream's state (KV_FORK: the destination's, src the source's).  The checks of each operation stand in the order its entry point always made them.
-static inline KvPlan kv_plan(int op, const KvGeom& g, const KvState& s, int64_t a = 0, int64_t b = 0, const KvState* src = nullptr, int bufs = KV_BUF_OK) {
+static inline KvPlan kv_plan(int op, const KvGeom& g, const KvState& s, int64_t a = 0, int64_t b = 0, const KvState* src = nullptr, int bufs = KV_BUF_OK,
+                             int flags = 0) {
     KvPlan p; p.after = s;
     const long long la = (long long)a, lb = (long long)b, len = (long long)s.len, sf = (long long)s.stash_from, st = (long long)s.stash_to;
     const bool outside = a < 0 || b < a || b > s.len, stashed = s.stash_from >= 0;          // a span [a, b) outside the context; a stash is held
@@ -127,9 +130,15 @@ static inline KvPlan kv_plan(int op, const KvGeom& g, const KvState& s, int64_t 
     case KV_DROP:
         if (outside) KV_REFUSE(MMD_ERANGE, "kv_drop [%lld, %lld) outside the context (%lld tokens)", la, lb, len);
         if (stashed) KV_REFUSE(MMD_EINVAL, "kv_drop while tokens [%lld, %lld) are stashed (unstash or drop the stash first)", sf, st);
+        // KV_F_SHIFT (mmd_kv_drop_shift): the keys that move down are turned back by to - from positions on the way (launch_kv_drop_shift), so slot t holds position
+        // t + pos_off again: the offset stays and the position shrinks with the length.  The rotation pairs dims (e, e + d/2) and moves 16-byte groups of both halves.
+        if ((flags & KV_F_SHIFT) && (g.head_dim % 2 != 0 || (g.elem_bytes != 2 && g.elem_bytes != 4) || ((size_t)(g.head_dim / 2) * g.elem_bytes) % 16 != 0 || g.rows() > 65535))
+            KV_REFUSE(MMD_EINVAL, "kv_drop_shift: head_dim %d x %d bytes (2- or 4-byte elements, half a head a multiple of 16 bytes) or %d x %d rows not supported", g.head_dim, g.elem_bytes,
+                      g.layers, g.kv_heads);
         if (a == b) { p.nothing = true; break; }
-        if (b < s.len) { p.launch = KV_LAUNCH_DROP; p.t0 = a; p.t1 = b; p.pitch_bytes = (int64_t)g.pitch_bytes(s.cap); }          // (a dropped tail moves nothing)
-        p.after.len = s.len - (b - a); p.after.pos_off = s.pos_off + (b - a);
+        if (b < s.len) { p.launch = (flags & KV_F_SHIFT) ? KV_LAUNCH_DROP_SHIFT : KV_LAUNCH_DROP; p.t0 = a; p.t1 = b; p.pitch_bytes = (int64_t)g.pitch_bytes(s.cap); }          // (a dropped tail moves nothing)
+        p.after.len = s.len - (b - a);
+        if (!(flags & KV_F_SHIFT)) p.after.pos_off = s.pos_off + (b - a);
         break;
     // Snapshots.  The canonical form K, V [layers][kv heads][n][d] is token-major for both and has the context's dtype: nothing in it depends on the arena's capacity, pitch
     // or V blocking.  launch_kv_canon converts; a fork stays in arena form (the stash's strided copy between two pitches).

@@ -1195,13 +1195,14 @@ static int kv_copy_pair(mmd_ctx* c, const KvPlan& p, char* K, char* V, void* Ko,
 }
 // One operation on s's arena as kv_plan states it: refused, or -- in this order -- memory behind the tokens it needs, the stash buffers, the launches, the bookkeeping.
 // Ko / Vo: the side of the launches that is not s's arena -- the caller's buffers, a fork's source arena, nullptr for the stash buffers
-static int kv_run(mmd_stream* s, int op, int64_t a = 0, int64_t b = 0, const mmd_stream* src = nullptr, const void* Ko = nullptr, const void* Vo = nullptr) {
+static int kv_run(mmd_stream* s, int op, int64_t a = 0, int64_t b = 0, const mmd_stream* src = nullptr, const void* Ko = nullptr, const void* Vo = nullptr, int flags = 0) {
     mmd_ctx* c = s->ctx; const KvGeom g = kv_geom(c);
     KvState from; if (src) from = kv_state(src);
-    auto plan = [&]() { return kv_plan(op, g, kv_state(s), a, b, src ? &from : nullptr, kv_bufs(Ko, Vo)); };
+    auto plan = [&]() { return kv_plan(op, g, kv_state(s), a, b, src ? &from : nullptr, kv_bufs(Ko, Vo), flags); };
     KvPlan p = plan();
     if (p.rc != MMD_OK) FAIL(c, p.rc, "%s", p.error);
     if (p.nothing) return MMD_OK;
+    if (p.launch == KV_LAUNCH_DROP_SHIFT && !c->inv_freq) FAIL(c, MMD_EINVAL, "kv_drop_shift: the context has no RoPE frequency table");
     if (p.reserve || p.stash_bytes || p.launch != KV_LAUNCH_NONE) hipSetDevice(c->device);
     if (p.reserve) {
         int rc = kv_reserve(c, s, p.reserve); if (rc) return rc;
@@ -1217,6 +1218,7 @@ static int kv_run(mmd_stream* s, int op, int64_t a = 0, int64_t b = 0, const mmd
     switch (p.launch) {
     case KV_ROWS_OUT: case KV_ROWS_IN: { int rc = kv_copy_pair(c, p, (char*)s->K, (char*)s->V, (void*)Ko, (void*)Vo); if (rc) return rc; break; }
     case KV_LAUNCH_DROP: HIPCHK(c, launch_kv_drop(c->cfg.dtype, s->K, s->V, rows, p.pitch_bytes, g.head_dim, p.t0, p.t1, s->len, c->stream)); break;
+    case KV_LAUNCH_DROP_SHIFT: HIPCHK(c, launch_kv_drop_shift(c->cfg.dtype, s->K, s->V, rows, p.pitch_bytes, g.head_dim, p.t0, p.t1, s->len, c->inv_freq, c->stream)); break;
     case KV_CANON_GATHER: case KV_CANON_SCATTER:
         HIPCHK(c, launch_kv_canon(c->cfg.dtype, p.launch == KV_CANON_SCATTER ? 1 : 0, s->K, s->V, rows, p.pitch_bytes, g.head_dim, p.t0, p.t1, (void*)Ko, (void*)Vo, c->stream)); break;
     default: break;
@@ -1234,6 +1236,7 @@ extern "C" int mmd_stream_reset(mmd_stream* s) { return s ? kv_run(s, KV_RESET) 
 extern "C" int mmd_kv_stash(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_STASH, from, to) : MMD_EINVAL; }
 extern "C" int mmd_kv_unstash(mmd_stream* s) { return s ? kv_run(s, KV_UNSTASH) : MMD_EINVAL; }
 extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_DROP, from, to) : MMD_EINVAL; }
+extern "C" int mmd_kv_drop_shift(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_DROP, from, to, nullptr, nullptr, nullptr, KV_F_SHIFT) : MMD_EINVAL; }
 // snapshots (DESIGN.md section 5 "Snapshots")
 extern "C" int mmd_kv_export(mmd_stream* s, int64_t from, int64_t to, void* K_out, void* V_out) { return s ? kv_run(s, KV_EXPORT, from, to, nullptr, K_out, V_out) : MMD_EINVAL; }
 extern "C" int mmd_kv_import(mmd_stream* s, const void* K_in, const void* V_in, int64_t n) { return s ? kv_run(s, KV_IMPORT, n, 0, nullptr, K_in, V_in) : MMD_EINVAL; }

@@ -1011,36 +1011,15 @@ static __device__ __forceinline__ u32x4_t kvd_funnel(const u32x4_t a, const u32x
     }
     return o;
 }
+// the V half of the walk, shared by kv_drop_kernel and kv_drop_shift_kernel: block `vblk` of the V blocks owns dims [vblk * ep, ...) of row blockIdx.y
 template <int ES>          // ES: bytes per element (2 or 4)
-__global__ __launch_bounds__(KVD_THREADS) void kv_drop_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, long long from, long long to, long long len,
-                                                              int kseg, int ku, int ep, int nb) {
+static __device__ __forceinline__ void kvd_walk_v(char* __restrict__ Vb, long long pitch, int d, long long from, long long to, long long len, int vblk, int ep, int nb) {
     constexpr int VEC = 16 / ES, CPL = 64 / VEC;          // tokens per 16-byte group of a V line, groups per line
     const int tid = threadIdx.x;
-    const long long n = len - to, delta = to - from;
-    u32x4_t ra[KVD_U];
-    if ((int)blockIdx.x < kseg) {
-        const long long tokb = (long long)d * ES;
-        char* row = Kb + (long long)blockIdx.y * pitch + (long long)blockIdx.x * ku * 16;
-        const long long tile = (long long)(KVD_THREADS * KVD_U) / ku;          // tokens per tile
-        for (long long t0 = 0; t0 < n; t0 += tile) {
-            long long off[KVD_U]; bool ok[KVD_U];
-#pragma unroll
-            for (int u = 0; u < KVD_U; ++u) {
-                const int idx = u * KVD_THREADS + tid;
-                const long long t = t0 + idx / ku;
-                ok[u] = idx / ku < tile && t < n;
-                off[u] = t * tokb + (idx % ku) * 16;
-                if (ok[u]) ra[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u]);
-            }
-            __syncthreads();
-#pragma unroll
-            for (int u = 0; u < KVD_U; ++u) if (ok[u]) *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u]) = ra[u];
-        }
-        return;
-    }
-    u32x4_t rb[KVD_U];
+    const long long delta = to - from;
+    u32x4_t ra[KVD_U], rb[KVD_U];
     char* row = Vb + (long long)blockIdx.y * pitch;
-    const int e0 = ((int)blockIdx.x - kseg) * ep;
+    const int e0 = vblk * ep;
     const int sh = (int)(delta % VEC) * ES;          // the source group's byte offset inside its aligned 16 bytes
     const long long newlen = len - delta;
     const int per_blk = ep * CPL;
@@ -1080,20 +1059,148 @@ __global__ __launch_bounds__(KVD_THREADS) void kv_drop_kernel(char* __restrict__
         }
     }
 }
+template <int ES>
+__global__ __launch_bounds__(KVD_THREADS) void kv_drop_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, long long from, long long to, long long len,
+                                                              int kseg, int ku, int ep, int nb) {
+    const int tid = threadIdx.x;
+    const long long n = len - to;
+    if ((int)blockIdx.x < kseg) {
+        u32x4_t ra[KVD_U];
+        const long long tokb = (long long)d * ES;
+        char* row = Kb + (long long)blockIdx.y * pitch + (long long)blockIdx.x * ku * 16;
+        const long long tile = (long long)(KVD_THREADS * KVD_U) / ku;          // tokens per tile
+        for (long long t0 = 0; t0 < n; t0 += tile) {
+            long long off[KVD_U]; bool ok[KVD_U];
+#pragma unroll
+            for (int u = 0; u < KVD_U; ++u) {
+                const int idx = u * KVD_THREADS + tid;
+                const long long t = t0 + idx / ku;
+                ok[u] = idx / ku < tile && t < n;
+                off[u] = t * tokb + (idx % ku) * 16;
+                if (ok[u]) ra[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u]);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < KVD_U; ++u) if (ok[u]) *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u]) = ra[u];
+        }
+        return;
+    }
+    kvd_walk_v<ES>(Vb, pitch, d, from, to, len, (int)blockIdx.x - kseg, ep, nb);
+}
+// how the V blocks of a launch split the d dims: esplit blocks of ep dims each, nb destination 64-token blocks per tile -> false where the head shape does not fit a tile
+static bool kvd_v_split(int d, int cpl, int* esplit_out, int* ep_out, int* nb_out) {
+    int esplit = d % 4 == 0 ? 4 : 1;
+    while (d % esplit == 0 && (d / esplit) * cpl > KVD_THREADS * KVD_U && esplit < d) esplit *= 2;
+    const int ep = d / esplit;
+    if (d % esplit != 0 || ep * cpl > KVD_THREADS * KVD_U) return false;
+    *esplit_out = esplit; *ep_out = ep; *nb_out = KVD_THREADS * KVD_U / (ep * cpl);
+    return true;
+}
 hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, hipStream_t st) {
     if (from < 0 || to < from || len < to) return hipErrorInvalidValue;
     if (from == to || to == len || rows <= 0) return hipSuccess;
     const int es = (int)dtype_size(dtype), units = d * es / 16, vec = 16 / es, cpl = 64 / vec;
     if ((d * es) % 16 != 0 || (pitch_bytes % 16) != 0 || rows > 65535) return hipErrorInvalidValue;
     const int ku = units % 8 == 0 ? 8 : units;                                  // 128-byte pieces of a K row where it divides
-    int esplit = d % 4 == 0 ? 4 : 1;
-    while (d % esplit == 0 && (d / esplit) * cpl > KVD_THREADS * KVD_U && esplit < d) esplit *= 2;
-    const int ep = d / esplit;
-    if (d % esplit != 0 || ep * cpl > KVD_THREADS * KVD_U || ku > KVD_THREADS * KVD_U) return hipErrorInvalidValue;
-    const int kseg = units / ku, nb = KVD_THREADS * KVD_U / (ep * cpl);
+    int esplit, ep, nb;
+    if (!kvd_v_split(d, cpl, &esplit, &ep, &nb) || ku > KVD_THREADS * KVD_U) return hipErrorInvalidValue;
+    const int kseg = units / ku;
     const dim3 grid(kseg + esplit, rows), block(KVD_THREADS);
     if (es == 4) hipLaunchKernelGGL(kv_drop_kernel<4>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, kseg, ku, ep, nb);
     else hipLaunchKernelGGL(kv_drop_kernel<2>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, kseg, ku, ep, nb);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mmd_kv_drop_shift: mmd_kv_drop whose surviving keys are turned back by delta = to - from positions, so that slot t of the arena holds the key of RoPE position
+// t + pos_off again and the stream's position shrinks with its length.  V is kvd_walk_v, byte for byte what kv_drop_kernel does.  K slots [0, from) are not written.
+//   Pairing: rope_append_kernel rotates (e, e + d/2) with frequency e.  With a = (float)delta * inv_freq[e] (one fp32 product), c = cosf(a), s = sinf(a) -- NOT rounded
+//   to the storage type: the writers' rounded table mirrors the reference's bf16 cos / sin, this step has no counterpart there -- the key becomes
+//   x1' = x1 c + x2 s, x2' = x2 c - x1 s: fp32 products and sums, one rounding to the storage type.
+//   Ownership: kv_drop_kernel's 128-byte column pieces would separate e from e + d/2, so a block owns KP 16-byte groups of the lower half of the token row TOGETHER
+//   with the KP groups d/2 elements above them, every token of them; a thread holds both groups of a pair.  The rest is the owner walk above: one owner per byte
+//   column, a tile's loads before the barrier, its stores behind it, tiles in ascending token order.  The block's KP * VEC (c, s) pairs are evaluated once, into LDS.
+// grid (KSEG + ESPLIT, rows): blocks x < KSEG own K groups [x * KP, ...) and [units / 2 + x * KP, ...), the others V dims as in kv_drop_kernel.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int KVS_KP = 4, KVS_U = KVD_U / 2;          // at most 4 pairs of groups per block (2 x 64 bytes of a token row); a thread holds KVS_U pairs = KVD_U groups
+template <int ES>
+__global__ __launch_bounds__(KVD_THREADS) void kv_drop_shift_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, long long from, long long to, long long len,
+                                                                    const float* __restrict__ inv_freq_tab, int kseg, int kp, int ep, int nb) {
+    constexpr int VEC = 16 / ES;
+    if ((int)blockIdx.x >= kseg) { kvd_walk_v<ES>(Vb, pitch, d, from, to, len, (int)blockIdx.x - kseg, ep, nb); return; }
+    __shared__ float2 cs[KVS_KP * 8];
+    const int tid = threadIdx.x;
+    const long long n = len - to, delta = to - from;
+    const long long tokb = (long long)d * ES, halfb = tokb / 2;
+    const int g0 = (int)blockIdx.x * kp;          // the block's first group of the lower half
+    if (tid < kp * VEC) {
+        const float ang = (float)delta * inv_freq_tab[g0 * VEC + tid];
+        cs[tid] = make_float2(cosf(ang), sinf(ang));
+    }
+    __syncthreads();
+    char* row = Kb + (long long)blockIdx.y * pitch + (long long)g0 * 16;
+    const long long tile = (long long)(KVD_THREADS * KVS_U) / kp;          // tokens per tile
+    for (long long t0 = 0; t0 < n; t0 += tile) {
+        u32x4_t lo[KVS_U], hi[KVS_U]; long long off[KVS_U]; int pi[KVS_U]; bool ok[KVS_U];
+#pragma unroll
+        for (int u = 0; u < KVS_U; ++u) {
+            const int idx = u * KVD_THREADS + tid;
+            const long long t = t0 + idx / kp;
+            ok[u] = idx / kp < tile && t < n;
+            pi[u] = idx % kp;
+            off[u] = t * tokb + pi[u] * 16;
+            if (ok[u]) {
+                lo[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u]);
+                hi[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u] + halfb);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KVS_U; ++u) {
+            if (!ok[u]) continue;
+            u32x4_t o1, o2;
+            if constexpr (ES == 4) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float2 r = cs[pi[u] * VEC + k];
+                    const float x1 = __uint_as_float(lo[u][k]), x2 = __uint_as_float(hi[u][k]);
+                    o1[k] = __float_as_uint(x1 * r.x + x2 * r.y);
+                    o2[k] = __float_as_uint(x2 * r.x - x1 * r.y);
+                }
+            } else {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    unsigned p1 = 0, p2 = 0;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const float2 r = cs[pi[u] * VEC + w * 2 + h];
+                        const float x1 = bf2f((bf16_t)(lo[u][w] >> (16 * h))), x2 = bf2f((bf16_t)(hi[u][w] >> (16 * h)));
+                        p1 |= (unsigned)f2bf(x1 * r.x + x2 * r.y) << (16 * h);
+                        p2 |= (unsigned)f2bf(x2 * r.x - x1 * r.y) << (16 * h);
+                    }
+                    o1[w] = p1; o2[w] = p2;
+                }
+            }
+            *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u]) = o1;
+            *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u] + halfb) = o2;
+        }
+    }
+}
+// bf16 and fp32 arenas whose half token row is whole 16-byte groups; anything else: hipErrorInvalidValue, nothing launched
+hipError_t launch_kv_drop_shift(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, const float* inv_freq_dev, hipStream_t st) {
+    if (from < 0 || to < from || len < to) return hipErrorInvalidValue;
+    if (dtype != MMD_BF16 && dtype != MMD_F32) return hipErrorInvalidValue;
+    const int es = (int)dtype_size(dtype), vec = 16 / es, cpl = 64 / vec;
+    if (d <= 0 || d % 2 != 0 || ((d / 2) * es) % 16 != 0 || (pitch_bytes % 16) != 0 || rows > 65535 || !inv_freq_dev) return hipErrorInvalidValue;
+    int esplit, ep, nb;
+    if (!kvd_v_split(d, cpl, &esplit, &ep, &nb)) return hipErrorInvalidValue;
+    if (from == to || to == len || rows <= 0) return hipSuccess;
+    const int hu = (d / 2) * es / 16;                                           // 16-byte groups in half a token row
+    const int kp = hu % KVS_KP == 0 ? KVS_KP : hu % 2 == 0 ? 2 : 1;
+    const int kseg = hu / kp;
+    const dim3 grid(kseg + esplit, rows), block(KVD_THREADS);
+    if (es == 4) hipLaunchKernelGGL(kv_drop_shift_kernel<4>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, inv_freq_dev, kseg, kp, ep, nb);
+    else hipLaunchKernelGGL(kv_drop_shift_kernel<2>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, inv_freq_dev, kseg, kp, ep, nb);
     return hipGetLastError();
 }
 

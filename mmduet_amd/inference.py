@@ -41,12 +41,16 @@ def _p1(l0, l1):
     return 1.0 / (1.0 + math.exp(d)) if d < 700.0 else 0.0
 
 
-def context_drop_amount(length, rows, window, sink):
+def context_drop_amount(length, rows, window, sink, quantum=0):
     """Sliding context window: tokens to drop from [sink, sink + m) before a forward of `rows` rows on a context of `length` tokens -- the smallest m with
-    length - m + rows <= window, at most length - sink (the sink stays); 0 with the window off (window <= 0) or wide enough."""
+    length - m + rows <= window, at most length - sink (the sink stays); 0 with the window off (window <= 0) or wide enough.  `quantum` > 0: a non-zero m is
+    rounded UP to a multiple of it (fewer, larger drops: with shifted positions every drop re-rounds the retained keys once), still at most length - sink."""
     if window <= 0 or length + rows <= window:
         return 0
-    return max(0, min(length + rows - window, length - sink))
+    m = max(0, min(length + rows - window, length - sink))
+    if quantum > 0 and m > 0:
+        m = max(0, min(-(-m // quantum) * quantum, length - sink))
+    return m
 
 
 class LiveInferForBenchmark:
@@ -118,6 +122,12 @@ class LiveInferForBenchmark:
         # encoded -- the system prompt and what came with it) and drop the oldest tokens behind them whenever a forward would take the context past `context_window`
         self.context_window = int(getattr(args, 'context_window', 0) or 0)
         self.context_sink = getattr(args, 'context_sink', None)
+        # 'kept' (default): retained keys keep their rotation and positions go on counting (mmd_kv_drop); 'shifted': positions are counted inside the window, every drop
+        # turns the retained keys back (mmd_kv_drop_shift; DESIGN.md "Shifted positions").  context_drop_quantum > 0 rounds every drop up to a multiple of it
+        self.context_positions = str(getattr(args, 'context_positions', None) or 'kept')
+        if self.context_positions not in ('kept', 'shifted'):
+            raise ValueError(f"context_positions must be 'kept' or 'shifted', not {self.context_positions!r}")
+        self.context_drop_quantum = int(getattr(args, 'context_drop_quantum', 0) or 0)
         self.frames_per_forward = max(1, int(getattr(args, 'frames_per_forward', 1)))
         self.overlap_vision = bool(getattr(args, 'overlap_vision', True))
         self.record_head_logits = False          # diagnostics (parity tests, bench.py's self-check): debug_data entries also carry the 4 raw head logits of the frame
@@ -322,9 +332,9 @@ class LiveInferForBenchmark:
         if sink is None:
             return
         n = len(self.past_key_values)
-        m = context_drop_amount(n, rows, self.context_window, min(sink, n))
+        m = context_drop_amount(n, rows, self.context_window, min(sink, n), self.context_drop_quantum)
         if m > 0:
-            self.past_key_values = self.model.kv_drop(self.past_key_values, min(sink, n), min(sink, n) + m)
+            self.past_key_values = self.model.kv_drop(self.past_key_values, min(sink, n), min(sink, n) + m, shift=self.context_positions == 'shifted')
             self.dropped_tokens += m
 
     def _note_first_forward(self):

@@ -671,10 +671,11 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             check(lib().mmd_kv_unstash(arena.h), self._ctx, 'mmd_kv_unstash')
         return KVCacheHandle(arena, end)
 
-    def kv_drop(self, handle: KVCacheHandle, start: int, end: int):
+    def kv_drop(self, handle: KVCacheHandle, start: int, end: int, shift: bool = False):
         """Sliding context window: tokens [start, end) leave `handle`'s context; the tokens behind them move down (device move, stream-ordered) and keep the
-        rotary positions they were written with, and whatever is appended next goes on counting from `kv_position`.  -> the handle of the shortened context;
-        every other handle that reached beyond `start` is stale."""
+        rotary positions they were written with, and whatever is appended next goes on counting from `kv_position`.  With `shift` (mmd_kv_drop_shift) the keys
+        behind the span are turned back by end - start positions instead, so positions are counted inside the arena and `kv_position` shrinks with the length.
+        -> the handle of the shortened context; every other handle that reached beyond `start` is stale."""
         if handle.stale:
             raise RuntimeError('stale KV handle')
         start, end = int(start), int(end)
@@ -686,14 +687,17 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         with self._lock:
             arena.truncate(handle.length)
             self._bind_stream()
-            check(lib().mmd_kv_drop(arena.h, start, end), self._ctx, 'mmd_kv_drop')
+            if shift:
+                check(lib().mmd_kv_drop_shift(arena.h, start, end), self._ctx, 'mmd_kv_drop_shift')
+            else:
+                check(lib().mmd_kv_drop(arena.h, start, end), self._ctx, 'mmd_kv_drop')
             for hd in list(arena.handles):
                 if hd.length > start:
                     hd.stale = True
         return KVCacheHandle(arena, handle.length - (end - start))
 
     def kv_position(self, handle: KVCacheHandle):
-        """The rotary position the next token appended to `handle` gets: its length plus everything `kv_drop` took out of its arena."""
+        """The rotary position the next token appended to `handle` gets: its length plus everything `kv_drop` took out of its arena without `shift`."""
         if handle is None or handle.arena is None:
             return 0
         with self._lock:

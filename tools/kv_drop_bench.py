@@ -1,6 +1,10 @@
 """Cost of one mmd_kv_drop at the 7B bf16 arena (28 layers, 4 kv heads, head_dim 128), beside hipMemcpyAsync device-to-device of the same byte count.
 
-    python tools/kv_drop_bench.py [--out FILE.json]
+    python tools/kv_drop_bench.py [--out FILE.json] [--shift] [--reps N]
+
+--shift: mmd_kv_drop_shift on the same span as well, the two calls alternating (in alternating order) on the same arena; the span of tests/test_gpu_kv_drop_trueshape.py
+is added to the shapes.  --reps N: N calls between the two events of a timed window (the length is declared again in front of each: host bookkeeping, no launch), the
+time reported per call.
 
 The arena is declared live with mmd_kv_debug_set_len (contents are whatever the pages hold: the move is the same traffic); no weights are loaded.  Bytes moved =
 tokens behind the span x 256 bytes x 112 (layer, kv head) rows x 2 (K and V), counted once (each is read once and written once)."""
@@ -14,6 +18,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
     ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--shift', action='store_true')
+    ap.add_argument('--reps', type=int, default=1)
     a = ap.parse_args()
     from mmduet_amd._lib import lib, check
     from mmduet_amd.configuration_live import VideoHeadLiveLlavaQwenConfig
@@ -29,34 +35,43 @@ def main():
     cache = m.new_cache(1024)
     h = cache.arena.h
     sink, out = 20, []
-    for behind in (15_000, 100_000):
-        for delta in (10, 1300):
-            n = sink + delta + behind
-            nbytes = behind * tok * rows * 2
-            src = torch.empty(nbytes, dtype=torch.uint8, device='cuda'); dst = torch.empty_like(src)
-            t_drop, t_copy = [], []
-            for it in range(a.iters + 1):
-                check(lib().mmd_kv_debug_set_len(h, n), m._ctx, 'set_len')
-                m._bind_stream()
-                st = torch.cuda.current_stream()
-                e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    calls = [('drop', lib().mmd_kv_drop)] + ([('drop_shift', lib().mmd_kv_drop_shift)] if a.shift else [])
+    shapes = ([(1980, 1000)] if a.shift else []) + [(behind, delta) for behind in (15_000, 100_000) for delta in (10, 1300)]
+    for behind, delta in shapes:
+        n = sink + delta + behind
+        nbytes = behind * tok * rows * 2
+        src = torch.empty(nbytes, dtype=torch.uint8, device='cuda'); dst = torch.empty_like(src)
+        t_drop, t_copy, t_shift = [], [], []
+        for it in range(a.iters + 1):
+            m._bind_stream()
+            st = torch.cuda.current_stream()
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            for name, call in (calls if it % 2 == 0 else calls[::-1]):
                 e[0].record(st)
-                check(lib().mmd_kv_drop(h, sink, sink + delta), m._ctx, 'mmd_kv_drop')
+                for _ in range(a.reps):
+                    check(lib().mmd_kv_debug_set_len(h, n), m._ctx, 'set_len')
+                    check(call(h, sink, sink + delta), m._ctx, name)
                 e[1].record(st)
-                e[2].record(st)
-                assert hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), nbytes, 3, st.cuda_stream) == 0
-                e[3].record(st)
                 st.synchronize()
-                assert int(lib().mmd_kv_len(h)) == n - delta
-                check(lib().mmd_stream_reset(h), m._ctx, 'reset')
-                if it:          # (the first round maps the pages)
-                    t_drop.append(e[0].elapsed_time(e[1])); t_copy.append(e[2].elapsed_time(e[3]))
-            del src, dst
-            md, mc = sorted(t_drop)[len(t_drop) // 2], sorted(t_copy)[len(t_copy) // 2]
-            rec = dict(tokens_behind=behind, delta=delta, bytes_moved=nbytes, drop_ms=md, drop_GBps=nbytes / md / 1e6, memcpy_ms=mc, memcpy_GBps=nbytes / mc / 1e6,
-                       ratio_drop_over_memcpy_time=md / mc, drop_ms_all=t_drop, memcpy_ms_all=t_copy)
-            print(json.dumps(rec), flush=True)
-            out.append(rec)
+                if it:
+                    (t_drop if name == 'drop' else t_shift).append(e[0].elapsed_time(e[1]) / a.reps)
+            e[2].record(st)
+            assert hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), nbytes, 3, st.cuda_stream) == 0
+            e[3].record(st)
+            st.synchronize()
+            assert int(lib().mmd_kv_len(h)) == n - delta
+            check(lib().mmd_stream_reset(h), m._ctx, 'reset')
+            if it:          # (the first round maps the pages)
+                t_copy.append(e[2].elapsed_time(e[3]))
+        del src, dst
+        md, mc = sorted(t_drop)[len(t_drop) // 2], sorted(t_copy)[len(t_copy) // 2]
+        rec = dict(tokens_behind=behind, delta=delta, bytes_moved=nbytes, drop_ms=md, drop_GBps=nbytes / md / 1e6, memcpy_ms=mc, memcpy_GBps=nbytes / mc / 1e6,
+                   ratio_drop_over_memcpy_time=md / mc, drop_ms_all=t_drop, memcpy_ms_all=t_copy, reps=a.reps)
+        if a.shift:
+            ms = sorted(t_shift)[len(t_shift) // 2]
+            rec.update(drop_shift_ms=ms, drop_shift_GBps=nbytes / ms / 1e6, ratio_shift_over_drop_time=ms / md, drop_shift_ms_all=t_shift)
+        print(json.dumps(rec), flush=True)
+        out.append(rec)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         json.dump(out, open(a.out, 'w'), indent=1)
