@@ -174,6 +174,13 @@ int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to);
  * written.  One launch, no host synchronisation.  Refusals as mmd_kv_drop, and MMD_EINVAL (with a message) unless the context is bf16 or fp32 with an even head_dim whose
  * half is a multiple of 16 bytes.  A refused call changes nothing. */
 int mmd_kv_drop_shift(mmd_stream* s, int64_t from, int64_t to);
+/* Many spans in one pass (DESIGN.md section 5 "Eviction"): the n spans spans_host[i] = (from_i, to_i), ascending and disjoint, leave every layer's arena; what stays moves
+ * down ONCE, bit for bit (shift == 0: the bookkeeping of mmd_kv_drop, the position stays) or with every retained key turned back ONCE by the tokens dropped in front of it
+ * (shift != 0: the arithmetic and the bookkeeping of mmd_kv_drop_shift, length and position shrink by the total).  Empty spans are ignored, touching spans are merged; up
+ * to 64 spans are one launch, more are one launch per 64.  The list is host memory and is read before the call returns; no host synchronisation.  MMD_ERANGE if a span
+ * is outside [0, length] or has to < from; MMD_EINVAL if the spans do not ascend or overlap, while a stash is held, for a null stream, n < 0 or a null list with n > 0, and
+ * (shift) for what mmd_kv_drop_shift refuses.  A refused call changes nothing. */
+int mmd_kv_drop_spans(mmd_stream* s, const int64_t* spans_host /* [n][2] */, int n, int shift);
 int64_t mmd_kv_position(const mmd_stream* s);             /* RoPE position of the next token written: mmd_kv_len + tokens dropped (-1: null stream) */
 int mmd_stream_reset(mmd_stream* s);                      /* LiveInferForBenchmark.reset (test/inference.py:169-183: past_key_values = None): length 0, position 0, arena kept */
 /* Snapshots: take a stream's context out of its arena, put one in, hold one twice (no reference counterpart: the reference's DynamicCache is a list of torch tensors that

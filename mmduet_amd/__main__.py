@@ -46,6 +46,8 @@ def cli_extra_args(argv):
     # up to a multiple of N tokens (0 = off)
     sp.add_argument('--context_positions', choices=('kept', 'shifted'), default='kept')
     sp.add_argument('--context_drop_quantum', type=int, default=0)
+    sp.add_argument('--context_evict', choices=('oldest', 'informative'), default='oldest')
+    sp.add_argument('--context_recent', type=int, default=None)
     return sp.parse_known_args(argv)[0]
 
 

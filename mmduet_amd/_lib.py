@@ -73,6 +73,7 @@ _SIGS = {
     'mmd_kv_unstash': (_I, [_VP]),
     'mmd_kv_drop': (_I, [_VP, _I64, _I64]),
     'mmd_kv_drop_shift': (_I, [_VP, _I64, _I64]),
+    'mmd_kv_drop_spans': (_I, [_VP, _VP, _I, _I]),
     'mmd_kv_position': (_I64, [_VP]),
     'mmd_kv_export': (_I, [_VP, _I64, _I64, _VP, _VP]),
     'mmd_kv_import': (_I, [_VP, _VP, _VP, _I64]),

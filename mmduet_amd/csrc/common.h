@@ -135,6 +135,10 @@ hipError_t launch_rope_append(int dtype, const void* qkv, int S, int nh, int nkv
 hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, hipStream_t st);
 // mmd_kv_drop_shift: the same move, the keys that arrive in [from, len - (to - from)) turned back by to - from positions (pairs (e, e + d/2), angle (float)(to - from) * inv_freq[e])
 hipError_t launch_kv_drop_shift(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, int64_t from, int64_t to, int64_t len, const float* inv_freq_dev, hipStream_t st);
+// mmd_kv_drop_spans: one owner walk over at most 64 retained segments segs[nseg][2] = (src, count) (HOST memory, passed on by value), segment i moving down to dst0 + the counts
+// in front of it; inv_freq_dev non-null: the keys of segment i turned back by src_i - dst_i positions.  len_end: the stream's length behind the launch
+hipError_t launch_kv_compact(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, const int64_t* segs, int nseg, int64_t dst0, int64_t len_end, const float* inv_freq_dev,
+                             hipStream_t st);
 // mmd_kv_export / mmd_kv_import: tokens [t0, t0 + n) of every one of `rows` arena rows (K rows of tokens, V in transposed 64-token blocks) <-> the canonical form
 // K_canon, V_canon [rows][n][d], token-major for both.  scatter = 0: arena -> canonical; 1: canonical -> arena slots [t0, t0 + n), no other slot's bytes written.
 // All four pointers 16-byte aligned, d * element size a multiple of 16 and at most 1 KiB.

@@ -3,9 +3,11 @@
 //   KvGeom       the only place the token <-> byte conversions and the V block size are written
 //   kv_plan()    one operation on a stream's arena (KV_DROP in two forms: flags): refused (code and message), nothing to do, or what must have memory behind it, what is launched over which spans and the
 //                bookkeeping the stream has afterwards.  kv_run (model.hip) does what it says, in that order.
+//   kv_plan_spans()   mmd_kv_drop_spans: a LIST of spans in one owner walk per 64 of them -- the same contract, the launches as a list of retained segments
 //   kv_vmm_*, kv_grow_*   the capacities growth tries: the chunk of the virtual-memory arena, the virtual reservations of mmd_stream_create, the fallback arena's reallocation
 #pragma once
 #include <stdio.h>
+#include <vector>
 #include "gemm_plan.h"          // round_up, the MMD_ codes
 
 // ---- geometry ----------------------------------------------------------------------------------------------------------
@@ -189,6 +191,85 @@ static inline KvPlan kv_plan(int op, const KvGeom& g, const KvState& s, int64_t 
     return p;
 }
 #undef KV_REFUSE
+
+// ---- many spans in one walk --------------------------------------------------------------------------------------------
+// KV_DROP_SPANS (mmd_kv_drop_spans): the spans (from_i, to_i), i < n, ascending and disjoint, leave the context in ONE owner walk per launch (launch_kv_compact): every
+// retained byte moves once, and with KV_F_SHIFT every retained key is turned back once, by the tokens dropped in front of it.  The operation has a span LIST for its
+// argument, so it has a planning function of its own beside kv_plan() (whose operations 0 .. KV_OPS - 1 and signature stay as they are); kv_run_spans (model.hip) does
+// what the plan says, launch by launch.
+//   Normalised: empty spans are ignored, touching spans are merged.  A launch carries at most KV_SPANS_PER_LAUNCH retained SEGMENTS (src, count): the tokens between one
+//   span and the next (or the end of the context); the destination is implied -- dst_0 is given, dst_{i+1} = dst_i + count_i -- and delta_i = src_i - dst_i, the tokens
+//   dropped in front of segment i, grows strictly.  A final span that ends at `len` yields no segment.
+//   More spans than one launch takes: the spans are cut into groups of KV_SPANS_PER_LAUNCH and each group is a complete compaction of its own -- of the whole context
+//   behind the group's first span, tail included -- issued HIGHEST GROUP FIRST, so that the coordinates of a lower group are untouched by the launches before it.  The
+//   tail behind a group moves once per group at or below it: more traffic than one pass, paid only beyond KV_SPANS_PER_LAUNCH spans.  (A device-resident table would
+//   lift the limit; it is deliberately not built.)
+constexpr int KV_SPANS_PER_LAUNCH = 64;
+enum { KV_DROP_SPANS = KV_OPS + 1 };                                   // not an operation of kv_plan(): kv_plan_spans() plans it
+enum { KV_LAUNCH_COMPACT = KV_LAUNCH_DROP_SHIFT + 1,                   // launch_kv_compact(segments, dst0, len_end), inv_freq null ...
+       KV_LAUNCH_COMPACT_SHIFT };                                      // ... or the context's table: KV_F_SHIFT
+struct KvSeg { int64_t src, count; };
+struct KvCompact {
+    int64_t dst0 = 0;                  // the first destination slot: the group's first span starts here
+    int64_t len_in = 0, len_end = 0;   // the stream's length in front of this launch and behind it; no segment reaches beyond len_in, the last destination is len_end
+    int nseg = 0; KvSeg seg[KV_SPANS_PER_LAUNCH];
+};
+struct KvSpansPlan {
+    int rc = MMD_OK; char error[256] = {0};
+    bool nothing = false;              // no span, or only empty ones: MMD_OK, and nothing else happens
+    int launch = KV_LAUNCH_NONE;       // the kind of every launch in `launches` (NONE: the spans were a dropped tail, only the bookkeeping changes)
+    int64_t pitch_bytes = 0;
+    int64_t spans = 0, dropped = 0;    // normalised spans; tokens they hold
+    std::vector<KvCompact> launches;   // in the order they are issued
+    KvState after;
+};
+// spans: [n][2] in host memory (from, to); flags: KV_F_SHIFT or 0.  The checks stand in KV_DROP's order: the ranges, then the list's order, the stash, the head shape.
+static inline KvSpansPlan kv_plan_spans(const KvGeom& g, const KvState& s, const int64_t* spans, int n, int flags = 0) {
+    KvSpansPlan p; p.after = s;
+#define KV_REFUSE(code, ...) do { p.rc = (code); snprintf(p.error, sizeof(p.error), __VA_ARGS__); return p; } while (0)
+    if (n < 0 || (n > 0 && !spans)) KV_REFUSE(MMD_EINVAL, "kv_drop_spans: %d spans, or no span list", n);
+    for (int i = 0; i < n; ++i) {
+        const int64_t a = spans[2 * i], b = spans[2 * i + 1];
+        if (a < 0 || b < a || b > s.len) KV_REFUSE(MMD_ERANGE, "kv_drop_spans: span %d [%lld, %lld) outside the context (%lld tokens)", i, (long long)a, (long long)b, (long long)s.len);
+    }
+    for (int i = 1; i < n; ++i)
+        if (spans[2 * i] < spans[2 * i - 1])
+            KV_REFUSE(MMD_EINVAL, "kv_drop_spans: span %d [%lld, %lld) %s span %d [%lld, %lld) (the spans must ascend and be disjoint)", i, (long long)spans[2 * i], (long long)spans[2 * i + 1],
+                      spans[2 * i] < spans[2 * i - 2] ? "stands in front of" : "overlaps", i - 1, (long long)spans[2 * i - 2], (long long)spans[2 * i - 1]);
+    if (s.stash_from >= 0) KV_REFUSE(MMD_EINVAL, "kv_drop_spans while tokens [%lld, %lld) are stashed (unstash or drop the stash first)", (long long)s.stash_from, (long long)s.stash_to);
+    if ((flags & KV_F_SHIFT) && (g.head_dim % 2 != 0 || (g.elem_bytes != 2 && g.elem_bytes != 4) || ((size_t)(g.head_dim / 2) * g.elem_bytes) % 16 != 0 || g.rows() > 65535))
+        KV_REFUSE(MMD_EINVAL, "kv_drop_shift: head_dim %d x %d bytes (2- or 4-byte elements, half a head a multiple of 16 bytes) or %d x %d rows not supported", g.head_dim, g.elem_bytes,
+                  g.layers, g.kv_heads);
+#undef KV_REFUSE
+    std::vector<int64_t> norm(2 * (size_t)n);          // the normalised spans (norm[2 i], norm[2 i + 1]), i < m
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t a = spans[2 * i], b = spans[2 * i + 1];
+        if (a == b) continue;
+        if (m > 0 && norm[2 * m - 1] == a) norm[2 * m - 1] = b;
+        else { norm[2 * m] = a; norm[2 * m + 1] = b; ++m; }
+    }
+    if (m == 0) { p.nothing = true; return p; }
+    p.spans = m;
+    const int groups = (m + KV_SPANS_PER_LAUNCH - 1) / KV_SPANS_PER_LAUNCH;
+    int64_t cur = s.len;
+    for (int gi = groups - 1; gi >= 0; --gi) {          // highest group first
+        const int j = gi * KV_SPANS_PER_LAUNCH, k = j + KV_SPANS_PER_LAUNCH < m ? j + KV_SPANS_PER_LAUNCH : m;
+        KvCompact c; c.dst0 = norm[2 * j]; c.len_in = cur;
+        int64_t gone = 0;
+        for (int i = j; i < k; ++i) {
+            gone += norm[2 * i + 1] - norm[2 * i];
+            const int64_t src = norm[2 * i + 1], end = i + 1 < k ? norm[2 * i + 2] : cur;          // the retained tokens behind span i: up to the next span of the group, or the whole tail
+            if (end > src) { c.seg[c.nseg].src = src; c.seg[c.nseg].count = end - src; ++c.nseg; }
+        }
+        cur -= gone; c.len_end = cur; p.dropped += gone;
+        if (c.nseg > 0) p.launches.push_back(c);          // (a dropped tail moves nothing)
+    }
+    if (!p.launches.empty()) { p.launch = (flags & KV_F_SHIFT) ? KV_LAUNCH_COMPACT_SHIFT : KV_LAUNCH_COMPACT; p.pitch_bytes = (int64_t)g.pitch_bytes(s.cap); }
+    p.after.len = s.len - p.dropped;
+    if (!(flags & KV_F_SHIFT)) p.after.pos_off = s.pos_off + p.dropped;
+    return p;
+}
 
 // ---- growth ------------------------------------------------------------------------------------------------------------
 // Every byte growth puts behind the arena is zero-filled before its first use: key tiles may cover slots beyond the live length (their P is masked to 0), so those slots

@@ -1193,9 +1193,30 @@ static int kv_copy_pair(mmd_ctx* c, const KvPlan& p, char* K, char* V, void* Ko,
     }
     return MMD_OK;
 }
+// KV_DROP_SPANS: kv_run's order of business for the one operation whose argument is a span LIST (kv_plan_spans): refused, nothing, or its launches in the planned order
+// (highest group first).  The list is read here, on the host; nothing waits for the device.  The bookkeeping follows every launch (each is a complete compaction that ends
+// at its own len_end), so a launch that fails behind an earlier one of a grouped plan leaves the stream's length and position those of the arena as it then stands.
+static int kv_run_spans(mmd_stream* s, const int64_t* spans, int n, int flags) {
+    mmd_ctx* c = s->ctx; const KvGeom g = kv_geom(c);
+    const KvSpansPlan p = kv_plan_spans(g, kv_state(s), spans, n, flags);
+    if (p.rc != MMD_OK) FAIL(c, p.rc, "%s", p.error);
+    if (p.nothing) return MMD_OK;
+    const bool shift = p.launch == KV_LAUNCH_COMPACT_SHIFT;
+    if (shift && !c->inv_freq) FAIL(c, MMD_EINVAL, "kv_drop_shift: the context has no RoPE frequency table");
+    if (p.launch != KV_LAUNCH_NONE) hipSetDevice(c->device);
+    for (const KvCompact& l : p.launches) {
+        HIPCHK(c, launch_kv_compact(c->cfg.dtype, s->K, s->V, (int)g.rows(), p.pitch_bytes, g.head_dim, reinterpret_cast<const int64_t*>(l.seg), l.nseg, l.dst0, l.len_end,
+                                    shift ? c->inv_freq : nullptr, c->stream));
+        if (!shift) s->pos_off += s->len - l.len_end;          // (what a dropped tail in front of this launch took is in the difference too)
+        s->len = l.len_end;
+    }
+    s->len = p.after.len; s->pos_off = p.after.pos_off;
+    return MMD_OK;
+}
 // One operation on s's arena as kv_plan states it: refused, or -- in this order -- memory behind the tokens it needs, the stash buffers, the launches, the bookkeeping.
 // Ko / Vo: the side of the launches that is not s's arena -- the caller's buffers, a fork's source arena, nullptr for the stash buffers
 static int kv_run(mmd_stream* s, int op, int64_t a = 0, int64_t b = 0, const mmd_stream* src = nullptr, const void* Ko = nullptr, const void* Vo = nullptr, int flags = 0) {
+    if (op == KV_DROP_SPANS) return kv_run_spans(s, static_cast<const int64_t*>(Ko), (int)a, flags);          // a = n, Ko = the span list
     mmd_ctx* c = s->ctx; const KvGeom g = kv_geom(c);
     KvState from; if (src) from = kv_state(src);
     auto plan = [&]() { return kv_plan(op, g, kv_state(s), a, b, src ? &from : nullptr, kv_bufs(Ko, Vo), flags); };
@@ -1237,6 +1258,9 @@ extern "C" int mmd_kv_stash(mmd_stream* s, int64_t from, int64_t to) { return s 
 extern "C" int mmd_kv_unstash(mmd_stream* s) { return s ? kv_run(s, KV_UNSTASH) : MMD_EINVAL; }
 extern "C" int mmd_kv_drop(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_DROP, from, to) : MMD_EINVAL; }
 extern "C" int mmd_kv_drop_shift(mmd_stream* s, int64_t from, int64_t to) { return s ? kv_run(s, KV_DROP, from, to, nullptr, nullptr, nullptr, KV_F_SHIFT) : MMD_EINVAL; }
+extern "C" int mmd_kv_drop_spans(mmd_stream* s, const int64_t* spans_host, int n, int shift) {
+    return s && n >= 0 && (spans_host || n == 0) ? kv_run(s, KV_DROP_SPANS, n, 0, nullptr, spans_host, nullptr, shift ? KV_F_SHIFT : 0) : MMD_EINVAL;
+}
 // snapshots (DESIGN.md section 5 "Snapshots")
 extern "C" int mmd_kv_export(mmd_stream* s, int64_t from, int64_t to, void* K_out, void* V_out) { return s ? kv_run(s, KV_EXPORT, from, to, nullptr, K_out, V_out) : MMD_EINVAL; }
 extern "C" int mmd_kv_import(mmd_stream* s, const void* K_in, const void* V_in, int64_t n) { return s ? kv_run(s, KV_IMPORT, n, 0, nullptr, K_in, V_in) : MMD_EINVAL; }

@@ -1123,6 +1123,32 @@ hipError_t launch_kv_drop(int dtype, void* K, void* V, int rows, int64_t pitch_b
 // grid (KSEG + ESPLIT, rows): blocks x < KSEG own K groups [x * KP, ...) and [units / 2 + x * KP, ...), the others V dims as in kv_drop_kernel.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int KVS_KP = 4, KVS_U = KVD_U / 2;          // at most 4 pairs of groups per block (2 x 64 bytes of a token row); a thread holds KVS_U pairs = KVD_U groups
+// one pair of 16-byte groups d/2 apart turned back by the angles whose (cos, sin) stand in r[0 .. VEC): x1' = x1 c + x2 s, x2' = x2 c - x1 s, rounded once
+template <int ES>
+static __device__ __forceinline__ void kvs_turn_back(const u32x4_t lo, const u32x4_t hi, const float2* r_, u32x4_t& o1, u32x4_t& o2) {
+    if constexpr (ES == 4) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float2 r = r_[k];
+            const float x1 = __uint_as_float(lo[k]), x2 = __uint_as_float(hi[k]);
+            o1[k] = __float_as_uint(x1 * r.x + x2 * r.y);
+            o2[k] = __float_as_uint(x2 * r.x - x1 * r.y);
+        }
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            unsigned p1 = 0, p2 = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float2 r = r_[w * 2 + h];
+                const float x1 = bf2f((bf16_t)(lo[w] >> (16 * h))), x2 = bf2f((bf16_t)(hi[w] >> (16 * h)));
+                p1 |= (unsigned)f2bf(x1 * r.x + x2 * r.y) << (16 * h);
+                p2 |= (unsigned)f2bf(x2 * r.x - x1 * r.y) << (16 * h);
+            }
+            o1[w] = p1; o2[w] = p2;
+        }
+    }
+}
 template <int ES>
 __global__ __launch_bounds__(KVD_THREADS) void kv_drop_shift_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, long long from, long long to, long long len,
                                                                     const float* __restrict__ inv_freq_tab, int kseg, int kp, int ep, int nb) {
@@ -1159,28 +1185,7 @@ __global__ __launch_bounds__(KVD_THREADS) void kv_drop_shift_kernel(char* __rest
         for (int u = 0; u < KVS_U; ++u) {
             if (!ok[u]) continue;
             u32x4_t o1, o2;
-            if constexpr (ES == 4) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float2 r = cs[pi[u] * VEC + k];
-                    const float x1 = __uint_as_float(lo[u][k]), x2 = __uint_as_float(hi[u][k]);
-                    o1[k] = __float_as_uint(x1 * r.x + x2 * r.y);
-                    o2[k] = __float_as_uint(x2 * r.x - x1 * r.y);
-                }
-            } else {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    unsigned p1 = 0, p2 = 0;
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const float2 r = cs[pi[u] * VEC + w * 2 + h];
-                        const float x1 = bf2f((bf16_t)(lo[u][w] >> (16 * h))), x2 = bf2f((bf16_t)(hi[u][w] >> (16 * h)));
-                        p1 |= (unsigned)f2bf(x1 * r.x + x2 * r.y) << (16 * h);
-                        p2 |= (unsigned)f2bf(x2 * r.x - x1 * r.y) << (16 * h);
-                    }
-                    o1[w] = p1; o2[w] = p2;
-                }
-            }
+            kvs_turn_back<ES>(lo[u], hi[u], cs + pi[u] * VEC, o1, o2);
             *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u]) = o1;
             *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u] + halfb) = o2;
         }
@@ -1201,6 +1206,226 @@ hipError_t launch_kv_drop_shift(int dtype, void* K, void* V, int rows, int64_t p
     const dim3 grid(kseg + esplit, rows), block(KVD_THREADS);
     if (es == 4) hipLaunchKernelGGL(kv_drop_shift_kernel<4>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, inv_freq_dev, kseg, kp, ep, nb);
     else hipLaunchKernelGGL(kv_drop_shift_kernel<2>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, (long long)from, (long long)to, (long long)len, inv_freq_dev, kseg, kp, ep, nb);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mmd_kv_drop_spans: many spans leave every (layer, kv head) row in ONE owner walk.  What stays is a list of at most KVC_SEGS retained segments (src_i, count_i),
+// ascending; segment i moves down to dst_i, dst_0 given, dst_{i+1} = dst_i + count_i, so delta_i = src_i - dst_i -- the tokens dropped in front of it -- is at
+// least 1 and grows strictly.  Destination tokens [dst_0, dst_end) are walked front to back in tiles; a destination token t finds its segment (dst_i <= t <
+// dst_{i+1}) and its source t + delta_i.  kv_compact_kernel moves K bit for bit; kv_compact_shift_kernel turns the keys of segment i back by delta_i positions with
+// kv_drop_shift_kernel's arithmetic (kvs_turn_back, the (cosf, sinf) pairs re-evaluated on entering a segment: a = (float)delta_i * inv_freq[e]), so a one-segment
+// table gives mmd_kv_drop_shift's bits.  V is the same walk for both.
+//   Why it is right.  (1) Every source lies above its destination: delta_i >= delta_0 >= 1.  (2) Tiles ascend, and a tile's loads stand in front of its one barrier,
+//   its stores behind it.  (3) A tile's destinations [T, T + n) lie below every later tile's sources: a later destination t' >= T + n reads t' + delta > t'.  So no
+//   store of a tile, however late a thread issues it, can reach bytes a later tile loads, and the stores of earlier tiles (destinations < T) cannot have reached what
+//   this tile loads (sources > T; the aligned 16-byte V groups a thread loads start at or above its own destination group, because delta >= 1 and both are aligned).
+//   A thread cannot run two tiles ahead of another: the next tile's barrier holds it.  (4) Blocks share no byte: a K block owns a 16-byte-unit range of the token
+//   row (the shifted form: KP groups of the lower half with the KP groups d/2 above them), a V block a range of dims, in whatever order blocks run.
+//   The table travels BY VALUE in the kernel arguments (1 KiB) and every block copies it into LDS before it indexes it: no device-side table, no launch in front of
+//   the walk, nothing to synchronise.
+//   K, plain: kv_drop_kernel's owners and tile; tiles are runs of destination tokens and may cross segments.  K, shifted: kv_drop_shift_kernel's owners; a tile never
+//   crosses a segment (the block's rotation table belongs to one delta).
+//   V: a destination group of VEC tokens inside one segment takes kvd_walk_v's path (two aligned loads, byte funnel; sh = delta_i % VEC is per thread).  A group that
+//   draws from several segments (a segment may be one token long: up to VEC of them), or holds dst_0 or dst_end, loads each of its elements from its own source slot
+//   -- in front of the barrier like every other load -- and is stored element by element inside [dst_0, dst_end) only: nothing below dst_0 and nothing at or above
+//   dst_end is ever written, so slots behind the new length keep the (finite) arena bytes they held.
+// grid (KSEG + ESPLIT, rows) as in kv_drop_kernel / kv_drop_shift_kernel.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int KVC_SEGS = 64;                         // = KV_SPANS_PER_LAUNCH (kv_plan.h)
+struct KvSegTable { long long src[KVC_SEGS]; long long count[KVC_SEGS]; };
+struct KvcLds { long long src[KVC_SEGS], cnt[KVC_SEGS], dst[KVC_SEGS + 1]; };          // dst[nseg] = dst_end
+static __device__ __forceinline__ void kvc_table(const KvSegTable& tab, int nseg, long long dst0, KvcLds& l) {
+    const int tid = threadIdx.x;
+    if (tid < nseg) { l.src[tid] = tab.src[tid]; l.cnt[tid] = tab.count[tid]; }
+    __syncthreads();
+    if (tid <= nseg) {
+        long long dpos = dst0;
+        for (int j = 0; j < tid; ++j) dpos += l.cnt[j];
+        l.dst[tid] = dpos;
+    }
+    __syncthreads();
+}
+template <int ES>
+static __device__ __forceinline__ void kvc_walk_v(char* __restrict__ Vb, long long pitch, int d, const KvcLds& l, int nseg, int vblk, int ep, int nb) {
+    constexpr int VEC = 16 / ES, CPL = 64 / VEC;
+    constexpr unsigned FULL = (1u << VEC) - 1;
+    const int tid = threadIdx.x;
+    u32x4_t ra[KVD_U], rb[KVD_U];
+    char* row = Vb + (long long)blockIdx.y * pitch;
+    const int e0 = vblk * ep, per_blk = ep * CPL;
+    const long long dst0 = l.dst[0], dend = l.dst[nseg];
+    int lo = 0;                                      // the segment of the tile's first token (the same in every thread)
+    for (long long b0 = dst0 >> 6; b0 * 64 < dend; b0 += nb) {          // nb destination blocks of 64 tokens per tile
+        while (lo + 1 < nseg && b0 * 64 >= l.dst[lo + 1]) ++lo;
+        long long dst[KVD_U]; int sh[KVD_U]; unsigned vm[KVD_U];          // vm: the tokens of the group that are stored
+#pragma unroll
+        for (int u = 0; u < KVD_U; ++u) {
+            const int idx = u * KVD_THREADS + tid;
+            const int bi = idx / per_blk, r = idx % per_blk, e = e0 + r / CPL, g = r % CPL;
+            const long long t = (b0 + bi) * 64 + g * VEC;          // first destination token of the group
+            dst[u] = ((((t >> 6) * d + e) << 6) + (t & 63)) * ES;
+            vm[u] = 0; sh[u] = 0;
+            if (!(bi < nb && t + VEC > dst0 && t < dend)) continue;
+            int i = lo;
+            while (i + 1 < nseg && t >= l.dst[i + 1]) ++i;
+            if (t >= dst0 && t + VEC <= l.dst[i + 1]) {          // the whole group inside segment i: every source token below src_i + count_i
+                const long long delta = l.src[i] - l.dst[i];
+                sh[u] = (int)(delta % VEC) * ES;
+                const long long s0 = (t + delta) & ~(long long)(VEC - 1), s1 = s0 + VEC;
+                ra[u] = *reinterpret_cast<const u32x4_t*>(row + ((((s0 >> 6) * d + e) << 6) + (s0 & 63)) * ES);
+                rb[u] = sh[u] ? *reinterpret_cast<const u32x4_t*>(row + ((((s1 >> 6) * d + e) << 6) + (s1 & 63)) * ES) : u32x4_t{0, 0, 0, 0};          // (sh != 0: the group's last source token lies in s1's group)
+                vm[u] = FULL;
+            } else {
+                u32x4_t o = {0, 0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    const long long tk = t + k;
+                    if (tk < dst0 || tk >= dend) continue;
+                    while (i + 1 < nseg && tk >= l.dst[i + 1]) ++i;
+                    const long long s = tk + (l.src[i] - l.dst[i]);
+                    const char* a = row + ((((s >> 6) * d + e) << 6) + (s & 63)) * ES;
+                    if constexpr (ES == 2) o[k >> 1] |= (unsigned)*reinterpret_cast<const unsigned short*>(a) << (16 * (k & 1));
+                    else o[k] = *reinterpret_cast<const unsigned*>(a);
+                    vm[u] |= 1u << k;
+                }
+                ra[u] = o; rb[u] = u32x4_t{0, 0, 0, 0};
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KVD_U; ++u) {
+            if (!vm[u]) continue;
+            const u32x4_t o = sh[u] ? kvd_funnel(ra[u], rb[u], sh[u]) : ra[u];
+            if (vm[u] == FULL) *reinterpret_cast<u32x4_t*>(row + dst[u]) = o;
+            else {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) {
+                    if (!((vm[u] >> k) & 1)) continue;
+                    const unsigned w = o[(k * ES) >> 2];
+                    if (ES == 2) *reinterpret_cast<unsigned short*>(row + dst[u] + k * 2) = (unsigned short)(k & 1 ? w >> 16 : w);
+                    else *reinterpret_cast<unsigned*>(row + dst[u] + k * 4) = w;
+                }
+            }
+        }
+    }
+}
+template <int ES>
+__global__ __launch_bounds__(KVD_THREADS) void kv_compact_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, const KvSegTable tab, int nseg, long long dst0,
+                                                                 int kseg, int ku, int ep, int nb) {
+    __shared__ KvcLds l;
+    kvc_table(tab, nseg, dst0, l);
+    if ((int)blockIdx.x >= kseg) { kvc_walk_v<ES>(Vb, pitch, d, l, nseg, (int)blockIdx.x - kseg, ep, nb); return; }
+    const int tid = threadIdx.x;
+    u32x4_t ra[KVD_U];
+    const long long tokb = (long long)d * ES, dend = l.dst[nseg];
+    char* row = Kb + (long long)blockIdx.y * pitch + (long long)blockIdx.x * ku * 16;
+    const long long tile = (long long)(KVD_THREADS * KVD_U) / ku;          // tokens per tile
+    int lo = 0;
+    for (long long t0 = dst0; t0 < dend; t0 += tile) {
+        while (lo + 1 < nseg && t0 >= l.dst[lo + 1]) ++lo;
+        long long off[KVD_U]; bool ok[KVD_U];
+#pragma unroll
+        for (int u = 0; u < KVD_U; ++u) {
+            const int idx = u * KVD_THREADS + tid;
+            const long long t = t0 + idx / ku;
+            ok[u] = idx / ku < tile && t < dend;
+            off[u] = t * tokb + (idx % ku) * 16;
+            if (ok[u]) {
+                int i = lo;
+                while (i + 1 < nseg && t >= l.dst[i + 1]) ++i;
+                ra[u] = *reinterpret_cast<const u32x4_t*>(row + (l.src[i] - l.dst[i]) * tokb + off[u]);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < KVD_U; ++u) if (ok[u]) *reinterpret_cast<u32x4_t*>(row + off[u]) = ra[u];
+    }
+}
+template <int ES>
+__global__ __launch_bounds__(KVD_THREADS) void kv_compact_shift_kernel(char* __restrict__ Kb, char* __restrict__ Vb, long long pitch, int d, const KvSegTable tab, int nseg, long long dst0,
+                                                                       const float* __restrict__ inv_freq_tab, int kseg, int kp, int ep, int nb) {
+    constexpr int VEC = 16 / ES;
+    __shared__ KvcLds l;
+    __shared__ float2 cs[KVS_KP * 8];
+    kvc_table(tab, nseg, dst0, l);
+    if ((int)blockIdx.x >= kseg) { kvc_walk_v<ES>(Vb, pitch, d, l, nseg, (int)blockIdx.x - kseg, ep, nb); return; }
+    const int tid = threadIdx.x;
+    const long long tokb = (long long)d * ES, halfb = tokb / 2;
+    const int g0 = (int)blockIdx.x * kp;          // the block's first group of the lower half
+    char* row = Kb + (long long)blockIdx.y * pitch + (long long)g0 * 16;
+    const long long tile = (long long)(KVD_THREADS * KVS_U) / kp;          // tokens per tile
+    for (int i = 0; i < nseg; ++i) {
+        const long long n = l.cnt[i], to = l.src[i], from = l.dst[i], delta = to - from;
+        __syncthreads();          // (the last tile of the segment before has read its table)
+        if (tid < kp * VEC) {
+            const float ang = (float)delta * inv_freq_tab[g0 * VEC + tid];
+            cs[tid] = make_float2(cosf(ang), sinf(ang));
+        }
+        __syncthreads();
+        for (long long t0 = 0; t0 < n; t0 += tile) {
+            u32x4_t lo[KVS_U], hi[KVS_U]; long long off[KVS_U]; int pi[KVS_U]; bool ok[KVS_U];
+#pragma unroll
+            for (int u = 0; u < KVS_U; ++u) {
+                const int idx = u * KVD_THREADS + tid;
+                const long long t = t0 + idx / kp;
+                ok[u] = idx / kp < tile && t < n;
+                pi[u] = idx % kp;
+                off[u] = t * tokb + pi[u] * 16;
+                if (ok[u]) {
+                    lo[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u]);
+                    hi[u] = *reinterpret_cast<const u32x4_t*>(row + to * tokb + off[u] + halfb);
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < KVS_U; ++u) {
+                if (!ok[u]) continue;
+                u32x4_t o1, o2;
+                kvs_turn_back<ES>(lo[u], hi[u], cs + pi[u] * VEC, o1, o2);
+                *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u]) = o1;
+                *reinterpret_cast<u32x4_t*>(row + from * tokb + off[u] + halfb) = o2;
+            }
+        }
+    }
+}
+// segs: [nseg][2] (src, count) in HOST memory, read before the call returns.  inv_freq_dev null: the plain form.  len_end: the stream's length behind the launch; the
+// last destination must not lie above it.  A table that is not ascending with delta_0 >= 1, or a head shape the walk does not take: hipErrorInvalidValue, nothing launched
+hipError_t launch_kv_compact(int dtype, void* K, void* V, int rows, int64_t pitch_bytes, int d, const int64_t* segs, int nseg, int64_t dst0, int64_t len_end, const float* inv_freq_dev,
+                             hipStream_t st) {
+    if (nseg < 0 || nseg > KVC_SEGS || (nseg > 0 && !segs) || dst0 < 0) return hipErrorInvalidValue;
+    if (inv_freq_dev && dtype != MMD_BF16 && dtype != MMD_F32) return hipErrorInvalidValue;
+    const int es = (int)dtype_size(dtype), units = d * es / 16, vec = 16 / es, cpl = 64 / vec;
+    if (d <= 0 || (d * es) % 16 != 0 || (pitch_bytes % 16) != 0 || rows > 65535) return hipErrorInvalidValue;
+    if (inv_freq_dev && (d % 2 != 0 || ((d / 2) * es) % 16 != 0)) return hipErrorInvalidValue;
+    KvSegTable tab = {};
+    int64_t dpos = dst0, last = dst0;          // last: the end of the sources so far
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t src = segs[2 * i], count = segs[2 * i + 1];
+        if (count <= 0 || src <= last) return hipErrorInvalidValue;          // src_0 > dst_0, and a gap (a dropped span) in front of every segment: delta grows strictly
+        tab.src[i] = src; tab.count[i] = count;
+        dpos += count; last = src + count;
+    }
+    if (dpos > len_end) return hipErrorInvalidValue;
+    int esplit, ep, nb;
+    if (!kvd_v_split(d, cpl, &esplit, &ep, &nb)) return hipErrorInvalidValue;
+    if (nseg == 0 || rows <= 0) return hipSuccess;
+    const dim3 block(KVD_THREADS);
+    if (inv_freq_dev) {
+        const int hu = (d / 2) * es / 16;                                           // 16-byte groups in half a token row
+        const int kp = hu % KVS_KP == 0 ? KVS_KP : hu % 2 == 0 ? 2 : 1;
+        const int kseg = hu / kp;
+        const dim3 grid(kseg + esplit, rows);
+        if (es == 4) hipLaunchKernelGGL(kv_compact_shift_kernel<4>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, tab, nseg, (long long)dst0, inv_freq_dev, kseg, kp, ep, nb);
+        else hipLaunchKernelGGL(kv_compact_shift_kernel<2>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, tab, nseg, (long long)dst0, inv_freq_dev, kseg, kp, ep, nb);
+    } else {
+        const int ku = units % 8 == 0 ? 8 : units;                                  // 128-byte pieces of a K row where it divides
+        if (ku > KVD_THREADS * KVD_U) return hipErrorInvalidValue;
+        const int kseg = units / ku;
+        const dim3 grid(kseg + esplit, rows);
+        if (es == 4) hipLaunchKernelGGL(kv_compact_kernel<4>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, tab, nseg, (long long)dst0, kseg, ku, ep, nb);
+        else hipLaunchKernelGGL(kv_compact_kernel<2>, grid, block, 0, st, (char*)K, (char*)V, (long long)pitch_bytes, d, tab, nseg, (long long)dst0, kseg, ku, ep, nb);
+    }
     return hipGetLastError();
 }
 

@@ -53,6 +53,29 @@ def context_drop_amount(length, rows, window, sink, quantum=0):
     return m
 
 
+def context_evict_spans(frames, need, sink, length, recent):
+    """Informative eviction: which frames leave a context of `length` tokens that must lose at least `need` of them.  `frames`: the ledger, (start, end, informative
+    score) of every frame in the context.  Candidates start at or behind `sink` and end at or in front of length - recent (the last `recent` tokens are never evicted);
+    they are taken in ascending score, ties oldest first, until `need` tokens are freed.  -> their spans, ascending and merged where they touch ([] for need <= 0), or
+    None when the candidates cannot free `need` tokens (the caller then drops the oldest tokens, as without the policy)."""
+    if need <= 0:
+        return []
+    picked, freed = [], 0
+    for score, start, end in sorted((f[2], f[0], f[1]) for f in frames if f[0] >= sink and f[1] <= length - recent):
+        if freed >= need:
+            break
+        picked.append((start, end)); freed += end - start
+    if freed < need:
+        return None
+    spans = []
+    for a, b in sorted(picked):
+        if spans and spans[-1][1] == a:
+            spans[-1] = (spans[-1][0], b)
+        else:
+            spans.append((a, b))
+    return spans
+
+
 class LiveInferForBenchmark:
     def __init__(self, args, model=None, tokenizer=None) -> None:
         assert not (args.bf16 and args.fp16), "only one of --bf16 true and --fp16 true can be set"
@@ -128,6 +151,17 @@ class LiveInferForBenchmark:
         if self.context_positions not in ('kept', 'shifted'):
             raise ValueError(f"context_positions must be 'kept' or 'shifted', not {self.context_positions!r}")
         self.context_drop_quantum = int(getattr(args, 'context_drop_quantum', 0) or 0)
+        # what the window takes out (DESIGN.md "Eviction"): 'oldest' (default) the tokens right behind the sink; 'informative' the frames the informative head scored
+        # lowest, wherever they lie in front of the last `context_recent` tokens (None: half the window), all in one mmd_kv_drop_spans
+        self.context_evict = str(getattr(args, 'context_evict', None) or 'oldest')
+        if self.context_evict not in ('oldest', 'informative'):
+            raise ValueError(f"context_evict must be 'oldest' or 'informative', not {self.context_evict!r}")
+        self.context_recent = getattr(args, 'context_recent', None)
+        if self.context_recent is not None:
+            if isinstance(self.context_recent, (bool, str)) or not isinstance(self.context_recent, (int, float)) or int(self.context_recent) != self.context_recent \
+                    or self.context_recent < 0:
+                raise ValueError(f'context_recent must be a token count >= 0 (or None: half the window), not {self.context_recent!r}')
+            self.context_recent = int(self.context_recent)
         self.frames_per_forward = max(1, int(getattr(args, 'frames_per_forward', 1)))
         self.overlap_vision = bool(getattr(args, 'overlap_vision', True))
         self.record_head_logits = False          # diagnostics (parity tests, bench.py's self-check): debug_data entries also carry the 4 raw head logits of the frame
@@ -185,6 +219,8 @@ class LiveInferForBenchmark:
         self._vit_batches, self._vit_events, self._vit_waited = [], [], set()
         self._sink_tokens = None             # context_sink None: the context length right after this stream's first forward
         self.dropped_tokens = 0              # tokens the context window took out of this stream
+        self.evicted_frames = 0              # ... and the frames that lost tokens to it, under either policy (a frame the oldest-first span only cuts counts too)
+        self._frame_ledger = []              # [start, end, informative score] of every frame whose tokens are in past_key_values, ascending
         self.forward_calls = 0              # LLM forwards issued (diagnostics of the chunked schedule)
         self.replayed_frames = 0
 
@@ -332,10 +368,40 @@ class LiveInferForBenchmark:
         if sink is None:
             return
         n = len(self.past_key_values)
+        self._ledger_update(length=n)
         m = context_drop_amount(n, rows, self.context_window, min(sink, n), self.context_drop_quantum)
-        if m > 0:
-            self.past_key_values = self.model.kv_drop(self.past_key_values, min(sink, n), min(sink, n) + m, shift=self.context_positions == 'shifted')
-            self.dropped_tokens += m
+        if m <= 0:
+            return
+        shift = self.context_positions == 'shifted'
+        if getattr(self, 'context_evict', 'oldest') == 'informative':
+            recent = self.context_window // 2 if self.context_recent is None else int(self.context_recent)
+            spans = context_evict_spans(self._frame_ledger, m, min(sink, n), n, recent)
+            if spans:
+                self.past_key_values = self.model.kv_drop_many(self.past_key_values, spans, shift=shift)
+                self.dropped_tokens += sum(b - a for a, b in spans)
+                self._ledger_update(spans=spans)
+                return
+        self.past_key_values = self.model.kv_drop(self.past_key_values, min(sink, n), min(sink, n) + m, shift=shift)
+        self.dropped_tokens += m
+        self._ledger_update(spans=[(min(sink, n), min(sink, n) + m)])
+
+    def _ledger_update(self, length=None, spans=()):
+        """Keep the frame ledger in step with the context.  `length`: the context was cut back to that many tokens (a speculative chunk's prefix, a rollback, a replay) --
+        frames that reach beyond it are gone.  `spans` (ascending, disjoint): those tokens were dropped -- a frame a span cuts is gone (counted in evicted_frames), the
+        frames behind a span slide down by what was dropped in front of them."""
+        led = self._frame_ledger
+        if length is not None:
+            while led and led[-1][1] > length:
+                led.pop()
+        if spans:
+            kept = []
+            for start, end, score in led:
+                if any(a < end and start < b for a, b in spans):
+                    self.evicted_frames += 1
+                    continue
+                gone = sum(b - a for a, b in spans if b <= start)
+                kept.append([start - gone, end - gone, score])
+            self._frame_ledger = kept
 
     def _note_first_forward(self):
         if getattr(self, '_sink_tokens', None) is None and self.past_key_values:
@@ -375,6 +441,9 @@ class LiveInferForBenchmark:
         for l0, l1, r0, r1 in self._chunk_head_logits:
             probs_inf.append(_p1(l0, l1)); probs_rel.append(_p1(r0, r1))
         ends = [n0 + P + (j + 1) * nt for j in range(len(frames))]
+        if getattr(self, 'context_window', 0) > 0:
+            self._ledger_update(length=n0)
+            self._frame_ledger.extend([e - nt, e, p] for e, p in zip(ends, probs_inf))
         return list(zip(probs_inf, probs_rel)), ends, cache
 
     def _step_input(self, prefix_ids, frames):
@@ -572,7 +641,8 @@ class LiveInferForBenchmark:
                         stash = self.model.kv_stash(cache, ends[j])
                     # context = everything up to the end of frame j; otherwise later frames of the chunk are replayed
                     self.past_key_values = cache if last else self.model.cache_prefix(arena_handle, ends[j])
-                    if not last and not keep_tail:
+                    if not last and not keep_tail:          # (under a stash the frames behind frame j come back with the unstash)
+                        self._ledger_update(length=ends[j])
                         for item in reversed(chunk[j + 1:]):
                             self.frame_embeds_queue.appendleft(item)
                         self.replayed_frames += k - 1 - j

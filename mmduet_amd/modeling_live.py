@@ -696,6 +696,33 @@ class VideoHeadLiveLlavaQwenForCausalLM:
                     hd.stale = True
         return KVCacheHandle(arena, handle.length - (end - start))
 
+    def kv_drop_many(self, handle: KVCacheHandle, spans, shift: bool = False):
+        """`kv_drop` for many spans at once (mmd_kv_drop_spans): `spans` is any iterable of (start, end), ascending and disjoint; what stays moves down once, and with
+        `shift` every retained key is turned back once, by the tokens dropped in front of it.  `kv_position` behaves as for `kv_drop`.
+        -> the handle of the shortened context; every other handle that reached beyond the first span is stale."""
+        if handle.stale:
+            raise RuntimeError('stale KV handle')
+        spans = [(int(a), int(b)) for a, b in spans]
+        for a, b in spans:
+            if not 0 <= a <= b <= handle.length:
+                raise ValueError(f'kv_drop_many [{a}, {b}) outside the context ({handle.length} tokens)')
+        arena = handle.arena
+        if arena is None or not spans:
+            return handle
+        flat = (C.c_int64 * (2 * len(spans)))(*[x for sp in spans for x in sp])
+        with self._lock:
+            arena.truncate(handle.length)
+            self._bind_stream()
+            check(lib().mmd_kv_drop_spans(arena.h, C.cast(flat, C.c_void_p), len(spans), 1 if shift else 0), self._ctx, 'mmd_kv_drop_spans')
+            total = sum(b - a for a, b in spans)
+            if total == 0:
+                return handle
+            first = min(a for a, b in spans if b > a)
+            for hd in list(arena.handles):
+                if hd.length > first:
+                    hd.stale = True
+        return KVCacheHandle(arena, handle.length - total)
+
     def kv_position(self, handle: KVCacheHandle):
         """The rotary position the next token appended to `handle` gets: its length plus everything `kv_drop` took out of its arena without `shift`."""
         if handle is None or handle.arena is None:
