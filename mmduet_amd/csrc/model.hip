@@ -11,6 +11,7 @@
 #include "tower_plan.h"
 #include "select_plan.h"
 #include "kv_plan.h"
+#include "pixel_taps.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -907,34 +908,7 @@ extern "C" int mmd_vit_debug_tap(mmd_ctx* c, int stage, void* out, int64_t out_e
     return MMD_OK;
 }
 
-// Pillow's bicubic tap tables (src/libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc)
-static double bicubic_filter(double x) {
-    const double a = -0.5;
-    if (x < 0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
-static void pil_coeffs(int in_size, int out_size, std::vector<int32_t>& coef, std::vector<int32_t>& bounds, int& ksize) {
-    double scale = (double)in_size / out_size, filterscale = scale < 1.0 ? 1.0 : scale;
-    double support = 2.0 * filterscale;
-    ksize = (int)ceil(support) * 2 + 1;
-    coef.assign((size_t)out_size * ksize, 0); bounds.assign((size_t)out_size * 2, 0);
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < out_size; ++xx) {
-        double center = (xx + 0.5) * scale, ww = 0.0, ss = 1.0 / filterscale;
-        int xmin = (int)(center - support + 0.5); if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5); if (xmax > in_size) xmax = in_size;
-        xmax -= xmin;
-        for (int x = 0; x < ksize; ++x) k[x] = 0.0;
-        for (int x = 0; x < xmax; ++x) { double w = bicubic_filter((x + xmin - center + 0.5) * ss); k[x] = w; ww += w; }
-        for (int x = 0; x < xmax; ++x) if (ww != 0.0) k[x] /= ww;
-        for (int x = 0; x < ksize; ++x) coef[(size_t)xx * ksize + x] = k[x] < 0 ? (int32_t)(-0.5 + k[x] * (1 << 22)) : (int32_t)(0.5 + k[x] * (1 << 22));
-        bounds[2 * xx] = xmin; bounds[2 * xx + 1] = xmax;
-    }
-}
-
-// Pillow tap tables + scratch for frames of resolution R (cached per context)
+// Pillow tap tables (pixel_taps.h) + scratch for frames of resolution R (cached per context)
 static int ensure_preprocess_tables(mmd_ctx* c, int T, int R) {
     const int size = c->cfg.vit_image;
     if (R != size && c->pp_R != R) {
@@ -967,41 +941,12 @@ extern "C" int mmd_preprocess_frames(mmd_ctx* c, const uint8_t* frames, int T, i
     return MMD_OK;
 }
 
-// OpenCV's 8-bit INTER_LINEAR tap table for one axis (imgproc/resize.cpp, resize() -> ResizeLinear setup):
-//   f = (float)((d + 0.5) * scale - 0.5); s = floor(f); f -= s; weights = saturate_cast<short>(w * 2048) (round half to even).
-// The x axis clamps the tap pair at the borders (s < 0 -> s = 0, f = 0; s >= n-1 -> s = n-1, f = 0); the y axis keeps f and
-// clips the two row indices instead.  Entry: {s0, s1, w0, w1}.
-static void cv_linear_taps(int src_n, int dst_n, bool x_axis, std::vector<int32_t>& tab) {
-    const double inv_scale = (double)dst_n / src_n, scale = 1.0 / inv_scale;
-    tab.resize((size_t)dst_n * 4);
-    for (int d = 0; d < dst_n; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        int s0, s1;
-        if (x_axis) {
-            if (s < 0) { f = 0.f; s = 0; }
-            if (s >= src_n - 1) { f = 0.f; s = src_n - 1; }
-            s0 = s; s1 = s + 1 < src_n ? s + 1 : src_n - 1;
-        } else {
-            s0 = s < 0 ? 0 : (s < src_n ? s : src_n - 1);
-            s1 = s + 1 < 0 ? 0 : (s + 1 < src_n ? s + 1 : src_n - 1);
-        }
-        const float w0 = (1.f - f) * 2048.f, w1 = f * 2048.f;
-        long r0 = lrintf(w0), r1 = lrintf(w1);
-        r0 = r0 < -32768 ? -32768 : (r0 > 32767 ? 32767 : r0); r1 = r1 < -32768 ? -32768 : (r1 > 32767 ? 32767 : r1);
-        tab[4 * d] = s0; tab[4 * d + 1] = s1; tab[4 * d + 2] = (int32_t)r0; tab[4 * d + 3] = (int32_t)r1;
-    }
-}
-
 extern "C" int mmd_letterbox_geometry(int W, int H, int R, int* new_w, int* new_h, int* top, int* bottom, int* left, int* right) {
     if (W <= 0 || H <= 0 || R <= 0) return MMD_EINVAL;
-    int nw, nh;
-    if (W > H) { nw = R; nh = (int)(((double)H / (double)W) * R); }       // test/datasets.py:53-60
-    else { nh = R; nw = (int)(((double)W / (double)H) * R); }
-    if (new_w) *new_w = nw; if (new_h) *new_h = nh;
-    if (top) *top = (R - nh) / 2; if (bottom) *bottom = (R - nh + 1) / 2;
-    if (left) *left = (R - nw) / 2; if (right) *right = (R - nw + 1) / 2;
+    const LetterboxGeom g = letterbox_geom(W, H, R);       // test/datasets.py:53-60
+    if (new_w) *new_w = g.new_w; if (new_h) *new_h = g.new_h;
+    if (top) *top = g.top; if (bottom) *bottom = g.bottom;
+    if (left) *left = g.left; if (right) *right = g.right;
     return MMD_OK;
 }
 
@@ -1024,9 +969,7 @@ extern "C" int mmd_letterbox_frames(mmd_ctx* c, const uint8_t* frames, int T, in
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->lb_W = W; c->lb_H = H; c->lb_R = R;
     }
-    // resize.cpp: INTER_LINEAR with both scales exactly 2 is routed to the 2x2 INTER_AREA kernel
-    const double sx = 1.0 / ((double)nw / W), sy = 1.0 / ((double)nh / H);
-    const int area2x = (fabs(sx - 2.0) < DBL_EPSILON && fabs(sy - 2.0) < DBL_EPSILON) ? 1 : 0;
+    const int area2x = letterbox_area2x(W, H, nw, nh);
     uint32_t pad = 0;
     if (pad_color) pad = (uint32_t)pad_color[0] | ((uint32_t)pad_color[1] << 8) | ((uint32_t)pad_color[2] << 16);
     ProfScope ps(c, MMD_K_OTHER, 0, 0);
