@@ -12,6 +12,7 @@
 #include "select_plan.h"
 #include "kv_plan.h"
 #include "pixel_taps.h"
+#include "model_plan.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -69,7 +70,7 @@ struct mmd_ctx {
     hipStream_t own_stream = nullptr, stream = nullptr;
     std::string err;
     std::unordered_map<std::string, RawTensor> raw;
-    std::vector<void*> allocs;
+    std::vector<void*> allocs, host_allocs;          // every device buffer (dev_alloc) and every pinned host buffer (host_alloc) of the context: mmd_destroy frees the lists
     int64_t weight_bytes = 0;
     bool finalized = false;
     // fused weights
@@ -177,6 +178,11 @@ static int dev_alloc(mmd_ctx* c, void** out, size_t bytes, bool zero = true) {
     *out = p;
     return MMD_OK;
 }
+static int host_alloc(mmd_ctx* c, void** out, size_t bytes) {
+    HIPCHK(c, hipHostMalloc(out, bytes));
+    c->host_allocs.push_back(*out);
+    return MMD_OK;
+}
 static void dev_free(mmd_ctx* c, void* p) {
     if (!p) return;
     for (size_t i = 0; i < c->allocs.size(); ++i) if (c->allocs[i] == p) { c->allocs[i] = c->allocs.back(); c->allocs.pop_back(); break; }
@@ -265,17 +271,8 @@ static bool gemm_pair_pm(mmd_ctx* c, const void* X1, int64_t ldx1, const void* W
 
 // ---- create / destroy ------------------------------------------------------------------------------------------------
 extern "C" int mmd_create(const mmd_config* cfg, int device, mmd_ctx** out) {
-    if (!cfg || !out) { g_create_error = "null argument"; return MMD_EINVAL; }
-    if (cfg->struct_size != (int32_t)sizeof(mmd_config)) { g_create_error = "mmd_config size mismatch (ABI)"; return MMD_EINVAL; }
-    if (cfg->dtype != MMD_F32 && cfg->dtype != MMD_BF16) { g_create_error = "unsupported dtype"; return MMD_EINVAL; }
-    if (cfg->weight_dtype != MMD_W_DTYPE && (cfg->weight_dtype != MMD_W_FP8_E4M3 || cfg->dtype != MMD_BF16)) { g_create_error = "weight_dtype fp8_e4m3 needs a bf16 context"; return MMD_EINVAL; }
-    if (!cfg->vision_only && (cfg->num_heads % cfg->num_kv_heads != 0 || cfg->head_dim % 2 != 0 || cfg->head_dim > 128)) { g_create_error = "unsupported head configuration"; return MMD_EINVAL; }
-    if (cfg->vit_hidden % cfg->vit_heads != 0 || cfg->vit_hidden / cfg->vit_heads > 128) { g_create_error = "unsupported ViT head configuration"; return MMD_EINVAL; }
-    if (cfg->tower_f16 && (cfg->dtype != MMD_BF16 || cfg->vision_only || cfg->vit_class_token || cfg->vit_pre_layernorm || cfg->vit_act != 0 || cfg->vit_pool_head ||
-                           (cfg->vit_hidden % 64) != 0 || ((cfg->vit_hidden / cfg->vit_heads) % 8) != 0)) {
-        g_create_error = "tower_f16 needs a bf16 context and the LLaVA SigLIP tower form (no class token / pre-LN / pooling head, hidden % 64 == 0, head_dim % 8 == 0)"; return MMD_EINVAL; }
-    if (cfg->tower_f16 < 0 || cfg->tower_f16 > 2 || (cfg->tower_f16 == 1 && (cfg->vit_post_layernorm || cfg->vit_hidden > 2048))) {
-        g_create_error = "tower_f16: 0 | 1 (autocast: fp32 residual stream; no post_layernorm, hidden <= 2048) | 2 (fp16 residual stream)"; return MMD_EINVAL; }
+    const ModelDims dims = model_dims(out ? cfg : nullptr);
+    if (dims.rc) { g_create_error = dims.error; return dims.rc; }
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return MMD_EHIP; }
     mmd_ctx* c = new mmd_ctx();
@@ -283,12 +280,7 @@ extern "C" int mmd_create(const mmd_config* cfg, int device, mmd_ctx** out) {
     e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete c; return MMD_EHIP; }
     c->stream = c->own_stream;
-    c->vit_grid = cfg->vit_image / cfg->vit_patch;
-    c->vit_tokens = c->vit_grid * c->vit_grid;
-    c->vit_seq = c->vit_tokens + (cfg->vit_class_token ? 1 : 0);
-    c->vit_kpad = (int)round_up(3 * cfg->vit_patch * cfg->vit_patch, 64);
-    c->vit_ipad = (int)round_up(cfg->vit_intermediate, 64);
-    c->qkv_w = cfg->vision_only ? 0 : (cfg->num_heads + 2 * cfg->num_kv_heads) * cfg->head_dim;
+    c->vit_grid = dims.vit_grid; c->vit_tokens = dims.vit_tokens; c->vit_seq = dims.vit_seq; c->vit_kpad = dims.vit_kpad; c->vit_ipad = dims.vit_ipad; c->qkv_w = dims.qkv_w;
     auto is1 = [](const char* name) { const char* v = getenv(name); return v && v[0] == '1'; };
     StepSwitches& sw = c->sw;
     { const char* nf = getenv("MMDUET_NO_FUSE"); sw.no_fuse = nf && nf[0] == '1'; sw.no_pm = nf && (nf[0] == '1' || nf[0] == '2'); }          // (2: only the piece-major MLP intermediates off -- their A/B)
@@ -309,15 +301,7 @@ extern "C" void mmd_destroy(mmd_ctx* c) {
     prof_drain(c);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     for (void* p : c->allocs) hipFree(p);
-    if (c->heads_host) hipHostFree(c->heads_host);
-    if (c->rows_host) hipHostFree(c->rows_host);
-    if (c->tok_host) hipHostFree(c->tok_host);
-    if (c->step_host) hipHostFree(c->step_host);
-    if (c->seg_host) hipHostFree(c->seg_host);
-    if (c->round_toks_host) hipHostFree(c->round_toks_host);
-    if (c->round_lp_rows_host) hipHostFree(c->round_lp_rows_host);
-    if (c->samp_rows_host) hipHostFree(c->samp_rows_host);
-    if (c->cons_rows_host) hipHostFree(c->cons_rows_host);
+    for (void* p : c->host_allocs) hipHostFree(p);
     for (auto& ev : c->seg_event) if (ev) hipEventDestroy(ev);
     c->dec_greedy.drop(); c->dec_sampled.drop();
     hipStreamDestroy(c->own_stream);
@@ -336,14 +320,6 @@ extern "C" int mmd_synchronize(mmd_ctx* c) { if (!c) return MMD_EINVAL; HIPCHK(c
 extern "C" int64_t mmd_weight_bytes(const mmd_ctx* c) { return c ? c->weight_bytes : 0; }
 
 // ---- weights ---------------------------------------------------------------------------------------------------------
-static std::string canon_name(const char* name) {
-    std::string n(name);
-    const std::string a = "model.vision_tower.vision_tower.vision_model.", b = "model.vision_tower.vision_tower.";
-    if (n.compare(0, a.size(), a) == 0) return "vit." + n.substr(a.size());
-    if (n.compare(0, b.size(), b) == 0) return "vit." + n.substr(b.size());
-    return n;
-}
-
 extern "C" int mmd_load_tensor(mmd_ctx* c, const char* name, const void* data, int src_dtype, const int64_t* shape, int rank, int on_device) {
     if (!c || !name || !data || rank < 1 || rank > 4) return MMD_EINVAL;
     if (c->finalized) FAIL(c, MMD_EINVAL, "weights already finalized");
@@ -406,32 +382,20 @@ extern "C" int mmd_set_rope_inv_freq(mmd_ctx* c, const float* host, int n) {
     return MMD_OK;
 }
 
-static int take(mmd_ctx* c, const std::string& name, std::vector<int64_t> shape, RawTensor* out) {
-    auto it = c->raw.find(name);
-    if (it == c->raw.end()) FAIL(c, MMD_ENOENT, "missing weight tensor '%s'", name.c_str());
-    int64_t n = 1; for (auto s : shape) n *= s;
-    if (it->second.numel != n) FAIL(c, MMD_EINVAL, "weight '%s' has %lld elements, expected %lld", name.c_str(), (long long)it->second.numel, (long long)n);
-    *out = it->second;
-    c->raw.erase(it);
-    return MMD_OK;
-}
-#define TAKE(var, name, ...) RawTensor var; { int _rc = take(c, name, __VA_ARGS__, &var); if (_rc) return _rc; }
-
 static int alloc_workspaces(mmd_ctx* c);
 
 // MFMA-fragment-major copy of a bf16 weight matrix for the weight-streaming skinny GEMM (null if the shape does not tile)
 static int make_packed(mmd_ctx* c, const void* W, int N, int K, void** out) {
     *out = nullptr;
-    if (c->cfg.dtype != MMD_BF16 || (N % 16) != 0 || (K % 32) != 0) return MMD_OK;
+    if (!weight_packs(c->cfg.dtype, N, K)) return MMD_OK;
     int rc = dev_alloc(c, out, (size_t)N * K * 2, false); if (rc) return rc;
     HIPCHK(c, launch_pack_w(W, K, N, K, *out, c->stream));
     return MMD_OK;
 }
-// pack and, when every GEMM regime can run from the packed copy alone (N % 64 == 0 and K % 64 == 0: gemv16 / skinny / big
-// kernels), drop the row-major original: one copy of the weights in HBM (15.8 GB instead of 31 GB for the 7B model)
+// pack and, where the plan says so (weight_releases, model_plan.h), drop the row-major original
 static int pack_and_release(mmd_ctx* c, void** W, int N, int K, void** out) {
     int rc = make_packed(c, *W, N, K, out); if (rc) return rc;
-    if (*out && (N % 64) == 0 && (K % 64) == 0) {
+    if (weight_releases(c->cfg.dtype, N, K)) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         dev_free(c, *W); *W = nullptr;
     }
@@ -439,9 +403,9 @@ static int pack_and_release(mmd_ctx* c, void** W, int N, int K, void** out) {
 }
 
 // fp8 e4m3 copy of a row-major bf16 matrix (W is replaced by bf16(q)); out8 = fragment-major bytes for the streaming kernels, scale = [N] fp32
+// (the shape was checked with the plan: N % 16 == 0, K % 64 == 0)
 static int quantize_fp8(mmd_ctx* c, void* W, int N, int K, void** out8, float** scale) {
     *out8 = nullptr; *scale = nullptr;
-    if ((N % 16) != 0 || (K % 64) != 0) FAIL(c, MMD_EINVAL, "fp8 weights need N %% 16 == 0 and K %% 64 == 0 (got %d x %d)", N, K);
     uint8_t* q8 = nullptr;
     HIPCHK(c, hipMalloc((void**)&q8, (size_t)N * K));
     int rc = dev_alloc(c, (void**)scale, (size_t)N * sizeof(float), false); if (rc) { hipFree(q8); return rc; }
@@ -454,154 +418,110 @@ static int quantize_fp8(mmd_ctx* c, void* W, int N, int K, void** out8, float** 
     return MMD_OK;
 }
 
+// The one name-to-field map: the member a plan entry (model_plan.h) names, in the context, a decoder layer or a tower layer.
+typedef void** (*FieldOf)(void*);
+#define FIELD(T, m) {#m, [](void* o) -> void** { return (void**)&((T*)o)->m; }}
+static void** field_of(mmd_ctx* c, int scope, int layer, const std::string& name) {
+    static const std::unordered_map<std::string, FieldOf> ctx = {
+        FIELD(mmd_ctx, embed), FIELD(mmd_ctx, fnorm), FIELD(mmd_ctx, lm_head), FIELD(mmd_ctx, lm_head_p), FIELD(mmd_ctx, heads4), FIELD(mmd_ctx, patch_w), FIELD(mmd_ctx, patch_w_p),
+        FIELD(mmd_ctx, patch_b), FIELD(mmd_ctx, pos_emb), FIELD(mmd_ctx, cls_emb), FIELD(mmd_ctx, pre_w), FIELD(mmd_ctx, pre_b), FIELD(mmd_ctx, post_w), FIELD(mmd_ctx, post_b),
+        FIELD(mmd_ctx, p0w), FIELD(mmd_ctx, p0w_p), FIELD(mmd_ctx, p0b), FIELD(mmd_ctx, p2w), FIELD(mmd_ctx, p2w_p), FIELD(mmd_ctx, p2b), FIELD(mmd_ctx, hd_probe), FIELD(mmd_ctx, hd_wq),
+        FIELD(mmd_ctx, hd_bq), FIELD(mmd_ctx, hd_wkv), FIELD(mmd_ctx, hd_bkv), FIELD(mmd_ctx, hd_wo), FIELD(mmd_ctx, hd_bo), FIELD(mmd_ctx, hd_lnw), FIELD(mmd_ctx, hd_lnb),
+        FIELD(mmd_ctx, hd_w1), FIELD(mmd_ctx, hd_b1), FIELD(mmd_ctx, hd_w2), FIELD(mmd_ctx, hd_b2),
+        // workspaces
+        FIELD(mmd_ctx, v_col), FIELD(mmd_ctx, v_h), FIELD(mmd_ctx, v_xn), FIELD(mmd_ctx, v_h32), FIELD(mmd_ctx, v_qkv), FIELD(mmd_ctx, v_attn), FIELD(mmd_ctx, v_mlp), FIELD(mmd_ctx, v_patch),
+        FIELD(mmd_ctx, v_splitk_ws), FIELD(mmd_ctx, v_attn_ws), FIELD(mmd_ctx, hd_q), FIELD(mmd_ctx, hd_kv), FIELD(mmd_ctx, hd_a), FIELD(mmd_ctx, hd_h), FIELD(mmd_ctx, hd_n), FIELD(mmd_ctx, hd_m),
+        FIELD(mmd_ctx, v_p1), FIELD(mmd_ctx, v_p2), FIELD(mmd_ctx, l_h), FIELD(mmd_ctx, l_xn), FIELD(mmd_ctx, l_qkv), FIELD(mmd_ctx, l_q), FIELD(mmd_ctx, l_attn), FIELD(mmd_ctx, l_act),
+        FIELD(mmd_ctx, l_hid), FIELD(mmd_ctx, splitk_ws), FIELD(mmd_ctx, chain_ssq), FIELD(mmd_ctx, rope_tab), FIELD(mmd_ctx, attn_ws), FIELD(mmd_ctx, logits_ws), FIELD(mmd_ctx, heads_dev),
+        FIELD(mmd_ctx, rows_dev), FIELD(mmd_ctx, tok_dev), FIELD(mmd_ctx, argmax_scratch), FIELD(mmd_ctx, prev_dev), FIELD(mmd_ctx, gen_embed), FIELD(mmd_ctx, heads_host),
+        FIELD(mmd_ctx, rows_host), FIELD(mmd_ctx, tok_host), FIELD(mmd_ctx, step_host), FIELD(mmd_ctx, seg_host), FIELD(mmd_ctx, seg_dev), FIELD(mmd_ctx, step_dev)};
+    static const std::unordered_map<std::string, FieldOf> llm = {
+        FIELD(LlmLayer, ln1), FIELD(LlmLayer, ln2), FIELD(LlmLayer, wqkv), FIELD(LlmLayer, bqkv), FIELD(LlmLayer, wo), FIELD(LlmLayer, wgu), FIELD(LlmLayer, wdown),
+        FIELD(LlmLayer, wqkv_p), FIELD(LlmLayer, wo_p), FIELD(LlmLayer, wgu_p), FIELD(LlmLayer, wdown_p), FIELD(LlmLayer, wqkv_8), FIELD(LlmLayer, wo_8), FIELD(LlmLayer, wgu_8),
+        FIELD(LlmLayer, wdown_8), FIELD(LlmLayer, sqkv), FIELD(LlmLayer, so), FIELD(LlmLayer, sgu), FIELD(LlmLayer, sdown)};
+    static const std::unordered_map<std::string, FieldOf> vit = {
+        FIELD(VitLayer, ln1w), FIELD(VitLayer, ln1b), FIELD(VitLayer, wqkv), FIELD(VitLayer, bqkv), FIELD(VitLayer, wo), FIELD(VitLayer, bo), FIELD(VitLayer, ln2w), FIELD(VitLayer, ln2b),
+        FIELD(VitLayer, w1), FIELD(VitLayer, b1), FIELD(VitLayer, w2), FIELD(VitLayer, b2), FIELD(VitLayer, wqkv_p), FIELD(VitLayer, wo_p), FIELD(VitLayer, w1_p), FIELD(VitLayer, w2_p)};
+    const auto& map = scope == IN_LLM_LAYER ? llm : scope == IN_VIT_LAYER ? vit : ctx;
+    void* owner = scope == IN_LLM_LAYER ? (void*)&c->L[layer] : scope == IN_VIT_LAYER ? (void*)&c->VL[layer] : (void*)c;
+    return map.at(name)(owner);
+}
+#undef FIELD
+
+// the dimensions mmd_create copied from model_dims()
+static ModelDims dims_of(const mmd_ctx* c) {
+    ModelDims d; d.vit_grid = c->vit_grid; d.vit_tokens = c->vit_tokens; d.vit_seq = c->vit_seq; d.vit_kpad = c->vit_kpad; d.vit_ipad = c->vit_ipad; d.qkv_w = c->qkv_w;
+    return d;
+}
+
+// Checks the whole weight plan against what was loaded, then executes it entry by entry.  A refusal consumes nothing: load the missing tensor and call again.
 extern "C" int mmd_finalize_weights(mmd_ctx* c) {
     if (!c) return MMD_EINVAL;
     if (c->finalized) return MMD_OK;
     hipSetDevice(c->device);
     const mmd_config& g = c->cfg;
     const int dt = g.dtype; const size_t e = es(c);
-    const int H = g.hidden_size, I = g.intermediate_size, V = g.vocab_size, d = g.head_dim, nh = g.num_heads, nkv = g.num_kv_heads;
     hipStream_t st = c->stream;
-    if (!g.vision_only) {
-    { TAKE(t, "model.embed_tokens.weight", {V, H}); c->embed = t.p; }
-    { TAKE(t, "model.norm.weight", {H}); c->fnorm = t.p; }
-    { TAKE(t, "lm_head.weight", {V, H}); c->lm_head = t.p; int rc = make_packed(c, c->lm_head, V, H, &c->lm_head_p); if (rc) return rc; }
-    {
-        TAKE(a, "informative_head.weight", {2, H}); TAKE(b, "relevance_head.weight", {2, H});
-        int rc = dev_alloc(c, &c->heads4, 4 * H * e); if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->heads4, a.p, 2 * H * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((char*)c->heads4 + 2 * H * e, b.p, 2 * H * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st)); dev_free(c, a.p); dev_free(c, b.p);
-    }
-    c->L.resize(g.num_layers);
-    for (int i = 0; i < g.num_layers; ++i) {
-        std::string p = "model.layers." + std::to_string(i) + ".";
-        LlmLayer& L = c->L[i];
-        { TAKE(t, p + "input_layernorm.weight", {H}); L.ln1 = t.p; }
-        { TAKE(t, p + "post_attention_layernorm.weight", {H}); L.ln2 = t.p; }
-        TAKE(wq, p + "self_attn.q_proj.weight", {nh * d, H}); TAKE(wk, p + "self_attn.k_proj.weight", {nkv * d, H}); TAKE(wv, p + "self_attn.v_proj.weight", {nkv * d, H});
-        TAKE(bq, p + "self_attn.q_proj.bias", {nh * d}); TAKE(bk, p + "self_attn.k_proj.bias", {nkv * d}); TAKE(bv, p + "self_attn.v_proj.bias", {nkv * d});
-        int rc = dev_alloc(c, &L.wqkv, (size_t)c->qkv_w * H * e, false); if (rc) return rc;
-        rc = dev_alloc(c, &L.bqkv, (size_t)c->qkv_w * e, false); if (rc) return rc;
-        size_t oq = (size_t)nh * d, ok = (size_t)nkv * d;
-        HIPCHK(c, hipMemcpyAsync(L.wqkv, wq.p, oq * H * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((char*)L.wqkv + oq * H * e, wk.p, ok * H * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((char*)L.wqkv + (oq + ok) * H * e, wv.p, ok * H * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(L.bqkv, bq.p, oq * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((char*)L.bqkv + oq * e, bk.p, ok * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync((char*)L.bqkv + (oq + ok) * e, bv.p, ok * e, hipMemcpyDeviceToDevice, st));
-        { TAKE(t, p + "self_attn.o_proj.weight", {H, nh * d}); L.wo = t.p; }
-        TAKE(wg, p + "mlp.gate_proj.weight", {I, H}); TAKE(wu, p + "mlp.up_proj.weight", {I, H});
-        int64_t Ipad = round_up(I, 16);
-        rc = dev_alloc(c, &L.wgu, (size_t)2 * Ipad * H * e, false); if (rc) return rc;
-        HIPCHK(c, launch_interleave16(dt, wg.p, wu.p, L.wgu, I, H, st));
-        if (Ipad != I) FAIL(c, MMD_EINVAL, "intermediate_size must be a multiple of 16 (got %d)", I);
-        { TAKE(t, p + "mlp.down_proj.weight", {H, I}); L.wdown = t.p; }
-        if (g.weight_dtype == MMD_W_FP8_E4M3) {      // quantise the fused matrices (one scale per output channel), then pack both copies
-            if ((rc = quantize_fp8(c, L.wqkv, c->qkv_w, H, &L.wqkv_8, &L.sqkv)) || (rc = quantize_fp8(c, L.wo, H, nh * d, &L.wo_8, &L.so)) ||
-                (rc = quantize_fp8(c, L.wgu, 2 * I, H, &L.wgu_8, &L.sgu)) || (rc = quantize_fp8(c, L.wdown, H, I, &L.wdown_8, &L.sdown))) return rc;
-        }
-        rc = pack_and_release(c, &L.wqkv, c->qkv_w, H, &L.wqkv_p); if (rc) return rc;
-        rc = pack_and_release(c, &L.wo, H, nh * d, &L.wo_p); if (rc) return rc;
-        rc = pack_and_release(c, &L.wgu, 2 * I, H, &L.wgu_p); if (rc) return rc;
-        rc = pack_and_release(c, &L.wdown, H, I, &L.wdown_p); if (rc) return rc;
-        HIPCHK(c, hipStreamSynchronize(st));
-        dev_free(c, wq.p); dev_free(c, wk.p); dev_free(c, wv.p); dev_free(c, bq.p); dev_free(c, bk.p); dev_free(c, bv.p); dev_free(c, wg.p); dev_free(c, wu.p);
-    }
-    }
-    // vision tower
+    const WeightPlan plan = weight_plan(g, dims_of(c));
+    const WeightRefusal bad = weight_plan_check(plan, [&](const std::string& name) { auto it = c->raw.find(name); return it == c->raw.end() ? -1LL : (long long)it->second.numel; });
+    if (bad.rc) FAIL(c, bad.rc, "%s", bad.error.c_str());
     if (g.tower_f16) {
         // the checkpoint's bf16 tower parameters become IEEE half, as autocast casts them per op (exact for every normal value: 8 mantissa bits into 11);
         // padding / fusing / fragment packing below only move 2-byte elements
         for (auto& kv : c->raw)
             if (kv.first.rfind("vit.", 0) == 0) HIPCHK(c, launch_convert(kv.second.p, MMD_BF16, kv.second.p, MMD_F16, kv.second.numel, st));
     }
-    const int C = g.vit_hidden, CI = g.vit_intermediate, P = g.vit_patch, KP = 3 * P * P;
-    {
-        TAKE(w, "vit.embeddings.patch_embedding.weight", {C, 3, P, P});
-        int rc = dev_alloc(c, &c->patch_w, (size_t)C * c->vit_kpad * e, false); if (rc) return rc;
-        HIPCHK(c, launch_pad_cols(dt, w.p, C, KP, c->patch_w, c->vit_kpad, st));
-        rc = make_packed(c, c->patch_w, C, c->vit_kpad, &c->patch_w_p); if (rc) return rc;
-        HIPCHK(c, hipStreamSynchronize(st)); dev_free(c, w.p);
-    }
-    { TAKE(t, "vit.embeddings.patch_embedding.bias", {C}); c->patch_b = t.p; }
-    { TAKE(t, "vit.embeddings.position_embedding.weight", {c->vit_seq, C}); c->pos_emb = t.p; }
-    if (g.vit_class_token) { TAKE(t, "vit.embeddings.class_embedding", {C}); c->cls_emb = t.p; }
-    if (g.vit_pre_layernorm) { { TAKE(t, "vit.pre_layrnorm.weight", {C}); c->pre_w = t.p; } { TAKE(t, "vit.pre_layrnorm.bias", {C}); c->pre_b = t.p; } }
-    c->VL.resize(g.vit_layers);
-    for (int i = 0; i < g.vit_layers; ++i) {
-        std::string p = "vit.encoder.layers." + std::to_string(i) + ".";
-        VitLayer& L = c->VL[i];
-        { TAKE(t, p + "layer_norm1.weight", {C}); L.ln1w = t.p; } { TAKE(t, p + "layer_norm1.bias", {C}); L.ln1b = t.p; }
-        { TAKE(t, p + "layer_norm2.weight", {C}); L.ln2w = t.p; } { TAKE(t, p + "layer_norm2.bias", {C}); L.ln2b = t.p; }
-        TAKE(wq, p + "self_attn.q_proj.weight", {C, C}); TAKE(wk, p + "self_attn.k_proj.weight", {C, C}); TAKE(wv, p + "self_attn.v_proj.weight", {C, C});
-        TAKE(bq, p + "self_attn.q_proj.bias", {C}); TAKE(bk, p + "self_attn.k_proj.bias", {C}); TAKE(bv, p + "self_attn.v_proj.bias", {C});
-        int rc = dev_alloc(c, &L.wqkv, (size_t)3 * C * C * e, false); if (rc) return rc;
-        rc = dev_alloc(c, &L.bqkv, (size_t)3 * C * e, false); if (rc) return rc;
-        RawTensor* ws[3] = {&wq, &wk, &wv}; RawTensor* bs[3] = {&bq, &bk, &bv};
-        for (int j = 0; j < 3; ++j) {
-            HIPCHK(c, hipMemcpyAsync((char*)L.wqkv + (size_t)j * C * C * e, ws[j]->p, (size_t)C * C * e, hipMemcpyDeviceToDevice, st));
-            HIPCHK(c, hipMemcpyAsync((char*)L.bqkv + (size_t)j * C * e, bs[j]->p, (size_t)C * e, hipMemcpyDeviceToDevice, st));
+    c->L.resize(g.vision_only ? 0 : g.num_layers); c->VL.resize(g.vit_layers);
+    std::vector<void*> spent;          // sources copied from, freed at the next release point
+    for (const WeightEntry& w : plan.entries) {
+        std::vector<RawTensor> src;
+        for (const WeightSrc& s : w.src) { auto it = c->raw.find(s.name); src.push_back(it->second); c->raw.erase(it); }
+        void** dst = field_of(c, w.scope, w.layer, w.field);
+        const size_t row = (size_t)w.K * e;
+        int rc = MMD_OK;
+        if (w.op == W_ALIAS) *dst = src[0].p;
+        else {
+            rc = dev_alloc(c, dst, (size_t)w.N * row, w.zero); if (rc) return rc;
+            for (const RawTensor& t : src) spent.push_back(t.p);
         }
-        { TAKE(t, p + "self_attn.out_proj.weight", {C, C}); L.wo = t.p; } { TAKE(t, p + "self_attn.out_proj.bias", {C}); L.bo = t.p; }
-        TAKE(w1, p + "mlp.fc1.weight", {CI, C}); TAKE(b1, p + "mlp.fc1.bias", {CI}); TAKE(w2, p + "mlp.fc2.weight", {C, CI});
-        { TAKE(t, p + "mlp.fc2.bias", {C}); L.b2 = t.p; }
-        // fc1 rows / fc2 columns zero-padded to vit_ipad: gelu(0) = 0 keeps the result exact and K tile-aligned
-        rc = dev_alloc(c, &L.w1, (size_t)c->vit_ipad * C * e, true); if (rc) return rc;
-        rc = dev_alloc(c, &L.b1, (size_t)c->vit_ipad * e, true); if (rc) return rc;
-        rc = dev_alloc(c, &L.w2, (size_t)C * c->vit_ipad * e, false); if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(L.w1, w1.p, (size_t)CI * C * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(L.b1, b1.p, (size_t)CI * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, launch_pad_cols(dt, w2.p, C, CI, L.w2, c->vit_ipad, st));
-        rc = pack_and_release(c, &L.wqkv, 3 * C, C, &L.wqkv_p); if (rc) return rc;
-        rc = pack_and_release(c, &L.wo, C, C, &L.wo_p); if (rc) return rc;
-        rc = pack_and_release(c, &L.w1, c->vit_ipad, C, &L.w1_p); if (rc) return rc;
-        rc = pack_and_release(c, &L.w2, C, c->vit_ipad, &L.w2_p); if (rc) return rc;
-        HIPCHK(c, hipStreamSynchronize(st));
-        dev_free(c, wq.p); dev_free(c, wk.p); dev_free(c, wv.p); dev_free(c, bq.p); dev_free(c, bk.p); dev_free(c, bv.p);
-        dev_free(c, w1.p); dev_free(c, b1.p); dev_free(c, w2.p);
-    }
-    if (g.vit_post_layernorm) {
-        { TAKE(t, "vit.post_layernorm.weight", {C}); c->post_w = t.p; } { TAKE(t, "vit.post_layernorm.bias", {C}); c->post_b = t.p; }
-    }
-    if (!g.vision_only) {
-    { TAKE(t, "model.mm_projector.0.weight", {H, C}); c->p0w = t.p; } { TAKE(t, "model.mm_projector.0.bias", {H}); c->p0b = t.p; }
-    { TAKE(t, "model.mm_projector.2.weight", {H, H}); c->p2w = t.p; } { TAKE(t, "model.mm_projector.2.bias", {H}); c->p2b = t.p; }
-    { int rc = make_packed(c, c->p0w, H, C, &c->p0w_p); if (rc) return rc; rc = make_packed(c, c->p2w, H, H, &c->p2w_p); if (rc) return rc; }
-    }
-    if (g.vit_pool_head) {
-        // SiglipMultiheadAttentionPoolingHead: nn.MultiheadAttention keeps q/k/v stacked in in_proj_weight [3C, C]
-        { TAKE(t, "vit.head.probe", {C}); c->hd_probe = t.p; }
-        TAKE(wi, "vit.head.attention.in_proj_weight", {3 * C, C}); TAKE(bi, "vit.head.attention.in_proj_bias", {3 * C});
-        int rc;
-        if ((rc = dev_alloc(c, &c->hd_wq, (size_t)C * C * e, false)) || (rc = dev_alloc(c, &c->hd_bq, (size_t)C * e, false)) ||
-            (rc = dev_alloc(c, &c->hd_wkv, (size_t)2 * C * C * e, false)) || (rc = dev_alloc(c, &c->hd_bkv, (size_t)2 * C * e, false))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->hd_wq, wi.p, (size_t)C * C * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->hd_wkv, (char*)wi.p + (size_t)C * C * e, (size_t)2 * C * C * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->hd_bq, bi.p, (size_t)C * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->hd_bkv, (char*)bi.p + (size_t)C * e, (size_t)2 * C * e, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st)); dev_free(c, wi.p); dev_free(c, bi.p);
-        { TAKE(t, "vit.head.attention.out_proj.weight", {C, C}); c->hd_wo = t.p; } { TAKE(t, "vit.head.attention.out_proj.bias", {C}); c->hd_bo = t.p; }
-        { TAKE(t, "vit.head.layernorm.weight", {C}); c->hd_lnw = t.p; } { TAKE(t, "vit.head.layernorm.bias", {C}); c->hd_lnb = t.p; }
-        { TAKE(t, "vit.head.mlp.fc1.weight", {CI, C}); c->hd_w1 = t.p; } { TAKE(t, "vit.head.mlp.fc1.bias", {CI}); c->hd_b1 = t.p; }
-        { TAKE(t, "vit.head.mlp.fc2.weight", {C, CI}); c->hd_w2 = t.p; } { TAKE(t, "vit.head.mlp.fc2.bias", {C}); c->hd_b2 = t.p; }
+        if (w.op == W_CAT_ROWS || w.op == W_PAD_ROWS) {
+            char* at = (char*)*dst;
+            for (const RawTensor& t : src) { HIPCHK(c, hipMemcpyAsync(at, t.p, (size_t)t.numel * e, hipMemcpyDeviceToDevice, st)); at += (size_t)t.numel * e; }
+        } else if (w.op == W_INTERLEAVE16) {
+            HIPCHK(c, launch_interleave16(dt, src[0].p, src[1].p, *dst, (int)(w.N / 2), (int)w.K, st));
+        } else if (w.op == W_PAD_COLS) {
+            HIPCHK(c, launch_pad_cols(dt, src[0].p, (int)w.N, (int)(src[0].numel / w.N), *dst, (int)w.K, st));
+        } else if (w.op == W_SPLIT_QKV) {
+            void** dst2 = field_of(c, w.scope, w.layer, w.field2);
+            rc = dev_alloc(c, dst2, (size_t)w.N2 * row, false); if (rc) return rc;
+            HIPCHK(c, hipMemcpyAsync(*dst, src[0].p, (size_t)w.N * row, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(*dst2, (char*)src[0].p + (size_t)w.N * row, (size_t)w.N2 * row, hipMemcpyDeviceToDevice, st));
+        }
+        const std::string f = w.field;
+        if (w.fp8) {      // quantise the fused matrix (one scale per output channel), then pack both copies
+            rc = quantize_fp8(c, *dst, (int)w.N, (int)w.K, field_of(c, w.scope, w.layer, f + "_8"), (float**)field_of(c, w.scope, w.layer, "s" + f.substr(1))); if (rc) return rc;
+        }
+        if (w.pack == PACK_KEEP) rc = make_packed(c, *dst, (int)w.N, (int)w.K, field_of(c, w.scope, w.layer, f + "_p"));
+        else if (w.pack == PACK_RELEASE) rc = pack_and_release(c, dst, (int)w.N, (int)w.K, field_of(c, w.scope, w.layer, f + "_p"));
+        if (rc) return rc;
+        if (w.release) {
+            HIPCHK(c, hipStreamSynchronize(st));
+            for (void* p : spent) dev_free(c, p);
+            spent.clear();
+        }
     }
     // tensors that are on the checkpoint but not on the path (post_layernorm when unused, pooling head, ...) are dropped
     for (auto& kv : c->raw) dev_free(c, kv.second.p);
     c->raw.clear();
     if (!c->inv_freq_user && !g.vision_only) {
-        int n = d / 2;
+        const int d = g.head_dim, n = d / 2;
         std::vector<float> t(n);
         for (int i = 0; i < n; ++i) t[i] = (float)(1.0 / std::pow((double)g.rope_theta, (double)(2 * i) / (double)d));
         if (!c->inv_freq) { int rc = dev_alloc(c, (void**)&c->inv_freq, sizeof(float) * n); if (rc) return rc; }
         HIPCHK(c, hipMemcpyAsync(c->inv_freq, t.data(), sizeof(float) * n, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipStreamSynchronize(st));
     }
-    size_t wb = 0; { size_t fr = 0, tot = 0; (void)fr; (void)tot; }
-    wb = ((size_t)2 * V * H + (size_t)g.num_layers * ((size_t)c->qkv_w * H + (size_t)H * nh * d + (size_t)3 * I * H) +
-          (size_t)g.vit_layers * ((size_t)4 * C * C + (size_t)2 * c->vit_ipad * C) + (size_t)C * c->vit_kpad + (size_t)H * C + (size_t)H * H) * e;
-    if (g.weight_dtype == MMD_W_FP8_E4M3) wb += (size_t)g.num_layers * ((size_t)c->qkv_w * H + (size_t)H * nh * d + (size_t)3 * I * H);     // the 1-byte copies
-    c->weight_bytes = (int64_t)wb;
+    c->weight_bytes = plan.weight_bytes(g);
     int rc = alloc_workspaces(c);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
@@ -609,50 +529,14 @@ extern "C" int mmd_finalize_weights(mmd_ctx* c) {
     return MMD_OK;
 }
 
-// fp32 split-K slab workspace of the LLM side: 64 MB; 192 MB for a model built for several streams' merged chunks (three slabs of a 2548-row down_proj are 110 MB)
-static size_t splitk_ws_size(const mmd_config& g) { return (size_t)(g.max_step_tokens > 2048 ? 192 : 64) << 20; }
-
 static int alloc_workspaces(mmd_ctx* c) {
-    const mmd_config& g = c->cfg; const size_t e = es(c);
-    const int C = g.vit_hidden, H = g.hidden_size;
-    int64_t Mv = round_up((int64_t)g.max_vit_batch * c->vit_seq, 128);
-    int rc;
-#define WS(ptr, bytes) rc = dev_alloc(c, (void**)&(ptr), (bytes)); if (rc) return rc;
-    WS(c->v_col, (size_t)Mv * c->vit_kpad * e); WS(c->v_h, (size_t)Mv * C * e); WS(c->v_xn, (size_t)Mv * C * e);
-    if (g.tower_f16 == 1) {
-        const int pout_ = (c->vit_grid + g.pool_stride - 1) / g.pool_stride;
-        c->v_h32_rows = Mv; WS(c->v_h32, (size_t)(Mv + (int64_t)g.max_vit_batch * 4 * pout_ * pout_) * C * sizeof(float));
+    const WorkspacePlan p = workspace_plan(c->cfg, dims_of(c), sizeof(StepState));
+    for (const WorkspaceEntry& w : p.entries) {
+        void** dst = field_of(c, IN_CTX, 0, w.field);
+        int rc = w.pinned ? host_alloc(c, dst, w.bytes) : dev_alloc(c, dst, w.bytes); if (rc) return rc;
     }
-    WS(c->v_qkv, (size_t)Mv * 3 * C * e); WS(c->v_attn, (size_t)Mv * C * e); WS(c->v_mlp, (size_t)round_up(Mv, 16) * c->vit_ipad * e);          // (rows padded to 16: the piece-major form of fc1's output holds whole 16-row pieces)
-    if (g.vit_class_token) { WS(c->v_patch, (size_t)Mv * C * e); }
-    c->v_splitk_bytes = (size_t)32 << 20; WS(c->v_splitk_ws, c->v_splitk_bytes);
-    c->v_attn_bytes = (size_t)32 << 20; WS(c->v_attn_ws, c->v_attn_bytes);
-    if (g.vit_pool_head) {
-        const size_t Bm = (size_t)g.max_vit_batch;
-        WS(c->hd_q, (size_t)C * e); WS(c->hd_kv, (size_t)Mv * 2 * C * e); WS(c->hd_a, Bm * C * e); WS(c->hd_h, Bm * C * e); WS(c->hd_n, Bm * C * e);
-        WS(c->hd_m, Bm * g.vit_intermediate * e);
-    }
-    if (g.vision_only) return MMD_OK;
-    WS(c->v_p1, (size_t)Mv * H * e); WS(c->v_p2, (size_t)Mv * H * e);
-    int64_t S = round_up(g.max_step_tokens, 128);
-    WS(c->l_h, (size_t)S * H * e); WS(c->l_xn, (size_t)S * H * e); WS(c->l_qkv, (size_t)S * c->qkv_w * e);
-    WS(c->l_q, (size_t)S * g.num_heads * g.head_dim * e); WS(c->l_attn, (size_t)S * g.num_heads * g.head_dim * e);
-    WS(c->l_act, (size_t)round_up(S, 16) * g.intermediate_size * e); WS(c->l_hid, (size_t)S * H * e);          // (l_act rows padded to 16: whole pieces in its piece-major form)
-    c->splitk_bytes = splitk_ws_size(g); WS(c->splitk_ws, c->splitk_bytes);
-    WS(c->chain_ssq, (size_t)GEMV_CHAIN_ROWS * GEMV_SSQ_STRIDE * sizeof(float)); WS(c->rope_tab, (size_t)S * 64 * 2 * sizeof(float));          // (cos, sin) of a step's positions: decode steps and, since round 3, chunks
-    c->attn_bytes = (size_t)128 << 20; WS(c->attn_ws, c->attn_bytes);
-    WS(c->logits_ws, (size_t)g.vocab_size * sizeof(float));
-    WS(c->heads_dev, (size_t)S * 4 * sizeof(float)); WS(c->rows_dev, (size_t)S * sizeof(int32_t));
-    WS(c->tok_dev, 64); WS(c->argmax_scratch, 1024); c->prev_cap = 16384; WS(c->prev_dev, (size_t)c->prev_cap * sizeof(int64_t));
-    WS(c->gen_embed, (size_t)H * e);
-#undef WS
-    HIPCHK(c, hipHostMalloc((void**)&c->heads_host, (size_t)S * 4 * sizeof(float)));
-    HIPCHK(c, hipHostMalloc((void**)&c->rows_host, (size_t)S * sizeof(int32_t)));
-    HIPCHK(c, hipHostMalloc((void**)&c->tok_host, 64));
-    HIPCHK(c, hipHostMalloc((void**)&c->step_host, sizeof(StepState)));
-    HIPCHK(c, hipHostMalloc((void**)&c->seg_host, 8 * STEP_MULTI_ATTN_MAX_RUN * sizeof(StepState)));
-    rc = dev_alloc(c, (void**)&c->seg_dev, 8 * STEP_MULTI_ATTN_MAX_RUN * sizeof(StepState)); if (rc) return rc;
-    rc = dev_alloc(c, (void**)&c->step_dev, sizeof(StepState)); if (rc) return rc;
+    c->v_splitk_bytes = p.v_splitk_bytes; c->v_attn_bytes = p.v_attn_bytes; c->v_h32_rows = p.v_h32_rows;
+    if (!c->cfg.vision_only) { c->splitk_bytes = p.splitk_bytes; c->attn_bytes = p.attn_bytes; c->prev_cap = p.prev_cap; }
     return MMD_OK;
 }
 
@@ -1596,7 +1480,7 @@ static void cons_fill_row(ConstraintRow& r, const ConsSet& s, const int32_t* ids
 static int cons_reserve(mmd_ctx* c) {
     if (c->cons_bias_dev) return MMD_OK;
     int rc = dev_alloc(c, (void**)&c->cons_rows_dev, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)); if (rc) return rc;
-    HIPCHK(c, hipHostMalloc((void**)&c->cons_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)));
+    rc = host_alloc(c, (void**)&c->cons_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)); if (rc) return rc;
     rc = dev_alloc(c, (void**)&c->cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t)); if (rc) return rc;
     return dev_alloc(c, (void**)&c->cons_bias_dev, CONS_MAX_TABLE * sizeof(float));
 }
@@ -1622,7 +1506,7 @@ static void fill_sample_row(SampleRow& r, const SampleArgs& a, const int64_t* pr
 static int sample_reserve(mmd_ctx* c) {
     if (c->samp_scratch) return MMD_OK;
     int rc = dev_alloc(c, (void**)&c->samp_rows_dev, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(SampleRow)); if (rc) return rc;
-    HIPCHK(c, hipHostMalloc((void**)&c->samp_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(SampleRow)));
+    rc = host_alloc(c, (void**)&c->samp_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(SampleRow)); if (rc) return rc;
     return dev_alloc(c, &c->samp_scratch, sample_topkp_scratch_bytes(c->cfg.vocab_size, MMD_ROUND_MAX_SAMPLERS, true), false);
 }
 static int check_sampling(mmd_ctx* c, float temperature, int top_k, float top_p) {
@@ -1799,7 +1683,7 @@ extern "C" int mmd_sampler_logprobs_read(mmd_sampler* sp, float* logprob_host, f
 static int round_record_reserve(mmd_ctx* c) {
     if (c->round_lp_scratch) return MMD_OK;
     int rc = dev_alloc(c, (void**)&c->round_lp_rows_dev, MMD_ROUND_MAX_SAMPLERS * sizeof(LogprobRow)); if (rc) return rc;
-    HIPCHK(c, hipHostMalloc((void**)&c->round_lp_rows_host, MMD_ROUND_MAX_SAMPLERS * sizeof(LogprobRow)));
+    rc = host_alloc(c, (void**)&c->round_lp_rows_host, MMD_ROUND_MAX_SAMPLERS * sizeof(LogprobRow)); if (rc) return rc;
     return dev_alloc(c, &c->round_lp_scratch, logprob_scratch_bytes(MMD_ROUND_MAX_SAMPLERS), false);
 }
 extern "C" int mmd_sampler_lane(const mmd_sampler* sp) { return sp ? (int)sp->lane : MMD_EINVAL; }
@@ -1879,7 +1763,7 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         rc = dev_alloc(c, &c->round_hidden, (size_t)MMD_ROUND_MAX_SAMPLERS * H * e); if (rc) return rc;
         if (!c->round_scratch) { rc = dev_alloc(c, &c->round_scratch, sample_batch_scratch_bytes()); if (rc) return rc; }          // (mmd_op_argmax may have brought it)
         rc = dev_alloc(c, (void**)&c->round_toks_dev, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)); if (rc) return rc;
-        HIPCHK(c, hipHostMalloc((void**)&c->round_toks_host, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)));
+        rc = host_alloc(c, (void**)&c->round_toks_host, MMD_ROUND_MAX_SAMPLERS * sizeof(int64_t)); if (rc) return rc;
     }
     int32_t need[STEP_NEED_MAX]; const int n_need = build_need_list(head_rows, n_head_rows, sample_row, n_sample, need);          // the heads' rows first, then the sampling rows
     rc = llm_step_segs(c, segs.data(), n_segs, c->l_h, S, nullptr, nullptr, n_need ? need : nullptr, n_need); if (rc) return rc;
@@ -2457,7 +2341,7 @@ extern "C" int mmd_op_gemm(mmd_ctx* c, const void* X, const void* W, const void*
                            int out_f32, int variant) {
     if (!c) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    if (!c->splitk_ws) { c->splitk_bytes = model_splitk_bytes(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
     int NO = epi == EPI_SWIGLU ? N / 2 : N;
     void* Wp = nullptr;
     // the model holds every matrix in both layouts (or packed only): give the dispatcher the same choice, variant 0 included
@@ -2473,7 +2357,7 @@ extern "C" int mmd_op_lm_nll(mmd_ctx* c, const void* X, const void* W, int M, in
     if (M == 0) return MMD_OK;
     if (!X || !W || !labels || !nll_out) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    if (!c->splitk_ws) { c->splitk_bytes = model_splitk_bytes(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
     void* Wp = nullptr;
     if (M <= 64 && (chunk_cols == 0 || chunk_cols >= V)) { int rc = make_packed(c, W, V, K, &Wp); if (rc) return rc; }
     int rc = lm_nll_run(c, X, W, Wp, M, V, K, labels, ignore_index, chunk_cols, nll_out, lse_out);
@@ -2512,7 +2396,7 @@ extern "C" int mmd_op_gemm_w8(mmd_ctx* c, const void* X, const void* Wq, const u
     if (!c || !X || !Wq || !q8 || !scale || !Y) return MMD_EINVAL;
     if (c->cfg.dtype != MMD_BF16 || (N % 16) != 0 || (K % 64) != 0) FAIL(c, MMD_EINVAL, "mmd_op_gemm_w8: bf16 context, N %% 16 == 0, K %% 64 == 0");
     hipSetDevice(c->device);
-    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    if (!c->splitk_ws) { c->splitk_bytes = model_splitk_bytes(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
     void *Wp = nullptr, *Wp8 = nullptr;
     int rc = make_packed(c, Wq, N, K, &Wp); if (rc) return rc;
     rc = dev_alloc(c, &Wp8, (size_t)N * K, false); if (rc) return rc;
@@ -2529,7 +2413,7 @@ extern "C" int mmd_op_gemm_pair(mmd_ctx* c, const void* X, const void* W1, const
                                 int piece_major, int* used_pm_out) {
     if (!c || !X || !W1 || !W2 || !Y) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    if (!c->splitk_ws) { c->splitk_bytes = model_splitk_bytes(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
     const int T = epi1 == EPI_SWIGLU ? N1 / 2 : N1;
     void *W1p = nullptr, *W2p = nullptr, *mid = nullptr; int rc;
     if ((rc = make_packed(c, W1, N1, K1, &W1p)) || (rc = make_packed(c, W2, N2, T, &W2p)) || (rc = dev_alloc(c, &mid, (size_t)round_up(M, 16) * T * es(c)))) return rc;
@@ -2558,7 +2442,7 @@ extern "C" int mmd_op_select_last_plan(mmd_ctx* c, int* out) { if (!c || !out) r
 extern "C" int mmd_op_gemm_bench(mmd_ctx* c, int M, int N, int K, int epi, int variant, int iters, float* avg_ms_out, const void* Xin, const void* Win) {
     if (!c || !avg_ms_out || iters <= 0) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    if (!c->splitk_ws) { c->splitk_bytes = model_splitk_bytes(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
     const size_t e = es(c);
     int NO = epi == EPI_SWIGLU ? N / 2 : N;
     void *X = nullptr, *W = nullptr, *Y = nullptr, *R = nullptr, *Wp = nullptr;
@@ -2639,7 +2523,7 @@ extern "C" int mmd_op_kv_write(mmd_ctx* c, int writer, const void* src, int n_sl
         if (e == hipSuccess) e = launch_rope_table(tab, S, half, freq, pos0, c->stream);
     }
     // (the split-KV workspace of a context that never ran a step: 128 MiB as in mmd_op_attention, an arbitrary test size that stays with the context -- not the model's own sizing)
-    if (e == hipSuccess && writer == 4 && !c->attn_ws) { c->attn_bytes = (size_t)128 << 20; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return done(rc); }
+    if (e == hipSuccess && writer == 4 && !c->attn_ws) { c->attn_bytes = MODEL_ATTN_WS_BYTES; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return done(rc); }
     if (e == hipSuccess) {
         if (writer <= 1) e = launch_rope_append(c->cfg.dtype, src, S, nh, nkv, d, freq, pos0, q_out, Kc, Vc, cap, writer, c->stream);
         else if (writer == 2) e = launch_rope_append_chunk(src, S, nh, nkv, tab, pos0, q_out, Kc, Vc, cap, c->stream);
@@ -2686,7 +2570,7 @@ extern "C" int mmd_op_gemv_chain(mmd_ctx* c, int role, const void* X, const void
     if (M < 1 || M > 16 || N < 16 || (N % 16) != 0 || K < 32 || (K % (q8 ? 64 : 32)) != 0 || (epi == EPI_SWIGLU && (N % 32) != 0))
         FAIL(c, MMD_EINVAL, "gemv_chain: 1 <= M <= 16, N %% 16 == 0 (SwiGLU: %% 32), K %% 32 == 0 (fp8: %% 64); got %d x %d x %d", M, N, K);
     hipSetDevice(c->device);
-    if (!c->splitk_ws) { c->splitk_bytes = splitk_ws_size(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
+    if (!c->splitk_ws) { c->splitk_bytes = model_splitk_bytes(c->cfg); int rc = dev_alloc(c, (void**)&c->splitk_ws, c->splitk_bytes); if (rc) return rc; }
     GemvChain ch;
     if (role == GEMV_PRODUCER) { ch.fin_h = h; ch.fin_ssq = ssq; }
     else { ch.xn_h = h; ch.xn_gamma = gamma; ch.xn_ssq = ssq; ch.xn_eps = eps; }
@@ -2804,7 +2688,7 @@ extern "C" int mmd_op_rope_append(mmd_ctx* c, void* qkv, int S, int nh, int nkv,
 extern "C" int mmd_op_attention(mmd_ctx* c, const void* q, const void* Kc, const void* Vc, void* out, int S, int nh, int nkv, int d, int64_t n_ctx,
                                 int64_t cap, int causal, int variant) {
     if (!c) return MMD_EINVAL; hipSetDevice(c->device);
-    if (!c->attn_ws) { c->attn_bytes = (size_t)128 << 20; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return rc; }
+    if (!c->attn_ws) { c->attn_bytes = MODEL_ATTN_WS_BYTES; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return rc; }
     AttnArgs a; memset(&a, 0, sizeof(a));
     a.q = q; a.ldq = (int64_t)nh * d; a.K = Kc; a.V = Vc; a.k_hs = cap * d; a.k_ts = d; a.v_hs = cap * d; a.v_ts = d; a.out = out; a.ldo = (int64_t)nh * d;
     a.S = S; a.nh = nh; a.nkv = nkv; a.d = d; a.n_ctx = n_ctx; a.causal = causal; a.batch = 1; a.ws = c->attn_ws; a.ws_bytes = c->attn_bytes; a.variant = variant;
@@ -2825,7 +2709,7 @@ extern "C" int mmd_op_attention(mmd_ctx* c, const void* q, const void* Kc, const
 extern "C" int mmd_op_attention_bench(mmd_ctx* c, int S, int nh, int nkv, int d, int64_t n_ctx, int variant, int iters, float* avg_ms_out) {
     if (!c || !avg_ms_out || iters <= 0) return MMD_EINVAL;
     hipSetDevice(c->device);
-    if (!c->attn_ws) { c->attn_bytes = (size_t)128 << 20; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return rc; }
+    if (!c->attn_ws) { c->attn_bytes = MODEL_ATTN_WS_BYTES; int rc = dev_alloc(c, (void**)&c->attn_ws, c->attn_bytes); if (rc) return rc; }
     const size_t e = es(c);
     int64_t cap = round_up(n_ctx + S, 64);
     void *q = nullptr, *K = nullptr, *V = nullptr, *o = nullptr; int rc;
