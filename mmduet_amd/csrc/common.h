@@ -6,6 +6,7 @@
 #include "../../include/mmduet.h"
 #include "gemm_plan.h"          // GemmArgs, GemmPlan and the dispatch decision (host-only: no GPU header), cdiv / round_up, MMD_F16
 #include "attn_plan.h"          // AttnArgs, AttnPlan and the attention dispatch decision (host-only too)
+#include "response_plan.h"      // CONS_MAX_TABLE / CONS_MAX_EOS / LP_MAX_TOP: the limits of a response's constraint set and records (host-only too)
 
 typedef uint16_t bf16_t;   // raw bfloat16 storage
 
@@ -173,7 +174,6 @@ constexpr int SMP_MAX_SLICES = 64;
 // constrained decoding (DESIGN.md "Constraints"): one ConstraintRow per logits row, in DEVICE memory beside its SampleRow.  The table is (id, bias) sorted by id, ids unique,
 // bias finite or -inf (= suppressed);  z_i = mask_i(pen(l_i + b_i)) / T, mask = -inf for a suppressed id and -- while fewer than min_new tokens have been returned -- for the
 // EOS ids.  step = tokens returned so far in this response; step_ptr (the captured step: &StepState::step) overrides it.  A row with n = 0, n_eos = 0 is unconstrained.
-constexpr int CONS_MAX_TABLE = 256, CONS_MAX_EOS = 8;
 struct ConstraintRow {
     const int32_t* ids; const float* bias; const int* step_ptr;
     long long eos[CONS_MAX_EOS];
@@ -185,7 +185,6 @@ __host__ __device__ inline bool cons_is_eos(const ConstraintRow& c, long long t)
 // beyond cap is not written), for the token toks[r]; rec == null: nothing is recorded.  With `rows` (mmd_round_multi: every row belongs to another sampler) row r has a
 // destination of its own, in DEVICE memory: rows[r].rec[rows[r].slot] with its own top_n, nothing when rows[r].rec is null or the slot is beyond rows[r].cap; rec / cap / dyn /
 // idx0 / top_n of the LogprobOut are then unused.
-constexpr int LP_MAX_TOP = 8;
 struct LogprobRec { float lp, slp; float top_lp[LP_MAX_TOP]; int top_id[LP_MAX_TOP]; };
 struct LogprobRow { LogprobRec* rec; int slot, cap, top_n; };
 struct LogprobOut { LogprobRec* rec; int cap; const StepState* dyn; int idx0; const int64_t* toks; int top_n; const LogprobRow* rows = nullptr; };

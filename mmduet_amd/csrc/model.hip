@@ -43,8 +43,15 @@ enum { SELECT_OF_OP = 0, SELECT_OF_GENERATE = 1, SELECT_OF_ROUND = 2 };
 constexpr int SELECT_LAST_FIELDS = SELECT_PLAN_FIELDS + 1 + GENERATE_PLAN_FIELDS;          // (a RoundBlocks is the shorter tail)
 static_assert(ROUND_BLOCKS_FIELDS <= GENERATE_PLAN_FIELDS, "the tail of select_last holds either");
 
-// a validated constraint set on the host (DESIGN.md "Constraints"): the table sorted by id, ids unique
-struct ConsSet { bool on = false; int n = 0, n_eos = 0, min_new = 0; int64_t eos[CONS_MAX_EOS] = {}; int32_t ids[CONS_MAX_TABLE] = {}; float bias[CONS_MAX_TABLE] = {}; };
+// The state of a response in progress (response_plan.h holds its rules, DESIGN.md "Response state" who owns what).  The context has one for its generate calls, every sampler
+// one for its rounds; the helpers below (response_*) are the only code that sizes, fills or frees these buffers.
+struct Response {
+    int64_t* prev_dev = nullptr; int prev_cap = 0; float penalty = 0.f;          // repetition-penalty list (device), its capacity, the penalty (0: off)
+    ConsSet cons; int32_t* cons_ids_dev = nullptr; float* cons_bias_dev = nullptr;          // the validated set and its table on the device (allocated with the first set that is on)
+    int lp_top = -1, lp_cap = 0; LogprobRec* lp_rec = nullptr;          // log-probabilities: the setting (-1 off), the device records of the current response
+    ResponseCount count;
+    bool zero_fill = false;            // the context's buffers are zero-filled when they are (re)placed, as its workspaces are; a sampler's never were
+};
 
 // one captured decode step: the instantiated graph, its source, and the (penalty, EOS, filter selection) it was captured for
 struct DecodeGraph {
@@ -99,7 +106,7 @@ struct mmd_ctx {
     int32_t* rows_dev = 0;
     int64_t* tok_dev = 0;              // sampled token id
     void* argmax_scratch = 0;          // candidates of the two-stage argmax
-    int64_t* prev_dev = 0; int prev_cap = 0;
+    Response resp;                     // of the generate calls; resp.prev_dev is the workspace entry "prev_dev" (model_plan.h)
     void* gen_embed = 0;               // [1,H]
     // pinned staging
     float* heads_host = 0; int32_t* rows_host = 0; int64_t* tok_host = 0;
@@ -137,13 +144,13 @@ struct mmd_ctx {
     // for MMD_ROUND_MAX_SAMPLERS rows
     SampleRow* samp_rows_dev = nullptr; SampleRow* samp_rows_host = nullptr; void* samp_scratch = nullptr;
     uint32_t sample_lane = 0; uint32_t n_samplers = 0;
-    // log-probabilities of generated tokens (mmd_set_generate_logprobs; allocated at their first use): lp_top = the setting (-1 off), lp_rec [lp_cap] the device records of the
-    // most recent generate call, lp_n of them valid with lp_call_top alternatives each
-    int lp_top = -1, lp_cap = 0, lp_n = 0, lp_call_top = -1; LogprobRec* lp_rec = nullptr; void* lp_scratch = nullptr;
-    // constrained decoding (mmd_set_generate_constraints; allocated at its first use): the validated set, the key the captured steps carry for it (0 off, 1 on: a call that
-    // sets, generates and clears finds its step again), row descriptors on the device ([0] the generate calls', [1..] a round's) with their pinned staging, and descriptor 0's table
-    ConsSet cons; uint32_t cons_gen = 0;
-    ConstraintRow* cons_rows_dev = nullptr; ConstraintRow* cons_rows_host = nullptr; int32_t* cons_ids_dev = nullptr; float* cons_bias_dev = nullptr;
+    // log-probabilities of generated tokens (mmd_set_generate_logprobs): resp.count.lp_n records of the most recent generate call are valid, with lp_call_top alternatives
+    // each (resp.lp_top is the setting for the next call); the record kernels' scratch for one row (allocated at its first use)
+    int lp_call_top = -1; void* lp_scratch = nullptr;
+    // constrained decoding (allocated at its first use): the key the captured steps carry for resp.cons (0 off, 1 on: a call that sets, generates and clears finds its step
+    // again), row descriptors on the device ([0] the generate calls', [1..] a round's) with their pinned staging
+    uint32_t cons_gen = 0;
+    ConstraintRow* cons_rows_dev = nullptr; ConstraintRow* cons_rows_host = nullptr;
     Prof prof;
 };
 
@@ -187,6 +194,63 @@ static void dev_free(mmd_ctx* c, void* p) {
     if (!p) return;
     for (size_t i = 0; i < c->allocs.size(); ++i) if (c->allocs[i] == p) { c->allocs[i] = c->allocs.back(); c->allocs.pop_back(); break; }
     hipFree(p);
+}
+
+// ---- a response's buffers (response_plan.h: the rules; struct Response: the fields) ----------------------------------------------------------------------------
+// `buf` [cap entries of elem bytes] must hold `need`: grown by doubling behind a drained stream (a step or a round in flight may still read or write the old buffer).
+// *moved is set when the old buffer is gone, whatever the answer -- the context drops its captured decode steps, which hold the pointer; a sampler has nothing to drop.
+static int response_grow(mmd_ctx* c, const Response& r, void** buf, int* cap, int need, int first, size_t elem, bool* moved) {
+    const int ncap = grow_capacity(*cap, need, first);
+    if (ncap == *cap) return MMD_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (moved) *moved = true;
+    dev_free(c, *buf); *buf = nullptr; *cap = 0;
+    int rc = dev_alloc(c, buf, (size_t)ncap * elem, r.zero_fill); if (rc) return rc;
+    *cap = ncap;
+    return MMD_OK;
+}
+static int response_reserve_list(mmd_ctx* c, Response& r, int need, int first, bool* moved = nullptr) { return response_grow(c, r, (void**)&r.prev_dev, &r.prev_cap, need, first, sizeof(int64_t), moved); }
+static int response_reserve_records(mmd_ctx* c, Response& r, int need, int first, bool* moved = nullptr) { return response_grow(c, r, (void**)&r.lp_rec, &r.lp_cap, need, first, sizeof(LogprobRec), moved); }
+// a validated set becomes the response's: its table goes to the device first.  The stream is drained before the upload (a step in flight may read the old values), then the
+// copy is synchronous -- no staging of pageable memory behind the caller's back
+static int response_set_constraints(mmd_ctx* c, Response& r, const ConsSet& s) {
+    if (s.on && !r.cons_bias_dev) {
+        int rc = dev_alloc(c, (void**)&r.cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t), r.zero_fill); if (rc) return rc;
+        rc = dev_alloc(c, (void**)&r.cons_bias_dev, CONS_MAX_TABLE * sizeof(float), r.zero_fill); if (rc) return rc;
+    }
+    if (s.on && s.n > 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(r.cons_ids_dev, s.ids, sizeof(int32_t) * s.n, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(r.cons_bias_dev, s.bias, sizeof(float) * s.n, hipMemcpyHostToDevice));
+    }
+    r.cons = s;
+    return MMD_OK;
+}
+// the record option of a response: -1 off, else the alternatives of a record.  (When a switch takes hold is its owner's business: a sampler switches at a response boundary
+// and reserves at once, the context's next generate call takes the setting.)
+static int response_lp_top_checked(mmd_ctx* c, int top_n) {
+    if (top_n < -1 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "log-probability alternatives: -1 (off) or 0..%d, got %d", LP_MAX_TOP, top_n);
+    return MMD_OK;
+}
+static void unpack_logprobs(const LogprobRec* h, int n, int top_n, float* lp, float* slp, int64_t* top_ids, float* top_lp) {
+    for (int i = 0; i < n; ++i) {
+        if (lp) lp[i] = h[i].lp;
+        if (slp) slp[i] = h[i].slp;
+        for (int j = 0; j < top_n; ++j) { if (top_ids) top_ids[(size_t)i * top_n + j] = h[i].top_id[j]; if (top_lp) top_lp[(size_t)i * top_n + j] = h[i].top_lp[j]; }
+    }
+}
+// the first n records, written with top_n alternatives each, into the caller's arrays (any of them may be null)
+static int response_read_records(mmd_ctx* c, const Response& r, int n, int top_n, float* lp, float* slp, int64_t* top_ids, float* top_lp, int cap_tokens) {
+    if (cap_tokens < n) FAIL(c, MMD_ERANGE, "%d records, room for %d", n, cap_tokens);
+    std::vector<LogprobRec> h((size_t)n);
+    HIPCHK(c, hipMemcpyAsync(h.data(), r.lp_rec, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unpack_logprobs(h.data(), n, top_n, lp, slp, top_ids, top_lp);
+    return MMD_OK;
+}
+static void response_release(mmd_ctx* c, Response& r) {
+    dev_free(c, r.prev_dev); dev_free(c, r.cons_ids_dev); dev_free(c, r.cons_bias_dev); dev_free(c, r.lp_rec);
+    r = Response{};
 }
 
 // ---- profiling ---------------------------------------------------------------------------------------------------
@@ -276,7 +340,7 @@ extern "C" int mmd_create(const mmd_config* cfg, int device, mmd_ctx** out) {
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { g_create_error = std::string("hipSetDevice: ") + hipGetErrorString(e); return MMD_EHIP; }
     mmd_ctx* c = new mmd_ctx();
-    c->cfg = *cfg; c->device = device;
+    c->cfg = *cfg; c->device = device; c->resp.zero_fill = true;
     e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete c; return MMD_EHIP; }
     c->stream = c->own_stream;
@@ -433,7 +497,7 @@ static void** field_of(mmd_ctx* c, int scope, int layer, const std::string& name
         FIELD(mmd_ctx, v_splitk_ws), FIELD(mmd_ctx, v_attn_ws), FIELD(mmd_ctx, hd_q), FIELD(mmd_ctx, hd_kv), FIELD(mmd_ctx, hd_a), FIELD(mmd_ctx, hd_h), FIELD(mmd_ctx, hd_n), FIELD(mmd_ctx, hd_m),
         FIELD(mmd_ctx, v_p1), FIELD(mmd_ctx, v_p2), FIELD(mmd_ctx, l_h), FIELD(mmd_ctx, l_xn), FIELD(mmd_ctx, l_qkv), FIELD(mmd_ctx, l_q), FIELD(mmd_ctx, l_attn), FIELD(mmd_ctx, l_act),
         FIELD(mmd_ctx, l_hid), FIELD(mmd_ctx, splitk_ws), FIELD(mmd_ctx, chain_ssq), FIELD(mmd_ctx, rope_tab), FIELD(mmd_ctx, attn_ws), FIELD(mmd_ctx, logits_ws), FIELD(mmd_ctx, heads_dev),
-        FIELD(mmd_ctx, rows_dev), FIELD(mmd_ctx, tok_dev), FIELD(mmd_ctx, argmax_scratch), FIELD(mmd_ctx, prev_dev), FIELD(mmd_ctx, gen_embed), FIELD(mmd_ctx, heads_host),
+        FIELD(mmd_ctx, rows_dev), FIELD(mmd_ctx, tok_dev), FIELD(mmd_ctx, argmax_scratch), {"prev_dev", [](void* o) -> void** { return (void**)&((mmd_ctx*)o)->resp.prev_dev; }}, FIELD(mmd_ctx, gen_embed), FIELD(mmd_ctx, heads_host),
         FIELD(mmd_ctx, rows_host), FIELD(mmd_ctx, tok_host), FIELD(mmd_ctx, step_host), FIELD(mmd_ctx, seg_host), FIELD(mmd_ctx, seg_dev), FIELD(mmd_ctx, step_dev)};
     static const std::unordered_map<std::string, FieldOf> llm = {
         FIELD(LlmLayer, ln1), FIELD(LlmLayer, ln2), FIELD(LlmLayer, wqkv), FIELD(LlmLayer, bqkv), FIELD(LlmLayer, wo), FIELD(LlmLayer, wgu), FIELD(LlmLayer, wdown),
@@ -536,7 +600,7 @@ static int alloc_workspaces(mmd_ctx* c) {
         int rc = w.pinned ? host_alloc(c, dst, w.bytes) : dev_alloc(c, dst, w.bytes); if (rc) return rc;
     }
     c->v_splitk_bytes = p.v_splitk_bytes; c->v_attn_bytes = p.v_attn_bytes; c->v_h32_rows = p.v_h32_rows;
-    if (!c->cfg.vision_only) { c->splitk_bytes = p.splitk_bytes; c->attn_bytes = p.attn_bytes; c->prev_cap = p.prev_cap; }
+    if (!c->cfg.vision_only) { c->splitk_bytes = p.splitk_bytes; c->attn_bytes = p.attn_bytes; c->resp.prev_cap = p.prev_cap; }
     return MMD_OK;
 }
 
@@ -1424,74 +1488,34 @@ extern "C" int mmd_frame_step_multi(mmd_ctx* c, mmd_stream* const* streams, cons
 struct mmd_sampler {
     mmd_ctx* ctx;
     int64_t* tok_dev = nullptr;                  // the token drawn last (fed back by the next round's embedding gather)
-    int64_t* prev_dev = nullptr; int prev_cap = 0; int n_prev = 0;          // repetition-penalty list (device) and the number of entries that count
-    int64_t eos = -1; float penalty = 0.f;
+    int64_t eos = -1;
     // sampling (mmd_sampler_set_sampling): off = arg-max.  `offset` counts the tokens drawn since the seed was set; `lane` is the sampler's id within its context
     bool sampling = false, seeded = false; float temperature = 1.f, top_p = 1.f; int top_k = 0; uint64_t seed = 0, offset = 0; uint32_t lane = 0;
-    // constraints (mmd_sampler_set_constraints): the set, its table on the device (sampler-owned, uploaded synchronously), tokens returned so far in this response
-    ConsSet cons; int32_t* cons_ids_dev = nullptr; float* cons_bias_dev = nullptr; int step = 0;
-    // log-probabilities (mmd_sampler_set_logprobs): the setting (-1 off), the device records of the current response (sampler-owned, sized for its max_new), how many of them
-    // the rounds have returned, and whether the response is over (EOS, or max_new tokens returned)
-    int lp_top = -1, lp_cap = 0, lp_n = 0, max_new = 0; LogprobRec* lp_rec = nullptr; bool ended = false;
+    // the response of its rounds: the penalty list, the constraints (mmd_sampler_set_constraints), the records (mmd_sampler_set_logprobs; sized for the response's max_new)
+    // and the counters -- tokens returned, records returned, whether the response is over
+    Response resp;
 };
 
-// ---- constraints: validation and the device descriptors ------------------------------------------------------------------------------------------------------------------
-// limits checked when a set is given, not per token (include/mmduet.h): <= 8 EOS ids and <= 256 unique table ids, all in [0, V); bias finite or -inf; min_new >= 0; the
-// suppressed ids and the EOS ids together must leave a token.  n_eos = min_new = n = 0 is "off".  The table is sorted by id for the kernel's binary search.
-static int cons_validate(mmd_ctx* c, int V, const int64_t* eos_ids, int n_eos, int min_new, const int32_t* ids, const float* bias, int n, ConsSet& out) {
-    if (n_eos < 0 || n < 0 || (n_eos > 0 && !eos_ids) || (n > 0 && (!ids || !bias))) FAIL(c, MMD_EINVAL, "bad constraint arguments");
-    if (n_eos > CONS_MAX_EOS) FAIL(c, MMD_EINVAL, "at most %d EOS ids, got %d", CONS_MAX_EOS, n_eos);
-    if (n > CONS_MAX_TABLE) FAIL(c, MMD_EINVAL, "at most %d biased / suppressed ids, got %d", CONS_MAX_TABLE, n);
-    if (min_new < 0) FAIL(c, MMD_EINVAL, "min_new_tokens %d is negative", min_new);
-    ConsSet s;
-    for (int k = 0; k < n_eos; ++k) {
-        if (eos_ids[k] < 0 || eos_ids[k] >= V) FAIL(c, MMD_EINVAL, "EOS id %lld outside the vocabulary of %d", (long long)eos_ids[k], V);
-        s.eos[k] = eos_ids[k];
-    }
-    std::vector<std::pair<int32_t, float>> t((size_t)n);
-    for (int k = 0; k < n; ++k) {
-        if (ids[k] < 0 || ids[k] >= V) FAIL(c, MMD_EINVAL, "table id %d outside the vocabulary of %d", ids[k], V);
-        if (bias[k] != bias[k] || bias[k] == INFINITY) FAIL(c, MMD_EINVAL, "the bias of id %d is %s: finite or -inf only", ids[k], bias[k] != bias[k] ? "NaN" : "+inf");
-        t[k] = {ids[k], bias[k]};
-    }
-    std::sort(t.begin(), t.end(), [](const std::pair<int32_t, float>& a, const std::pair<int32_t, float>& b) { return a.first < b.first; });
-    for (int k = 1; k < n; ++k) if (t[k].first == t[k - 1].first) FAIL(c, MMD_EINVAL, "table id %d is listed twice", t[k].first);
-    long long covered = 0;
-    for (int k = 0; k < n; ++k) { s.ids[k] = t[k].first; s.bias[k] = t[k].second; if (t[k].second == -INFINITY) ++covered; }
-    for (int k = 0; k < n_eos; ++k) {
-        bool dup = false;
-        for (int j = 0; j < k; ++j) dup |= s.eos[j] == s.eos[k];
-        for (int j = 0; j < n; ++j) dup |= s.ids[j] == s.eos[k] && s.bias[j] == -INFINITY;
-        if (!dup) ++covered;
-    }
-    if ((n > 0 || n_eos > 0) && covered >= V) FAIL(c, MMD_EINVAL, "the suppressed ids and the EOS ids cover the whole vocabulary of %d: no token could be returned", V);
-    s.n = n; s.n_eos = n_eos; s.min_new = min_new; s.on = n > 0 || n_eos > 0 || min_new > 0;
-    out = s;
+// ---- constraints: the device descriptors -----------------------------------------------------------------------------------------------------------------------------------
+// a set through constraint_set() (response_plan.h: the limits, the order of the checks and their messages); a refusal becomes the context's error
+static int cons_checked(mmd_ctx* c, int V, const int64_t* eos_ids, int n_eos, int min_new, const int32_t* ids, const float* bias, int n, ConsSet& out) {
+    const ConsSetResult r = constraint_set(V, eos_ids, n_eos, min_new, ids, bias, n);
+    if (r.rc) FAIL(c, r.rc, "%s", r.error);
+    out = r.set;
     return MMD_OK;
 }
-// the device descriptor of a set: an empty EOS set falls back to the call's / sampler's own eos id
-static void cons_fill_row(ConstraintRow& r, const ConsSet& s, const int32_t* ids_dev, const float* bias_dev, int64_t eos_id, int V, int step, const int* step_ptr) {
+// the device descriptor of a set: the EOS ids are response_eos()'s answer, the same the host stops on
+static void cons_fill_row(ConstraintRow& r, const ConsSet& s, const int32_t* ids_dev, const float* bias_dev, const ResponseEos& eos, int step, const int* step_ptr) {
     r.ids = ids_dev; r.bias = bias_dev; r.step_ptr = step_ptr; r.n = s.n; r.min_new = s.min_new; r.step = step;
-    for (int k = 0; k < CONS_MAX_EOS; ++k) r.eos[k] = -1;
-    if (s.n_eos > 0) { r.n_eos = s.n_eos; for (int k = 0; k < s.n_eos; ++k) r.eos[k] = s.eos[k]; }
-    else if (eos_id >= 0 && eos_id < V) { r.n_eos = 1; r.eos[0] = eos_id; }
-    else r.n_eos = 0;
+    r.n_eos = eos.n;
+    for (int k = 0; k < CONS_MAX_EOS; ++k) r.eos[k] = k < eos.n ? eos.ids[k] : -1;
 }
+static void cons_fill_row(ConstraintRow& r, const Response& rs, const ResponseEos& eos) { cons_fill_row(r, rs.cons, rs.cons_ids_dev, rs.cons_bias_dev, eos, rs.count.step, nullptr); }
+// the row descriptors of constrained selections, on the device and pinned
 static int cons_reserve(mmd_ctx* c) {
-    if (c->cons_bias_dev) return MMD_OK;
+    if (c->cons_rows_host) return MMD_OK;
     int rc = dev_alloc(c, (void**)&c->cons_rows_dev, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)); if (rc) return rc;
-    rc = host_alloc(c, (void**)&c->cons_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow)); if (rc) return rc;
-    rc = dev_alloc(c, (void**)&c->cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t)); if (rc) return rc;
-    return dev_alloc(c, (void**)&c->cons_bias_dev, CONS_MAX_TABLE * sizeof(float));
-}
-// the table of a set into its device buffers: the stream is drained first (a step in flight may read the old values), then the copy is synchronous -- no staging of
-// pageable memory behind the caller's back
-static int cons_upload_table(mmd_ctx* c, const ConsSet& s, int32_t* ids_dev, float* bias_dev) {
-    if (s.n <= 0) return MMD_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(ids_dev, s.ids, sizeof(int32_t) * s.n, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(bias_dev, s.bias, sizeof(float) * s.n, hipMemcpyHostToDevice));
-    return MMD_OK;
+    return host_alloc(c, (void**)&c->cons_rows_host, (size_t)(1 + MMD_ROUND_MAX_SAMPLERS) * sizeof(ConstraintRow));
 }
 
 // one draw's parameters
@@ -1502,6 +1526,10 @@ static void fill_sample_row(SampleRow& r, const SampleArgs& a, const int64_t* pr
     r.prev = prev; r.n_prev_ptr = n_prev_ptr; r.tok = tok; r.append = append; r.offset = *a.offset_inout;
     r.n_prev = pen ? n_prev : 0; r.prev_cap = prev_cap; r.penalty = pen ? penalty : 1.f; r.temperature = a.temperature; r.top_k = a.top_k; r.top_p = a.top_p;
     r.seed_lo = (uint32_t)a.seed; r.seed_hi = (uint32_t)(a.seed >> 32); r.lane = lane; r.advance = advance;
+}
+// ... of a response's row: its list at the length that counts now
+static void fill_sample_row(SampleRow& r, const SampleArgs& a, const Response& rs, const int* n_prev_ptr, int64_t* tok, int64_t* append, uint32_t lane, uint32_t advance) {
+    fill_sample_row(r, a, rs.prev_dev, rs.penalty > 0.f, rs.count.n_prev, rs.prev_cap, rs.penalty, n_prev_ptr, tok, append, lane, advance);
 }
 static int sample_reserve(mmd_ctx* c) {
     if (c->samp_scratch) return MMD_OK;
@@ -1587,48 +1615,30 @@ extern "C" void mmd_sampler_destroy(mmd_sampler* sp) {
     hipSetDevice(sp->ctx->device);
     hipStreamSynchronize(sp->ctx->stream);
     if (sp->tok_dev) hipFree(sp->tok_dev);
-    if (sp->prev_dev) hipFree(sp->prev_dev);
-    if (sp->cons_ids_dev) hipFree(sp->cons_ids_dev);
-    if (sp->cons_bias_dev) hipFree(sp->cons_bias_dev);
-    if (sp->lp_rec) hipFree(sp->lp_rec);
+    response_release(sp->ctx, sp->resp);
     delete sp;
 }
-// the records of a response: room for max_new of them once the sampler records.  Like the penalty list the array grows by doubling behind a drained stream
+// the records of a response: room for max_new of them once the sampler records
 static int sampler_lp_reserve(mmd_sampler* sp) {
-    mmd_ctx* c = sp->ctx;
-    const int need = sp->max_new > 0 ? sp->max_new : 1;
-    if (sp->lp_top < 0 || need <= sp->lp_cap) return MMD_OK;
-    int ncap = sp->lp_cap > 0 ? sp->lp_cap : 256;
-    while (ncap < need) ncap *= 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // (a round in flight may still write the old array)
-    if (sp->lp_rec) { hipFree(sp->lp_rec); sp->lp_rec = nullptr; sp->lp_cap = 0; }
-    if (hipMalloc((void**)&sp->lp_rec, (size_t)ncap * sizeof(LogprobRec)) != hipSuccess) FAIL(c, MMD_ENOMEM, "hipMalloc of %d log-probability records failed", ncap);
-    sp->lp_cap = ncap;
-    return MMD_OK;
+    if (sp->resp.lp_top < 0) return MMD_OK;
+    return response_reserve_records(sp->ctx, sp->resp, sampler_records_need(sp->resp.count.max_new), RESPONSE_SAMPLER_RECORDS_FIRST);
 }
 extern "C" int mmd_sampler_begin(mmd_sampler* sp, int64_t eos_id, float rep_penalty, const int64_t* prev_ids_host, int n_prev, int max_new) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
     if (n_prev < 0 || max_new < 0 || (n_prev > 0 && !prev_ids_host)) FAIL(c, MMD_EINVAL, "bad sampler arguments");
-    sp->eos = eos_id; sp->penalty = rep_penalty > 0.f ? rep_penalty : 0.f; sp->n_prev = 0; sp->step = 0;
-    sp->max_new = max_new; sp->lp_n = 0; sp->ended = false;
-    { const int rc = sampler_lp_reserve(sp); if (rc) return rc; }
-    if (sp->penalty <= 0.f) return MMD_OK;
-    const int need = n_prev + max_new + 1;          // (the slot behind the list receives every drawn token; it counts only when the token is not EOS)
-    if (need > sp->prev_cap) {
-        int ncap = sp->prev_cap > 0 ? sp->prev_cap : 1024;
-        while (ncap < need) ncap *= 2;
-        HIPCHK(c, hipStreamSynchronize(c->stream));          // (a round in flight may still read the old list)
-        if (sp->prev_dev) { hipFree(sp->prev_dev); sp->prev_dev = nullptr; sp->prev_cap = 0; }
-        if (hipMalloc((void**)&sp->prev_dev, (size_t)ncap * sizeof(int64_t)) != hipSuccess) FAIL(c, MMD_ENOMEM, "hipMalloc of a %d-entry penalty list failed", ncap);
-        sp->prev_cap = ncap;
-    }
+    Response& r = sp->resp;
+    sp->eos = eos_id; r.penalty = rep_penalty > 0.f ? rep_penalty : 0.f;
+    r.count = ResponseCount{}; r.count.max_new = max_new;
+    int rc = sampler_lp_reserve(sp); if (rc) return rc;
+    if (r.penalty <= 0.f) return MMD_OK;
+    rc = response_reserve_list(c, r, sampler_prev_need(n_prev, max_new), RESPONSE_SAMPLER_PREV_FIRST); if (rc) return rc;
     // (pageable host memory: the copy is staged before the call returns, the caller's list may change afterwards)
-    if (n_prev > 0) HIPCHK(c, hipMemcpyAsync(sp->prev_dev, prev_ids_host, sizeof(int64_t) * n_prev, hipMemcpyHostToDevice, c->stream));
-    sp->n_prev = n_prev;
+    if (n_prev > 0) HIPCHK(c, hipMemcpyAsync(r.prev_dev, prev_ids_host, sizeof(int64_t) * n_prev, hipMemcpyHostToDevice, c->stream));
+    r.count.n_prev = n_prev;
     return MMD_OK;
 }
-extern "C" int mmd_sampler_prev_len(const mmd_sampler* sp) { return sp ? sp->n_prev : MMD_EINVAL; }
+extern "C" int mmd_sampler_prev_len(const mmd_sampler* sp) { return sp ? sp->resp.count.n_prev : MMD_EINVAL; }
 extern "C" int mmd_sampler_set_sampling(mmd_sampler* sp, float temperature, int top_k, float top_p, uint64_t seed) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx;
@@ -1642,42 +1652,31 @@ extern "C" int mmd_sampler_set_sampling(mmd_sampler* sp, float temperature, int 
 extern "C" int mmd_sampler_set_constraints(mmd_sampler* sp, const int64_t* eos_ids_host, int n_eos, int min_new, const int32_t* ids_host, const float* bias_host, int n) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
-    ConsSet s; int rc = cons_validate(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
+    ConsSet s; int rc = cons_checked(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
     if (s.on) {
         rc = select_refused(c, select_plan(select_rows(false, true, false, 1, false, false, c->cfg.vocab_size, nullptr))); if (rc) return rc;
         rc = cons_reserve(c); if (rc) return rc;
-        if (!sp->cons_bias_dev) {
-            if (hipMalloc((void**)&sp->cons_ids_dev, CONS_MAX_TABLE * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&sp->cons_bias_dev, CONS_MAX_TABLE * sizeof(float)) != hipSuccess)
-                FAIL(c, MMD_ENOMEM, "hipMalloc of a sampler's constraint table failed");
-        }
-        rc = cons_upload_table(c, s, sp->cons_ids_dev, sp->cons_bias_dev); if (rc) return rc;
     }
-    sp->cons = s;
-    return MMD_OK;
+    return response_set_constraints(c, sp->resp, s);
 }
-static void unpack_logprobs(const LogprobRec* h, int n, int top_n, float* lp, float* slp, int64_t* top_ids, float* top_lp);
 extern "C" int mmd_sampler_set_logprobs(mmd_sampler* sp, int top_n) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
-    if (top_n < -1 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "log-probability alternatives: -1 (off) or 0..%d, got %d", LP_MAX_TOP, top_n);
-    if (sp->step > 0 && !sp->ended) FAIL(c, MMD_EINVAL, "the response has returned %d token(s): log-probabilities are switched at a response boundary", sp->step);
-    if (top_n >= 0) { const int rc = select_refused(c, select_plan(select_rows(false, false, true, 1, false, false, c->cfg.vocab_size, nullptr))); if (rc) return rc; }
-    sp->lp_top = top_n; sp->lp_n = 0;          // (behind a finished response: its records go with the setting they were written under)
+    ResponseCount& n = sp->resp.count;
+    int rc = response_lp_top_checked(c, top_n); if (rc) return rc;
+    if (n.step > 0 && !n.ended) FAIL(c, MMD_EINVAL, "the response has returned %d token(s): log-probabilities are switched at a response boundary", n.step);
+    if (top_n >= 0) { rc = select_refused(c, select_plan(select_rows(false, false, true, 1, false, false, c->cfg.vocab_size, nullptr))); if (rc) return rc; }
+    sp->resp.lp_top = top_n; n.lp_n = 0;          // (behind a finished response: its records go with the setting they were written under)
     return sampler_lp_reserve(sp);
 }
 extern "C" int mmd_sampler_logprobs_read(mmd_sampler* sp, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out) {
     if (!sp) return MMD_EINVAL;
     mmd_ctx* c = sp->ctx; hipSetDevice(c->device);
     if (!n_out || cap_tokens < 0) FAIL(c, MMD_EINVAL, "bad mmd_sampler_logprobs_read arguments");
-    const int n = sp->lp_top >= 0 ? sp->lp_n : 0;
+    const int n = sp->resp.lp_top >= 0 ? sp->resp.count.lp_n : 0;
     *n_out = n;
     if (n == 0) return MMD_OK;
-    if (cap_tokens < n) FAIL(c, MMD_ERANGE, "%d records, room for %d", n, cap_tokens);
-    std::vector<LogprobRec> h((size_t)n);
-    HIPCHK(c, hipMemcpyAsync(h.data(), sp->lp_rec, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    unpack_logprobs(h.data(), n, sp->lp_top, logprob_host, sampling_logprob_host, top_ids_host, top_logprob_host);
-    return MMD_OK;
+    return response_read_records(c, sp->resp, n, sp->resp.lp_top, logprob_host, sampling_logprob_host, top_ids_host, top_logprob_host, cap_tokens);
 }
 // the round's record descriptors and the record kernels' scratch for a round's rows
 static int round_record_reserve(mmd_ctx* c) {
@@ -1708,8 +1707,8 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         if ((fl & (MMD_SEG_FEED | MMD_SEG_SAMPLE)) && (!sp || sp->ctx != c)) FAIL(c, MMD_EINVAL, "segment %d feeds / samples without a sampler of this context", j);
         RoundSeg& r = rsegs[j];
         r.feed = (fl & MMD_SEG_FEED) != 0; r.sample = (fl & MMD_SEG_SAMPLE) != 0; r.rows = segs[j].rows;
-        if (sp) { r.sampling = sp->sampling; r.constrained = sp->cons.on; r.sampler = (int)sp->lane; r.top_k = sp->top_k; r.top_p = sp->top_p; }          // (lane: the sampler's index within its context)
-        if (sp && sp->lp_top >= 0) { r.record = true; r.lp_top = sp->lp_top; }
+        if (sp) { r.sampling = sp->sampling; r.constrained = sp->resp.cons.on; r.sampler = (int)sp->lane; r.top_k = sp->top_k; r.top_p = sp->top_p; }          // (lane: the sampler's index within its context)
+        if (sp && sp->resp.lp_top >= 0) { r.record = true; r.lp_top = sp->resp.lp_top; }
         if (r.feed) {
             if (n_feed >= MMD_ROUND_MAX_SAMPLERS) FAIL(c, MMD_ERANGE, "more than %d feed segments", MMD_ROUND_MAX_SAMPLERS);
             feed.tok[n_feed] = sp->tok_dev; feed.row[n_feed] = segs[j].row0; ++n_feed;
@@ -1732,25 +1731,23 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
     if (nd > 0 || plain_tail > 0) { rc = sample_reserve(c); if (rc) return rc; }
     if (n_rec > 0) { rc = round_record_reserve(c); if (rc) return rc; }
     for (int i = 0; i < n_sample; ++i) {
-        const int j = sample_seg[i]; mmd_sampler* sp = samplers[j];
-        const bool pen = sp->penalty > 0.f;
-        int64_t* append = (pen && sp->n_prev < sp->prev_cap) ? sp->prev_dev + sp->n_prev : nullptr;
+        const int j = sample_seg[i]; mmd_sampler* sp = samplers[j]; const Response& r = sp->resp;
+        const bool pen = r.penalty > 0.f;
+        int64_t* append = (pen && r.count.n_prev < r.prev_cap) ? r.prev_dev + r.count.n_prev : nullptr;
         sample_row[i] = segs[j].row0 + segs[j].rows - 1;
-        if (n_rec > 0) c->round_lp_rows_host[i] = sp->lp_top >= 0 ? LogprobRow{sp->lp_rec, sp->step, sp->lp_cap, sp->lp_top} : LogprobRow{nullptr, 0, 0, 0};
+        if (n_rec > 0) c->round_lp_rows_host[i] = r.lp_top >= 0 ? LogprobRow{r.lp_rec, r.count.step, r.lp_cap, r.lp_top} : LogprobRow{nullptr, 0, 0, 0};
         if (i < n_plain) {
-            sb.prev[i] = sp->prev_dev; sb.n_prev[i] = pen ? sp->n_prev : 0; sb.penalty[i] = pen ? sp->penalty : 1.f; sb.tok[i] = sp->tok_dev; sb.append[i] = append;
-            if (i >= rb.rec0[SEL_ARGMAX])
-                fill_sample_row(c->samp_rows_host[1 + nd + (i - rb.rec0[SEL_ARGMAX])], SampleArgs{1.f, 0, 1.f, 0, &no_offset}, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr,
-                                nullptr, nullptr, 0, 0);
+            sb.prev[i] = r.prev_dev; sb.n_prev[i] = pen ? r.count.n_prev : 0; sb.penalty[i] = pen ? r.penalty : 1.f; sb.tok[i] = sp->tok_dev; sb.append[i] = append;
+            if (i >= rb.rec0[SEL_ARGMAX]) fill_sample_row(c->samp_rows_host[1 + nd + (i - rb.rec0[SEL_ARGMAX])], SampleArgs{1.f, 0, 1.f, 0, &no_offset}, r, nullptr, nullptr, nullptr, 0, 0);
             continue;
         }
-        if (sp->cons.on) { rc = cons_reserve(c); if (rc) return rc; }
+        if (r.cons.on) { rc = cons_reserve(c); if (rc) return rc; }
         const bool draw = i >= n_greedy;
         const SampleArgs a = draw ? SampleArgs{sp->temperature, sp->top_k, sp->top_p, sp->seed, &sp->offset} : SampleArgs{1.f, 0, 1.f, 0, &no_offset};
         const int slot = 1 + i - n_plain;
-        fill_sample_row(c->samp_rows_host[slot], a, sp->prev_dev, pen, sp->n_prev, sp->prev_cap, sp->penalty, nullptr, sp->tok_dev, append, draw ? sp->lane : 0, 0);
+        fill_sample_row(c->samp_rows_host[slot], a, r, nullptr, sp->tok_dev, append, draw ? sp->lane : 0, 0);
         if (c->cons_rows_host) {
-            if (sp->cons.on) cons_fill_row(c->cons_rows_host[slot], sp->cons, sp->cons_ids_dev, sp->cons_bias_dev, sp->eos, V, sp->step, nullptr);
+            if (r.cons.on) cons_fill_row(c->cons_rows_host[slot], r, response_eos(r.cons, sp->eos, V));
             else c->cons_rows_host[slot] = ConstraintRow{};
         }
     }
@@ -1824,11 +1821,8 @@ extern "C" int mmd_round_multi(mmd_ctx* c, mmd_stream* const* streams, const int
         tokens_out_host[sample_seg[i]] = tok;
         if (i >= n_greedy) sp->offset += 1;
         if (tok < 0) FAIL(c, MMD_EDOM, "segment %d: a NaN among the logits, or every score is -inf: no token drawn", sample_seg[i]);
-        sp->step += 1;
-        if (sp->lp_top >= 0) sp->lp_n += 1;
-        const bool is_eos = (sp->cons.on && sp->cons.n_eos > 0) ? std::find(sp->cons.eos, sp->cons.eos + sp->cons.n_eos, tok) != sp->cons.eos + sp->cons.n_eos : tok == sp->eos;
-        if (sp->penalty > 0.f && !is_eos && sp->n_prev < sp->prev_cap) sp->n_prev += 1;          // (EOS is neither fed back nor penalised: models/modeling_live.py:66-72)
-        if (is_eos || sp->step >= sp->max_new) sp->ended = true;
+        Response& r = sp->resp;          // (the kernels have appended the token where the list had room: the count follows)
+        response_note_token(r.count, response_is_eos(response_eos(r.cons, sp->eos, V), tok), r.penalty > 0.f, r.lp_top >= 0, r.prev_cap);
     }
     return MMD_OK;
 }
@@ -1929,39 +1923,39 @@ extern "C" int mmd_frame_step(mmd_ctx* c, mmd_stream* s, const void* embeds, int
 
 // what a generate call's selection launches over: the context's one-row buffers -- logits_ws, row / constraint descriptor 0, tok_dev; the plain arg-max takes the penalty list
 // in kernel arguments (dyn: its length from *dyn)
-static SelectIO generate_select_io(mmd_ctx* c, const SelectPlan& p, bool pen, float rep_penalty, int np, const StepState* dyn, const LogprobOut* lp) {
+static SelectIO generate_select_io(mmd_ctx* c, const SelectPlan& p, const StepState* dyn, const LogprobOut* lp) {
+    const Response& r = c->resp; const bool pen = r.penalty > 0.f;
     SelectIO io{};
     io.logits = c->logits_ws; io.V = c->cfg.vocab_size; io.n = 1; io.rows = c->samp_rows_dev; io.cons = c->cons_rows_dev; io.lp = lp;
     io.toks = p.kind == SEL_DRAW ? nullptr : c->tok_dev;          // (the draw's row descriptor names tok_dev itself)
     io.scratch = c->samp_scratch; io.lp_scratch = c->lp_scratch; io.am_scratch = c->argmax_scratch;
-    io.prev = c->prev_dev; io.n_prev = pen ? (np < c->prev_cap ? np : c->prev_cap) : 0; io.penalty = pen ? rep_penalty : 1.f; io.dyn = dyn;
+    io.prev = r.prev_dev; io.n_prev = pen ? r.count.n_prev : 0; io.penalty = pen ? r.penalty : 1.f; io.dyn = dyn;
     return io;
 }
 
 // one decode step (feed the previously drawn token, choose the next as `sel` says) enqueued on the stream; `dyn` selects the graph-capturable form that reads position / arena /
 // penalty-list length from device state.  `lp`: where the step records (the kernels stand between the choice of the token and the state's advance)
-static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, const SelectPlan& sel, bool pen, float rep_penalty, int np, int64_t eos_id, const StepState* dyn, const LogprobOut* lp) {
+static int decode_step_enqueue(mmd_ctx* c, mmd_stream* s, const SelectPlan& sel, int64_t eos_id, const StepState* dyn, const LogprobOut* lp) {
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size;
     // the next token's embedding is gathered straight into the residual-stream buffer (llm_step_segs skips its copy when embeds == l_h)
     HIPCHK(c, launch_embed(g.dtype, c->embed, c->tok_dev, 1, H, g.vocab_size, c->l_h, st));
     int rc = llm_step_impl(c, s, c->l_h, 1, nullptr, dyn); if (rc) return rc;
     rc = gemm(c, c->l_hid, H, c->lm_head, H, nullptr, nullptr, 0, c->logits_ws, g.vocab_size, 1, g.vocab_size, H, EPI_NONE, 1, GEMM_AUTO, c->lm_head_p); if (rc) return rc;
-    HIPCHK(c, select_enqueue(c, sel, generate_select_io(c, sel, pen, rep_penalty, np, dyn, lp)));
-    if (sel.advance) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->prev_dev, c->prev_cap, eos_id, pen ? 1 : 0, st, sel.needs_cons ? c->cons_rows_dev : nullptr));
+    HIPCHK(c, select_enqueue(c, sel, generate_select_io(c, sel, dyn, lp)));
+    if (sel.advance) HIPCHK(c, launch_advance_state(c->step_dev, c->tok_dev, c->resp.prev_dev, c->resp.prev_cap, eos_id, c->resp.penalty > 0.f ? 1 : 0, st, sel.needs_cons ? c->cons_rows_dev : nullptr));
     return MMD_OK;
 }
 
 // captures one dynamic decode step into dg for the key (key_pen, eos_id, the plan's key).  Capture runs on the context's own stream (the legacy null stream -- torch's default --
 // cannot be captured); the instantiated graph is then launched on whatever stream the caller bound
-static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, const SelectPlan& sel, const GeneratePlan& gp, bool pen, float rep_penalty, int np, int64_t eos_id, float key_pen,
-                               const LogprobOut* lp) {
+static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, const SelectPlan& sel, const GeneratePlan& gp, int64_t eos_id, float key_pen, const LogprobOut* lp) {
     hipStream_t st = c->stream;
     dg.drop();
     HIPCHK(c, hipStreamSynchronize(st));
     c->stream = c->own_stream;
     hipError_t be = hipStreamBeginCapture(c->own_stream, hipStreamCaptureModeThreadLocal);
     if (be != hipSuccess) { c->stream = st; HIPCHK(c, be); }
-    int rc = decode_step_enqueue(c, s, sel, pen, rep_penalty, np, eos_id, c->step_dev, lp);
+    int rc = decode_step_enqueue(c, s, sel, eos_id, c->step_dev, lp);
     hipError_t ce = hipStreamEndCapture(c->own_stream, &dg.src);
     c->stream = st;
     if (rc) { dg.drop(); return rc; }
@@ -1971,34 +1965,9 @@ static int capture_decode_step(mmd_ctx* c, mmd_stream* s, DecodeGraph& dg, const
     return MMD_OK;
 }
 
-// The reference penalises EVERY id generated so far in the video (models/modeling_live.py:60-66; the list persists across turns): the device copy grows
-// with it (doubling; both captured decode steps hold the old pointer and are dropped).  No cap.
-static int penalty_reserve(mmd_ctx* c, int need) {
-    if (need <= c->prev_cap) return MMD_OK;
-    int ncap = c->prev_cap > 0 ? c->prev_cap : 16384;
-    while (ncap < need) ncap *= 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->dec_greedy.drop(); c->dec_sampled.drop();
-    dev_free(c, c->prev_dev); c->prev_dev = nullptr; c->prev_cap = 0;
-    int rc = dev_alloc(c, (void**)&c->prev_dev, (size_t)ncap * sizeof(int64_t)); if (rc) return rc;
-    c->prev_cap = ncap;
-    return MMD_OK;
-}
-
-// the records of a call's tokens: like the penalty list the buffer grows by doubling, and the captured steps that hold the old pointer are dropped
-static int logprob_reserve(mmd_ctx* c, int need) {
-    if (!c->lp_scratch) { int rc = dev_alloc(c, &c->lp_scratch, logprob_scratch_bytes(1), false); if (rc) return rc; }
-    if (need <= c->lp_cap) return MMD_OK;
-    int ncap = c->lp_cap > 0 ? c->lp_cap : 1024;
-    while (ncap < need) ncap *= 2;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->dec_greedy.drop(); c->dec_sampled.drop();
-    if (c->lp_rec) dev_free(c, c->lp_rec);
-    c->lp_rec = nullptr; c->lp_cap = 0;
-    int rc = dev_alloc(c, (void**)&c->lp_rec, (size_t)ncap * sizeof(LogprobRec)); if (rc) return rc;
-    c->lp_cap = ncap;
-    return MMD_OK;
-}
+// The reference penalises EVERY id generated so far in the video (models/modeling_live.py:60-66; the list persists across turns): the device copy grows with it.  No cap.
+// Both captured decode steps hold the list's and the records' pointers: when either buffer moves they are dropped.
+static void generate_buffer_moved(mmd_ctx* c, bool moved) { if (moved) { c->dec_greedy.drop(); c->dec_sampled.drop(); } }
 
 // ---- the token loop of a response: prompt step, then one token in, one token out --------------------------------------------------------------------------
 // samp == nullptr: arg-max (+ repetition penalty).  Otherwise the sampling chain of sample.hip stands where the arg-max stood.  Which launches choose a token is
@@ -2011,46 +1980,58 @@ static int logprob_reserve(mmd_ctx* c, int need) {
 static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, int S, int64_t eos_id, float rep_penalty, int64_t* prev_ids_host, int* n_prev, int prev_cap,
                          int64_t* out_ids_host, int max_new, int* n_out, const SampleArgs* samp) {
     c->dec_route = 0; *n_out = 0;
-    const int lp_top = c->lp_top; const bool lp_on = lp_top >= 0;
-    c->lp_n = 0; c->lp_call_top = lp_top;
+    Response& rs = c->resp; ResponseCount& cnt = rs.count;
+    const int lp_top = rs.lp_top; const bool lp_on = lp_top >= 0;
+    cnt = ResponseCount{}; cnt.max_new = max_new; c->lp_call_top = lp_top;
     if (max_new == 0) return MMD_OK;          // nothing asked for: nothing is enqueued, the stream is not extended
     if (!s || s->ctx != c) FAIL(c, MMD_EINVAL, "stream does not belong to this context");
     if (S < 1) FAIL(c, MMD_EINVAL, "empty prompt");
     int rc;
     if (samp) { rc = check_sampling(c, samp->temperature, samp->top_k, samp->top_p); if (rc) return rc; }
     const mmd_config& g = c->cfg; hipStream_t st = c->stream; const int H = g.hidden_size, V = g.vocab_size; const size_t e = es(c);
-    const bool cons_on = c->cons.on;
+    const bool cons_on = rs.cons.on;
     const SelectPlan sel0 = select_plan(select_rows(samp != nullptr, cons_on, lp_on, 1, true, false, V, samp));          // the prompt step's choice
     rc = select_refused(c, sel0); if (rc) return rc;
     const bool pen = rep_penalty > 0.f;
-    int np = (pen && n_prev) ? *n_prev : 0;
-    if (pen) { rc = penalty_reserve(c, np + max_new); if (rc) return rc; }
+    rs.penalty = pen ? rep_penalty : 0.f;
+    const int np0 = (pen && n_prev) ? *n_prev : 0;          // cnt.n_prev from here on: the list's length, grown by response_note_token
+    bool moved = false;
+    if (pen) { rc = response_reserve_list(c, rs, generate_prev_need(np0, max_new), MODEL_PREV_CAP, &moved); generate_buffer_moved(c, moved); if (rc) return rc; }
     if (sel0.needs_row) { rc = sample_reserve(c); if (rc) return rc; }
-    // constraints on: descriptor 0 on the device carries the EOS set (the call's own eos_id when the set is empty), min_new and the table; the captured step reads the response
-    // step through &step_dev->step, an eager arg-max step gets it posted.  EOS below is membership of that set.
+    // constraints on: descriptor 0 on the device carries the response's EOS ids (response_eos: the call's own eos_id when the set has none), min_new and the table; the captured
+    // step reads the response step through &step_dev->step, an eager arg-max step gets it posted.  The host stops on the same ids.
+    const ResponseEos eos = response_eos(rs.cons, eos_id, V);
     ConstraintRow crow{};
-    if (cons_on) cons_fill_row(crow, c->cons, c->cons_ids_dev, c->cons_bias_dev, eos_id, V, 0, nullptr);
+    if (cons_on) cons_fill_row(crow, rs, eos);
     auto post_cons = [&](bool dynamic, int step) -> int {
         crow.step = step; crow.step_ptr = dynamic ? &c->step_dev->step : nullptr;
         c->cons_rows_host[0] = crow;
         HIPCHK(c, hipMemcpyAsync(c->cons_rows_dev, c->cons_rows_host, sizeof(ConstraintRow), hipMemcpyHostToDevice, st));
         return MMD_OK;
     };
-    auto is_eos = [&](int64_t t) -> bool { return cons_on ? cons_is_eos(crow, t) : t == eos_id; };
-    if (lp_on) { rc = logprob_reserve(c, max_new); if (rc) return rc; }
-    if (np > 0) HIPCHK(c, hipMemcpyAsync(c->prev_dev, prev_ids_host, sizeof(int64_t) * np, hipMemcpyHostToDevice, st));
+    if (lp_on && !c->lp_scratch) { rc = dev_alloc(c, &c->lp_scratch, logprob_scratch_bytes(1), false); if (rc) return rc; }
+    if (lp_on) { rc = response_reserve_records(c, rs, max_new, RESPONSE_CTX_RECORDS_FIRST, &moved); generate_buffer_moved(c, moved); if (rc) return rc; }
+    if (np0 > 0) HIPCHK(c, hipMemcpyAsync(rs.prev_dev, prev_ids_host, sizeof(int64_t) * np0, hipMemcpyHostToDevice, st));
+    cnt.n_prev = np0;
     uint64_t no_offset = 0;
     // row descriptor 0: the draw's row, or -- behind an arg-max -- the row of the scores that the constraints and the records read: the penalty at T = 1, no filter, no draw.
     // (Every earlier upload from this staging slot has been waited for: a token read lies in between.)
     auto post_row = [&](bool dynamic) -> int {
         const SampleArgs plain{1.f, 0, 1.f, 0, &no_offset};
-        fill_sample_row(c->samp_rows_host[0], samp ? *samp : plain, c->prev_dev, pen, np < c->prev_cap ? np : c->prev_cap, c->prev_cap, rep_penalty, dynamic ? &c->step_dev->n_prev : nullptr,
-                        samp ? c->tok_dev : nullptr, nullptr, samp ? c->sample_lane : 0, samp ? 1 : 0);
+        fill_sample_row(c->samp_rows_host[0], samp ? *samp : plain, rs, dynamic ? &c->step_dev->n_prev : nullptr, samp ? c->tok_dev : nullptr, nullptr, samp ? c->sample_lane : 0, samp ? 1 : 0);
         HIPCHK(c, hipMemcpyAsync(c->samp_rows_dev, c->samp_rows_host, sizeof(SampleRow), hipMemcpyHostToDevice, st));
         return MMD_OK;
     };
-    LogprobOut lpo{c->lp_rec, c->lp_cap, nullptr, 0, c->tok_dev, lp_top};
-    int produced = 0;
+    LogprobOut lpo{rs.lp_rec, rs.lp_cap, nullptr, 0, c->tok_dev, lp_top};
+    // a token read: returned and counted; unless it is EOS it joins the penalty list -- on the device by a copy here (`copy`) or by advance_state_kernel, in the caller's list here
+    auto take_token = [&](int64_t tok, bool copy) -> int {
+        out_ids_host[cnt.step] = tok; *n_out = cnt.step + 1;
+        if (!response_note_token(cnt, response_is_eos(eos, tok), pen, lp_on, rs.prev_cap)) return MMD_OK;
+        const int at = cnt.n_prev - 1;
+        if (copy) HIPCHK(c, hipMemcpyAsync(rs.prev_dev + at, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (prev_ids_host && at < prev_cap) prev_ids_host[at] = tok;
+        return MMD_OK;
+    };
     auto read_token = [&](int64_t* tok) -> int {
         HIPCHK(c, hipMemcpyAsync(c->tok_host, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -2068,17 +2049,12 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         if (sel0.needs_row) { rc = post_row(false); if (rc) return rc; }
         if (sel0.needs_cons) { rc = post_cons(false, 0); if (rc) return rc; }
         ProfScope ps(c, MMD_K_OTHER, 0, 0);
-        HIPCHK(c, select_enqueue(c, sel0, generate_select_io(c, sel0, pen, rep_penalty, np, nullptr, &lpo)));
+        HIPCHK(c, select_enqueue(c, sel0, generate_select_io(c, sel0, nullptr, &lpo)));
     }
     int64_t tok = 0;
     rc = read_token(&tok); if (rc) return rc;
-    out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
-    const bool stop = is_eos(tok);
-    if (!stop && pen) {
-        if (np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
-        ++np;
-    }
+    rc = take_token(tok, true); if (rc) return rc;
+    const bool stop = response_is_eos(eos, tok);
     // steps 1..: one token in, one token out
     GenerateShape shape;
     shape.sampled = samp != nullptr; shape.constrained = cons_on; shape.record = lp_on; shape.pen = pen; shape.max_new = max_new; shape.first_is_eos = stop;
@@ -2092,7 +2068,7 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
     if (gp.can_graph) { rc = kv_reserve(c, s, s->len + max_new + 1); if (rc) return rc; }
     if (gp.upload_state) {
         StepState* hs = c->step_host;
-        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = np; hs->step = 1; hs->pos_off = s->pos_off;
+        hs->n_ctx = s->len; hs->cap = s->cap; hs->K = s->K; hs->V = s->V; hs->n_prev = cnt.n_prev; hs->step = 1; hs->pos_off = s->pos_off;
         HIPCHK(c, hipMemcpyAsync(c->step_dev, hs, sizeof(StepState), hipMemcpyHostToDevice, st));
     }
     if (gp.post_row_dynamic) { rc = post_row(true); if (rc) return rc; }
@@ -2103,7 +2079,7 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
         const float key_pen = pen ? (gp.pen_key_is_value ? rep_penalty : 1.f) : 0.f;
         c->dec_route = 1;
         if (!dg.exec || dg.pen != key_pen || dg.eos != eos_id || dg.sel != gp.key_sel || dg.lp != gp.key_lp || dg.cons != gp.key_cons_gen) {
-            rc = capture_decode_step(c, s, dg, sel, gp, pen, rep_penalty, np, eos_id, key_pen, &lpo); if (rc) { c->dec_route = 0; return rc; }
+            rc = capture_decode_step(c, s, dg, sel, gp, eos_id, key_pen, &lpo); if (rc) { c->dec_route = 0; return rc; }
             c->dec_route = 2;
         }
         sel.fields(c->select_last);          // the plan the replayed step was captured from
@@ -2114,18 +2090,13 @@ static int generate_impl(mmd_ctx* c, mmd_stream* s, const void* prompt_embeds, i
             if (gp.post_row_each_eager_step) { rc = post_row(false); if (rc) return rc; }
             if (gp.post_cons_each_eager_step) { rc = post_cons(false, i); if (rc) return rc; }
             lpo.idx0 = i;
-            rc = decode_step_enqueue(c, s, sel, pen, rep_penalty, np, eos_id, nullptr, &lpo); if (rc) return rc;
+            rc = decode_step_enqueue(c, s, sel, eos_id, nullptr, &lpo); if (rc) return rc;
         }
         rc = read_token(&tok); if (rc) return rc;
-        out_ids_host[produced++] = tok; *n_out = produced; if (lp_on) c->lp_n = produced;
-        if (is_eos(tok)) break;
-        if (pen) {          // (the list grows by a copy here or in advance_state_kernel)
-            if (gp.host_appends_penalty && np < c->prev_cap) HIPCHK(c, hipMemcpyAsync(c->prev_dev + np, c->tok_dev, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-            if (prev_ids_host && np < prev_cap) prev_ids_host[np] = tok;
-            ++np;
-        }
+        rc = take_token(tok, gp.host_appends_penalty); if (rc) return rc;
+        if (response_is_eos(eos, tok)) break;
     }
-    if (pen && n_prev) *n_prev = np;
+    if (pen && n_prev) *n_prev = cnt.n_prev;
     return MMD_OK;
 }
 
@@ -2148,29 +2119,18 @@ extern "C" int mmd_sample_generate(mmd_ctx* c, mmd_stream* s, const void* prompt
 
 extern "C" int mmd_set_generate_constraints(mmd_ctx* c, const int64_t* eos_ids_host, int n_eos, int min_new, const int32_t* ids_host, const float* bias_host, int n) {
     NEED_FINAL(c);
-    ConsSet s; int rc = cons_validate(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
-    if (s.on) {
-        rc = cons_reserve(c); if (rc) return rc;
-        rc = cons_upload_table(c, s, c->cons_ids_dev, c->cons_bias_dev); if (rc) return rc;
-    }
+    ConsSet s; int rc = cons_checked(c, c->cfg.vocab_size, eos_ids_host, n_eos, min_new, ids_host, bias_host, n, s); if (rc) return rc;
+    if (s.on) { rc = cons_reserve(c); if (rc) return rc; }
+    rc = response_set_constraints(c, c->resp, s); if (rc) return rc;
     c->cons_gen = s.on ? 1 : 0;          // on <-> off: another captured step.  Everything else about a set -- EOS ids, min_new, the table -- is read from descriptor 0 on the device
-    c->cons = s;
     return MMD_OK;
 }
 
 extern "C" int mmd_set_generate_logprobs(mmd_ctx* c, int top_n) {
     if (!c) return MMD_EINVAL;
-    if (top_n < -1 || top_n > LP_MAX_TOP) FAIL(c, MMD_ERANGE, "log-probability alternatives: -1 (off) or 0..%d, got %d", LP_MAX_TOP, top_n);
-    c->lp_top = top_n;
+    const int rc = response_lp_top_checked(c, top_n); if (rc) return rc;
+    c->resp.lp_top = top_n;          // (the next call's; the last call's records stay readable under lp_call_top)
     return MMD_OK;
-}
-
-static void unpack_logprobs(const LogprobRec* h, int n, int top_n, float* lp, float* slp, int64_t* top_ids, float* top_lp) {
-    for (int i = 0; i < n; ++i) {
-        if (lp) lp[i] = h[i].lp;
-        if (slp) slp[i] = h[i].slp;
-        for (int j = 0; j < top_n; ++j) { if (top_ids) top_ids[(size_t)i * top_n + j] = h[i].top_id[j]; if (top_lp) top_lp[(size_t)i * top_n + j] = h[i].top_lp[j]; }
-    }
 }
 
 extern "C" int mmd_generate_logprobs_read(mmd_ctx* c, float* logprob_host, float* sampling_logprob_host, int64_t* top_ids_host, float* top_logprob_host, int cap_tokens, int* n_out) {
@@ -2178,13 +2138,9 @@ extern "C" int mmd_generate_logprobs_read(mmd_ctx* c, float* logprob_host, float
     hipSetDevice(c->device);
     if (!n_out || cap_tokens < 0) FAIL(c, MMD_EINVAL, "bad mmd_generate_logprobs_read arguments");
     *n_out = 0;
-    const int n = c->lp_n;
+    const int n = c->resp.count.lp_n;
     if (n == 0) return MMD_OK;
-    if (cap_tokens < n) FAIL(c, MMD_ERANGE, "%d records, room for %d", n, cap_tokens);
-    std::vector<LogprobRec> h((size_t)n);
-    HIPCHK(c, hipMemcpyAsync(h.data(), c->lp_rec, sizeof(LogprobRec) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    unpack_logprobs(h.data(), n, c->lp_call_top, logprob_host, sampling_logprob_host, top_ids_host, top_logprob_host);
+    const int rc = response_read_records(c, c->resp, n, c->lp_call_top, logprob_host, sampling_logprob_host, top_ids_host, top_logprob_host, cap_tokens); if (rc) return rc;
     *n_out = n;
     return MMD_OK;
 }
@@ -2229,8 +2185,8 @@ static int op_select_impl(mmd_ctx* c, const float* logits, int n, int V, const i
         fill_sample_row(rows[i], a, prev_ids_dev, pen_on, n_prev, n_prev, rep_penalty, nullptr, nullptr, nullptr, (uint32_t)i, 0);
         if (!oc) continue;
         const int o = oc->tab_off[i];
-        for (int k = 0; k < oc->sets[i].n; ++k) { ids[o + k] = oc->sets[i].ids[k]; bias[o + k] = oc->sets[i].bias[k]; }          // (sorted by cons_validate)
-        cons_fill_row(crows[i], oc->sets[i], ids_dev + o, bias_dev + o, -1, V, oc->step[i], nullptr);
+        for (int k = 0; k < oc->sets[i].n; ++k) { ids[o + k] = oc->sets[i].ids[k]; bias[o + k] = oc->sets[i].bias[k]; }          // (sorted by constraint_set)
+        cons_fill_row(crows[i], oc->sets[i], ids_dev + o, bias_dev + o, response_eos(oc->sets[i], -1, V), oc->step[i], nullptr);
     }
     // (synchronous copies: the vectors above are pageable)
     OPCHK(hipMemcpy(rows_dev, rows.data(), sizeof(SampleRow) * n, hipMemcpyHostToDevice));
@@ -2294,7 +2250,7 @@ extern "C" int mmd_op_sample_logprobs(mmd_ctx* c, const float* logits, int n, in
 }
 
 // raw operator of the constrained chain: mmd_op_sample_logprobs with one constraint set per row.  Row i's table is entries [tab_off[i], tab_off[i + 1]) of tab_ids / tab_bias;
-// every set goes through cons_validate (the limits of mmd_set_generate_constraints).  Unlike the two entries above, a row without a token fails the call.
+// every set goes through constraint_set (the limits of mmd_set_generate_constraints).  Unlike the two entries above, a row without a token fails the call.
 extern "C" int mmd_op_sample_constrained(mmd_ctx* c, const float* logits, int n, int V, const int64_t* prev_ids_dev, int n_prev, float rep_penalty, float temperature, int top_k, float top_p,
                                          uint64_t seed, uint64_t offset, const uint64_t* r_host, int greedy, int top_n,
                                          const int32_t* tab_off_host, const int32_t* tab_ids_host, const float* tab_bias_host, const int64_t* eos_host, const int32_t* n_eos_host,
@@ -2311,8 +2267,8 @@ extern "C" int mmd_op_sample_constrained(mmd_ctx* c, const float* logits, int n,
     for (int i = 0; i < n; ++i) {
         const int o = tab_off_host[i], m = tab_off_host[i + 1] - o;
         if (m < 0 || step_host[i] < 0) FAIL(c, MMD_EINVAL, "row %d: bad table offsets or step", i);
-        rc = cons_validate(c, V, eos_host ? eos_host + (size_t)i * CONS_MAX_EOS : nullptr, n_eos_host[i], min_new_host[i], tab_ids_host ? tab_ids_host + o : nullptr,
-                           tab_bias_host ? tab_bias_host + o : nullptr, m, sets[i]);
+        rc = cons_checked(c, V, eos_host ? eos_host + (size_t)i * CONS_MAX_EOS : nullptr, n_eos_host[i], min_new_host[i], tab_ids_host ? tab_ids_host + o : nullptr,
+                          tab_bias_host ? tab_bias_host + o : nullptr, m, sets[i]);
         if (rc) return rc;
     }
     const OpConstraints oc{sets.data(), tab_off_host, step_host};

@@ -4,7 +4,8 @@
 //   generate_plan()  what a generate call decides once, behind its first token: captured or eager steps, which descriptors are posted when, who grows the penalty list,
 //                    the key of the captured step.
 //   round_blocks()   the sampling segments of a scheduler round ordered into its three blocks of logits rows, each block's recording rows as its tail.
-// mmd_op_select_last_plan reads the answers back.
+// mmd_op_select_last_plan reads the answers back.  What a response in progress owns -- the constraint set and its limits, the EOS ids it stops on, how its penalty list and
+// records grow, what a token read back does to its counters -- is response_plan.h's, not decided here.
 #pragma once
 #include <stdio.h>
 #include "step_plan.h"
