@@ -276,29 +276,6 @@ __global__ void attn_combine_kernel(AttnP p, int nrows_total_all) {
     }
 }
 
-#ifdef MMDUET_ATTN_GRP_LSB
-#define ATTN_GRP(w) ((w) & 1)
-#else
-#define ATTN_GRP(w) ((w) >> 2)
-#endif
-#ifdef MMDUET_ATTN_TIMING
-// debug build only (`make ATTN_TIMING=1`, tools/attn_timing.py; never shipped): per-wave issue-time stamps of the chunk kernel's loop segments, summed over all
-// waves of all launches since the last reset: [0] wait + barrier + next tile's DMA issue, [1] score MFMAs (+ K fragment reads), [2] softmax, [3] P.V MFMAs (+ V reads), [4] tiles, [5] whole kernel
-__device__ unsigned long long g_attn_t[8];
-extern "C" int mmd_debug_attn_timing(unsigned long long* out8, int reset) {
-    if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_attn_t), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_attn_t), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
-#define ATS_DECL unsigned long long ats_[6] = {0, 0, 0, 0, 0, 0}, ats_t_ = __builtin_readcyclecounter(), ats_k_ = ats_t_
-#define ATS(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); ats_[i] += n_ - ats_t_; ats_t_ = n_; } while (0)
-#define ATS_FLUSH do { ats_[5] = __builtin_readcyclecounter() - ats_k_; if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 6; ++i_) atomicAdd(&g_attn_t[i_], ats_[i_]); } while (0)
-#else
-#define ATS_DECL
-#define ATS(i)
-#define ATS_FLUSH
-#endif
-
 // ------------------------------------------------------------------------------------------------------------------
 // attn_gqa128_kernel: the LLM attention of the streaming loop (head_dim 128, bf16, K arena [kvh][cap][128], V arena
 // transposed in 64-token blocks).  One block = 4 waves x RT row-tiles of 16 "rows" (row = tok*G + g: the G query heads
@@ -318,7 +295,7 @@ extern "C" int mmd_debug_attn_timing(unsigned long long* out8, int reset) {
 //     latency instead of four; the q prologue (slab sum + RoPE) loads are issued before the DMAs and finished under them.
 //   * WAVES = 8 (chunks of >= 1024 rows per kv head): 256 query rows per block, ONE block per CU, the four-slot ring fed by all eight waves (4 DMA pieces per
 //     wave and tile, counted vmcnt, raw barrier).  The 128-row form is bound by its K / V stream, not by MFMA or VALU: each block re-reads the whole key range
-//     of its kv head from L2 with one 32 KB tile in flight (tools/attn_timing.py: 43-59 % of every wave's cycles sit in the per-tile wait + barrier; 2.1 GB per
+//     of its kv head from L2 with one 32 KB tile in flight (per-segment cycle stamps, profiles/history/r03_attention_experiments.md: 43-59 % of every wave's cycles sit in the per-tile wait + barrier; 2.1 GB per
 //     launch at 15 k keys = 5.7 TB/s).  256 rows halve that traffic per flop and three tiles in flight cover the L2 latency.
 template <int RT, int NSLOT = 2, int WAVES = 4>
 // (launch bound: the four-wave forms are compiled for TWO blocks per CU although the decode ring's 128 KB of LDS admit one -- at one wave per SIMD hipcc has 512 registers, moves the
@@ -562,7 +539,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
     }
     // (ring form: wave 0 wrote the new token's K row above and never counts vmcnt again -- drain it here, before the first barrier lets a loader stage that row's tile)
     if constexpr (NSLOT == 4 && !ALLRING) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ATS_DECL;
     if constexpr (ALLRING) {
         // The q fragments come from ordinary global loads; their first use sits behind a branch (wave_active), so hipcc would place its wait for them -- a full vmcnt(0),
         // which also drains the ring's DMAs -- at the score MFMAs INSIDE the tile loop, every tile.  Touch them here: the wait happens once, before the loop.
@@ -571,15 +547,11 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
 #pragma unroll
             for (int c = 0; c < 4; ++c) asm volatile("" :: "v"(qf[rt][c]));
         // Phase-split loop.  Left to itself every wave runs score MFMAs -> softmax -> P.V MFMAs in the same order behind the same per-tile barrier, so the two waves
-        // of a SIMD want the matrix pipe together and the VALU together (tools/attn_timing.py: ~6400 cycles per wave and tile for 1024 cycles of MFMA).  Here a
+        // of a SIMD want the matrix pipe together and the VALU together (per-segment cycle stamps, profiles/history/r03_attention_experiments.md: ~6400 cycles per wave and tile for 1024 cycles of MFMA).  Here a
         // wave's tile i is two SEGMENTS,
         //     A_i = P.V of tile i-1  +  scores of tile i   (64 MFMAs, 32 LDS fragment reads)        B_i = softmax of tile i   (VALU only),
         // and waves 4-7 (the second wave of every SIMD: a block's waves are dealt to the SIMDs cyclically) run half a tile out of step with waves 0-3.
-#ifdef MMDUET_ATTN_GRP_LSB
-        const int grp = wave & 1;               // (experiment: pairs the waves that do NOT share a SIMD)
-#else
         const int grp = wave >> 2;
-#endif
         f32x4_t st[RT][2][2];
         bf16x8_t pf[RT][2];
         static_assert(!ALLRING || NPC == 2, "counted waits below assume 4 DMAs per wave and tile");
@@ -593,11 +565,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
         // before barrier i.  A DMA issued beside bare MFMAs costs the wave 60-185 cycles, in a VALU stretch 25-60.
         auto seg_barrier = [&](int k) {
             if (k < ntile) { if (k + 1 < ntile) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-            ATS(3);                                  // (debug build: [3] = the DMA wait alone, [0] = barrier + DMA issue)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             if (grp == 1 && k + 2 < ntile) stage((k + 2) & (NSLOT - 1), kbeg + (long long)(k + 2) * KT);
-            ATS(0);
         };
         auto stage_after_softmax = [&](int i) { if (grp == 0 && i + 2 < ntile) stage((i + 2) & (NSLOT - 1), kbeg + (long long)(i + 2) * KT); };
         auto do_pv = [&](int i) {               // O += P(i) V(i)
@@ -720,26 +690,18 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
             if (grp == 1) seg_barrier(0);
             if (grp == 0) seg_barrier(0);
             if (wave_active) do_qk(0);                          // A_0
-            ATS(1);
             if (grp == 1) seg_barrier(1);
             if (wave_active) do_softmax(0);                     // B_0
             stage_after_softmax(0);
-            ATS(2);
             for (int i = 1; i < ntile; ++i) {
                 if (grp == 0) seg_barrier(i);
                 if (wave_active) do_a(i);                       // A_i = P.V(i - 1) + scores(i)
-                ATS(1);
                 if (grp == 1) seg_barrier(i + 1);
                 if (wave_active) do_softmax(i);                 // B_i
                 stage_after_softmax(i);
-                ATS(2);
-#ifdef MMDUET_ATTN_TIMING
-                ats_[4] += 1;
-#endif
             }
             if (grp == 0) seg_barrier(ntile);
             if (wave_active) do_pv(ntile - 1);                  // A_n
-            ATS(3);
         }
     } else {
     int slot = 0, ti = 0;
@@ -748,7 +710,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (k0 + KT < kend) stage(slot ^ 1, k0 + KT);
-            ATS(0);
         } else {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (wave 0 only: its reads of the previous tile are done before the loaders may refill that slot)
             __builtin_amdgcn_s_barrier();
@@ -777,7 +738,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) st[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[rt][c], st[rt][t], 0, 0, 0);
                 }
-            ATS(1);
             bf16x8_t pf[RT];
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {
@@ -814,21 +774,15 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void attn_gqa128_ke
                 l_run[rt] += psum;
                 pf[rt] = __builtin_bit_cast(bf16x8_t, pk);
             }
-            ATS(2);
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const bf16x8_t vfb = *reinterpret_cast<const bf16x8_t*>(Vt + (t * 16 + lr) * KT + (((h * 4 + lq) ^ vsw) * 8));
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) oacc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfb, pf[rt], oacc[rt][t], 0, 0, 0);
             }
-            ATS(3);
         }
-#ifdef MMDUET_ATTN_TIMING
-        ats_[4] += 1;
-#endif
     }
     }
-    if constexpr (RT == 2) { ATS_FLUSH; }
 
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -1162,24 +1116,18 @@ __global__ __launch_bounds__(256, 2) void attn_rowmajor_kernel(AttnP p) {
 //            distinct banks).  With the blocked [d-tile][quad][4][16] image of attn_rowmajor_kernel a 1 KB DMA block touches 32 cache lines and uses a quarter
 //            of each; row-major it touches 7-8 (measured: 153 -> 145 us).
 // Waves 0-1 bring K, waves 2-3 V: five 1 KB blocks each per tile.
-// What bounds it (profiles/r05_vit_attention.md, timing-only builds -DD72_DBG=n): the exponentials -- quarter rate on the vector port, a third of the matrix time at head_dim 72,
+// What bounds it (timing-only ablations of round 5: profiles/history/r05_vit_attention.md, r05_d72_ablate.txt): the exponentials -- quarter rate on the vector port, a third of the matrix time at head_dim 72,
 // -21 % without them; every other component is 3-9 %, and the savings add up (vector-issue-bound).  The ten transposing V reads of a half tile MUST be issued as one group:
 // interleaved with the P.V MFMAs (hipcc does that as soon as the half tile is behind a branch) the kernel returns different results from run to run.
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef D72_DBG
-#define D72_DBG 0
-#endif
 // The 16-deep MFMA that finishes a score tile (dims 64..71) reads the 32-deep MFMA's result as SrcC.  Issued DIRECTLY behind its producer (hipcc does that whenever its schedule of
 // the half tile shifts: twice this round, with a branch and with a scalar FMA in the softmax) the first row tile of every wave came back wrong and different from run to run -- with
 // one independent MFMA between the two it is right (the order of the source: rt 0, rt 1, tail rt 0, tail rt 1).  The barriers below pin exactly that order of the matrix instructions
 // (mask: everything but MFMAs may still cross); tests/test_attn_isa.py checks the distance in the listing.
 #define D72_MFMA_PIN 0x7F6
 // Round 6: the hazard is removed structurally -- the tail's 16-deep MFMA no longer takes the 32-deep MFMA's result as SrcC at all: it accumulates onto ZERO in registers of its own
-// and one v_add_f32 per score register folds it in where the softmax reads the scores (D72_TAIL_SEPARATE 1).  No MFMA of the kernel then reads another MFMA's result of a different
-// depth, in any instruction order; the pin and the ISA test stay as the second line.  0 = the chained form of round 5 (A/B: `make EXTRA_DEFS=-DD72_TAIL_SEPARATE=0`).
-#ifndef D72_TAIL_SEPARATE
-#define D72_TAIL_SEPARATE 1
-#endif
+// and one v_add_f32 per score register folds it in where the softmax reads the scores (the "separate tail", D72_TAIL_SEPARATE in the documents).  No MFMA of the kernel then reads
+// another MFMA's result of a different depth, in any instruction order; the pin and the ISA test stay as the second line.
 template <bool F16>
 __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
     constexpr int WAVES = 4, RT = 2, NC = 2, DVT = 5, D = 72, KT = 64, NSLOT = 2;
@@ -1273,8 +1221,8 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
     for (int i = 0; i < ntile; ++i) {
         const int k0 = i * KT;
         // this wave's five blocks of tile i have landed (nothing younger is in flight yet); the barrier publishes everybody's and retires the slot of tile i - 1
-        if (D72_DBG != 8) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier(); }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
         if (i + NSLOT - 1 < ntile) stage((i + NSLOT - 1) % NSLOT, k0 + (NSLOT - 1) * KT);
         if (!wave_active) continue;
         const bf16_t* Ks = ring72 + (i % NSLOT) * (2 * IMG);
@@ -1284,35 +1232,28 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && k0 + 32 >= kend) break;          // the second half of the last tile lies wholly behind the keys (729 = 11 tiles + 25 keys): its P is 0, its exponentials -- the limiter of this kernel -- are not computed
             f32x4_t st[RT][2];
-#if D72_TAIL_SEPARATE
-            f32x4_t tt[RT][2];          // dims 64..71 of the scores: their own accumulators (see D72_TAIL_SEPARATE)
-#endif
+            f32x4_t tt[RT][2];          // dims 64..71 of the scores: their own accumulators (the separate tail, above)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) { st[rt][0] = f32x4_t{0, 0, 0, 0}; st[rt][1] = f32x4_t{0, 0, 0, 0}; }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
-                    bf16x8_t kf = D72_DBG == 6 ? qf[0][c] : *reinterpret_cast<const bf16x8_t*>(Ks + (h * 32 + t * 16 + lr) * KLD + c * 32 + lq * 8);
+                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(Ks + (h * 32 + t * 16 + lr) * KLD + c * 32 + lq * 8);
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
-                        if (D72_DBG == 3) { st[rt][t][0] += (float)kf[0] * (float)qf[rt][c][0]; } else st[rt][t] = mfma16<F16>(kf, qf[rt][c], st[rt][t]);
+                        st[rt][t] = mfma16<F16>(kf, qf[rt][c], st[rt][t]);
                         if (c == NC - 1) __builtin_amdgcn_sched_barrier(D72_MFMA_PIN);
                     }
                 }
                 // (rows lr >= 8 read the tail from the DUPLICATE in the tenth place: rows lr and lr + 8 are 1280 B = 0 banks apart, the duplicate sits 4 banks further -- the b64 reads of a
                 //  32-lane group then fall on distinct banks; lq >= 2 reads the other copy's bytes: finite, against zeros)
-                const s16x4_t kt = D72_DBG == 6 ? qt[0] : *reinterpret_cast<const s16x4_t*>(Ks + (h * 32 + t * 16 + lr) * KLD + 64 + ((lr >> 3) & 1) * 8 + lq * 4);
+                const s16x4_t kt = *reinterpret_cast<const s16x4_t*>(Ks + (h * 32 + t * 16 + lr) * KLD + 64 + ((lr >> 3) & 1) * 8 + lq * 4);
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) {
-#if D72_TAIL_SEPARATE
                     const f32x4_t z = {0, 0, 0, 0};
-                    if (D72_DBG == 3) { tt[rt][t] = z; tt[rt][t][1] = (float)kt[0]; } else if constexpr (F16) tt[rt][t] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, kt), __builtin_bit_cast(f16x4_t, qt[rt]), z, 0, 0, 0);
+                    if constexpr (F16) tt[rt][t] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, kt), __builtin_bit_cast(f16x4_t, qt[rt]), z, 0, 0, 0);
                     else tt[rt][t] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kt, qt[rt], z, 0, 0, 0);
-#else
-                    if (D72_DBG == 3) { st[rt][t][1] += (float)kt[0]; } else if constexpr (F16) st[rt][t] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, kt), __builtin_bit_cast(f16x4_t, qt[rt]), st[rt][t], 0, 0, 0);
-                    else st[rt][t] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(kt, qt[rt], st[rt][t], 0, 0, 0);
-#endif
                     __builtin_amdgcn_sched_barrier(D72_MFMA_PIN);
                 }
             }
@@ -1323,11 +1264,7 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
-#if D72_TAIL_SEPARATE
                     for (int r = 0; r < 4; ++r) sv[t * 4 + r] = st[rt][t][r] + tt[rt][t][r];
-#else
-                    for (int r = 0; r < 4; ++r) sv[t * 4 + r] = st[rt][t][r];
-#endif
                 if (need_mask) {                  // wave-uniform: the tile at the end of the keys only
                     int lim = (row_ok[rt] ? kend : 0) - (k0 + h * 32 + lq * 4);
                     asm volatile("" : "+v"(lim));             // (keeps this a BRANCH and the compares inside it: hipcc otherwise evaluates 7 compares + 8 selects per row tile in EVERY tile)
@@ -1338,8 +1275,8 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
                             if (!(t * 16 + r < lim)) sv[t * 4 + r] = -INFINITY;
                 }
                 // (a chain, not a tree: every step but the last folds into a three-input v_max3_f32 -- 4 instructions for the 8 values instead of 7; max is exact in any order)
-                float mx = D72_DBG == 7 ? sv[0] : fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(sv[0], sv[1]), sv[2]), sv[3]), sv[4]), sv[5]), sv[6]), sv[7]);
-                if (D72_DBG != 7) mx = quad_lanes_max(mx);
+                float mx = fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(fmaxf(sv[0], sv[1]), sv[2]), sv[3]), sv[4]), sv[5]), sv[6]), sv[7]);
+                mx = quad_lanes_max(mx);
                 mx *= p.scale_log2;
                 if (mx > m_run[rt] + ATTN_DEFER) {
                     const float alpha = __builtin_amdgcn_exp2f(m_run[rt] - mx);
@@ -1354,8 +1291,8 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {          // (two scalar FMAs: v_pk_fma_f32 is the same fused operation per element but measures SLOWER here -- 147.6 vs 145.0 us per layer)
                     const float a0 = fmaf(sv[e], p.scale_log2, neg_m), a1 = fmaf(sv[e + 1], p.scale_log2, neg_m);
-                    const float p0 = D72_DBG == 1 ? a0 : __builtin_amdgcn_exp2f(a0), p1 = D72_DBG == 1 ? a1 : __builtin_amdgcn_exp2f(a1);
-                    if (D72_DBG != 2) { psum += p0; psum += p1; }
+                    const float p0 = __builtin_amdgcn_exp2f(a0), p1 = __builtin_amdgcn_exp2f(a1);
+                    psum += p0; psum += p1;
                     pk[e] = (short)f2raw<F16>(p0); pk[e + 1] = (short)f2raw<F16>(p1);
                 }
                 l_run[rt] += psum;
@@ -1371,7 +1308,6 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
                 const char __attribute__((address_space(3)))* vb = (const char __attribute__((address_space(3)))*)Vs + ((h * 32 + lq * 4 + (lr >> 2)) * 160 + (lr & 3) * 8);
 #pragma unroll
                 for (int t = 0; t < DVT; ++t) {
-                    if (D72_DBG == 5) { vlo[t] = qt[0]; vhi[t] = qt[1]; continue; }
                     vlo[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(vb + t * 32));
                     vhi[t] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)(vb + t * 32 + 2560));
                 }
@@ -1383,7 +1319,7 @@ __global__ __launch_bounds__(256, 4) void attn_d72_ring_kernel(AttnP p) {
                 s16x8_t vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 bf16x8_t vfb = __builtin_bit_cast(bf16x8_t, vf);
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) { if (D72_DBG == 4) { oacc[rt][t][0] += (float)vfb[0] * (float)pf[rt][0]; } else oacc[rt][t] = mfma16<F16>(vfb, pf[rt], oacc[rt][t]); }
+                for (int rt = 0; rt < RT; ++rt) oacc[rt][t] = mfma16<F16>(vfb, pf[rt], oacc[rt][t]);
             }
         }
     }

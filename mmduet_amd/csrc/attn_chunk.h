@@ -1,5 +1,5 @@
 // attn_chunk.h -- attn_gqa128_chunk_kernel: the LLM attention of a multi-frame chunk (>= 1024 stacked rows per kv head; head_dim 128, bf16, causal GQA with a query offset
-// over the KV arena; Qwen2Attention.forward, transformers qwen2/modeling_qwen2.py:200-240).  Included by attn.hip (AttnP, xcd helpers, quad_lanes_max, ATTN_DEFER, ATS_*).
+// over the KV arena; Qwen2Attention.forward, transformers qwen2/modeling_qwen2.py:200-240).  Included by attn.hip (AttnP, xcd helpers, quad_lanes_max, ATTN_DEFER).
 //
 // The wave program is attn_gqa128_kernel<2, 4, 8>'s of round 3 (256 query rows per block = 8 waves x 2 row tiles, four-slot K / V ring fed by all eight waves, a tile =
 // two barrier-separated segments -- A_i = P.V(i-1) + scores(i), B_i = softmax(i) -- with waves 4-7 one segment behind waves 0-3, so that on every SIMD one wave is in its MFMA
@@ -14,12 +14,10 @@
 //   with the same integer formulas -- no markers, nothing to initialise: a unit that one block covers alone is written straight to the output, and the merge skips it.
 //
 // Rounding points = attn_gqa128_kernel's; a row's result depends on where its unit is cut (fp32 summation order of the partials), deterministically.
+// (What each component of the loop costs -- timing-only ablations of round 5, no longer in the source: profiles/history/r05_chunk_ablate.txt, r05_attention_chunk.md.)
 #pragma once
 
 // unit geometry: ChunkTab (attn_plan.h, where plan_gqa128_chunk builds it -- the host side of the formulas below -- and decides whether this form takes a launch)
-#ifndef CHUNK_DBG
-#define CHUNK_DBG 0          // timing-only ablations (wrong results): tools/probes/chunk_ablate.sh
-#endif
 // block b of nb owns linear tiles [b * W / nb, (b + 1) * W / nb)
 __device__ __forceinline__ long long chunk_cut(long long W, int nb, int b) { return (W * b) / nb; }
 __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, ChunkTab tab) {
@@ -82,7 +80,6 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
         first_seg = false;
 
         auto stage = [&](int slot, long long k0) {
-            if (CHUNK_DBG == 9) return;
             bf16_t* ks = kv + slot * 2 * TILE;
             bf16_t* vt = ks + TILE;
             // (the tile's two bases as OPAQUE scalar pairs: left visible, hipcc re-associates base + tile offset + lane offset inside the tile loop and falls back to 64-bit
@@ -140,10 +137,9 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
         // start of global segment sg: this wave's pieces of tile k have landed (tile k + 1 may stay in flight), every LDS read of the previous interval is done, block barrier,
         // then (group 1 here, group 0 behind its softmax) tile k + 2 goes out into the slot of tile k - 2
         auto seg_barrier = [&](int k) {
-            if (CHUNK_DBG != 8) {
             if (k < ntile) { if (k + 1 < ntile) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier(); }
+            __builtin_amdgcn_s_barrier();
             if (grp == 1 && k + 2 < ntile) stage((k + 2) & (NSLOT - 1), kbeg + (long long)(k + 2) * KT);
         };
         auto stage_after_softmax = [&](int i) { if (grp == 0 && i + 2 < ntile) stage((i + 2) & (NSLOT - 1), kbeg + (long long)(i + 2) * KT); };
@@ -180,12 +176,12 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
             if constexpr (g < 4) {
                 constexpr int h = g >> 1, tq = (g & 1) * 4;
 #pragma unroll
-                for (int u = 0; u < 4; ++u) fr[u] = CHUNK_DBG == 5 ? qf[0][u] : *reinterpret_cast<const bf16x8_t*>(Vt + ((tq + u) * 16 + lr) * KT + (((h * 4 + lq) ^ vsw) * 8));
+                for (int u = 0; u < 4; ++u) fr[u] = *reinterpret_cast<const bf16x8_t*>(Vt + ((tq + u) * 16 + lr) * KT + (((h * 4 + lq) ^ vsw) * 8));
             } else {
                 constexpr int h = (g - 4) >> 1, c0 = ((g - 4) & 1) * 2;
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    fr[u] = CHUNK_DBG == 6 ? qf[1][u] : *reinterpret_cast<const bf16x8_t*>(Ks + (h * 32 + (lr >> 2) * 8 + (u & 1) * 4 + (lr & 3)) * D + ((((c0 + (u >> 1)) * 4 + lq) ^ lr) * 8));
+                    fr[u] = *reinterpret_cast<const bf16x8_t*>(Ks + (h * 32 + (lr >> 2) * 8 + (u & 1) * 4 + (lr & 3)) * D + ((((c0 + (u >> 1)) * 4 + lq) ^ lr) * 8));
             }
         };
         auto a_mma = [&](auto G_, const bf16x8_t (&fr)[4]) {
@@ -195,7 +191,7 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
 #pragma unroll
-                    for (int rt = 0; rt < RT; ++rt) { if (CHUNK_DBG == 4) oacc[rt][tq + u][0] += (float)fr[u][0] * (float)pf[rt][h][0]; else oacc[rt][tq + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[u], pf[rt][h], oacc[rt][tq + u], 0, 0, 0); }
+                    for (int rt = 0; rt < RT; ++rt) oacc[rt][tq + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[u], pf[rt][h], oacc[rt][tq + u], 0, 0, 0);
             } else {
                 constexpr int h = (g - 4) >> 1, c0 = ((g - 4) & 1) * 2;
 #pragma unroll
@@ -203,8 +199,7 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
 #pragma unroll
                     for (int rt = 0; rt < RT; ++rt) {
                         const int c = c0 + (u >> 1), t = u & 1;
-                        if (CHUNK_DBG == 3) { if (c == 0) st[rt][h][t] = f32x4_t{0, 0, 0, 0}; st[rt][h][t][0] += (float)fr[u][0] * (float)qf[rt][c][0]; }
-                        else st[rt][h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[u], qf[rt][c], c == 0 ? f32x4_t{0, 0, 0, 0} : st[rt][h][t], 0, 0, 0);
+                        st[rt][h][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[u], qf[rt][c], c == 0 ? f32x4_t{0, 0, 0, 0} : st[rt][h][t], 0, 0, 0);
                     }
             }
         };
@@ -236,9 +231,9 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
                             for (int r = 0; r < 4; ++r)
                                 if (!(h * 32 + t * 4 + r < rel)) SV(h, t, r) = -INFINITY;
                 }
-                float mx = CHUNK_DBG == 7 ? SV(0, 0, 0) : fmaxf(fmaxf(fmaxf(fmaxf(SV(0, 0, 0), SV(0, 0, 1)), fmaxf(SV(0, 0, 2), SV(0, 0, 3))), fmaxf(fmaxf(SV(0, 1, 0), SV(0, 1, 1)), fmaxf(SV(0, 1, 2), SV(0, 1, 3)))),
+                float mx = fmaxf(fmaxf(fmaxf(fmaxf(SV(0, 0, 0), SV(0, 0, 1)), fmaxf(SV(0, 0, 2), SV(0, 0, 3))), fmaxf(fmaxf(SV(0, 1, 0), SV(0, 1, 1)), fmaxf(SV(0, 1, 2), SV(0, 1, 3)))),
                                  fmaxf(fmaxf(fmaxf(SV(1, 0, 0), SV(1, 0, 1)), fmaxf(SV(1, 0, 2), SV(1, 0, 3))), fmaxf(fmaxf(SV(1, 1, 0), SV(1, 1, 1)), fmaxf(SV(1, 1, 2), SV(1, 1, 3)))));
-                if (CHUNK_DBG != 7) mx = quad_lanes_max(mx);
+                mx = quad_lanes_max(mx);
                 mx *= p.scale_log2;
                 if (mx > m_run[rt] + ATTN_DEFER) {
                     const float alpha = __builtin_amdgcn_exp2f(m_run[rt] - mx);
@@ -253,7 +248,7 @@ __global__ __launch_bounds__(512, 1) void attn_gqa128_chunk_kernel(AttnP p, Chun
                 for (int h = 0; h < 2; ++h) {
                     s16x8_t pk;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { const float a_ = fmaf(SV(h, e >> 2, e & 3), p.scale_log2, neg_m); float pv = CHUNK_DBG == 1 ? a_ : __builtin_amdgcn_exp2f(a_); if (CHUNK_DBG != 2) psum += pv; pk[e] = (short)f2bf(pv); }
+                    for (int e = 0; e < 8; ++e) { const float a_ = fmaf(SV(h, e >> 2, e & 3), p.scale_log2, neg_m); const float pv = __builtin_amdgcn_exp2f(a_); psum += pv; pk[e] = (short)f2bf(pv); }
                     pf[rt][h] = __builtin_bit_cast(bf16x8_t, pk);
                 }
 #undef SV

@@ -20,13 +20,9 @@
 //   padding.  <= 256 registers per wave: hipcc then emits the VGPR form of every MFMA (beyond 256 it switches ALL of them to the AGPR form and pays an accvgpr move per score).
 //
 // Rounding points = attn_gqa128_kernel's: scores fp32, statistics fp32, P rounded to bf16 before P.V, l = fp32 sum of the UNROUNDED probabilities.
+// (What each component of the loop costs -- timing-only ablations of round 5, no longer in the source: profiles/history/r05_attn_small_s.md.)
 #pragma once
 #include <type_traits>
-// timing-only ablations (WRONG results; tools/attn_w1_ablate.sh builds one debug library per value, never shipped): 1 no exp2, 2 no row-sum adds, 3 no score MFMAs,
-// 4 no P.V MFMAs, 5 no fragment reads after the first three, 6 no tile barrier / DMA wait, 7 no maximum chain
-#ifndef W1_DBG
-#define W1_DBG 0
-#endif
 
 template <int RT, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void attn_gqa128_w1_kernel(AttnP p) {
@@ -81,7 +77,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void attn_gqa128_w1_kernel(A
     // tile t's K / V have landed for everybody and the slot of tile t - 2 (its V was last read two phases ago) is free: this wave's pieces of tile t are complete once at
     // most the pieces of tile t + 1 (2 NPC DMAs) are outstanding; then tile t + 2 goes out.
     auto sync_tile = [&](int t) {
-        if constexpr (W1_DBG == 6) { if (t + 2 < ntile) stage(t + 2); return; }
         if (t + 1 < ntile || t + 1 <= 2) { if constexpr (NPC == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }          // (t + 1 <= 2: one of the three opening stages, real or not)
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -164,18 +159,15 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void attn_gqa128_w1_kernel(A
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
-                if constexpr (W1_DBG != 5) {
                 if (g + 3 < 8) { if constexpr (WITH_S) fr[(g + 3) & 3] = kfrag(Ks, h, g + 3); }
                 else if constexpr (NEXT) fr[(g + 3) & 3] = vfrag(Vn, hv, g + 3 - 8);
-                }
 #pragma unroll
                 for (int rt = 0; rt < RA; ++rt) {
-                    if constexpr (WITH_S && W1_DBG != 3)
+                    if constexpr (WITH_S)
                         st[bn][rt][g & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[g & 3], qf[rt][g >> 1], g < 2 ? f32x4_t{0, 0, 0, 0} : st[bn][rt][g & 1], 0, 0, 0);
-                    if constexpr (W1_DBG == 1) ex[rt][g] = ar[rt] * 0.001f; else
                     ex[rt][g] = __builtin_amdgcn_exp2f(ar[rt]);
                     if (g + 1 < 8) ar[rt] = fmaf(st[bc][rt][(g + 1) >> 2][(g + 1) & 3], scale, neg_m[rt]);
-                    if (g >= 1 && W1_DBG != 2) l_run[rt] += ex[rt][g - 1];          // (one step behind its exponential: no wait for the transcendental pipe)
+                    if (g >= 1) l_run[rt] += ex[rt][g - 1];          // (one step behind its exponential: no wait for the transcendental pipe)
                     if (g >= 2 && (g & 1) == 0) {
                         const bf16x2_t v2 = __builtin_convertvector(f32x2_t{ex[rt][g - 2], ex[rt][g - 1]}, bf16x2_t);
                         pk[rt][(g >> 1) - 1] = __builtin_bit_cast(unsigned, v2);
@@ -222,15 +214,13 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void attn_gqa128_w1_kernel(A
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
-                if constexpr (W1_DBG != 5) {
                 if (t + 3 < 8) fr[(t + 3) & 3] = vfrag(Vt, h, t + 3);
                 else if constexpr (NEXT) fr[(t + 3) & 3] = kfrag(Kn, hk, t + 3 - 8);
-                }
 #pragma unroll
                 for (int rt = 0; rt < RA; ++rt) {
-                    if constexpr (W1_DBG != 4) oacc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[t & 3], pf[rt], oacc[rt][t], 0, 0, 0);
+                    oacc[rt][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[t & 3], pf[rt], oacc[rt][t], 0, 0, 0);
                     // the vector chain of this row tile, one link per step
-                    if constexpr (WITH_X && W1_DBG != 7) {
+                    if constexpr (WITH_X) {
                         const f32x4_t s0 = st[bx_][rt][0], s1 = st[bx_][rt][1];
                         if (t == 0) mxr[rt] = fmaxf(fmaxf(s0[0], s0[1]), s0[2]);
                         if (t == 1) mxr[rt] = fmaxf(fmaxf(mxr[rt], s0[3]), s1[0]);
@@ -245,7 +235,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void attn_gqa128_w1_kernel(A
                 __builtin_amdgcn_sched_barrier(0);
             }
             bool any = false;
-            if constexpr (WITH_X && W1_DBG != 7) {
+            if constexpr (WITH_X) {
 #pragma unroll
                 for (int rt = 0; rt < RA; ++rt) { asm volatile("" : "+v"(m_run[rt]), "+v"(neg_m[rt]), "+v"(alpha[rt])); any |= mvd[rt]; }          // (anchors, as in phase A)
             }

@@ -687,13 +687,13 @@ template <int N_, typename F> __device__ __forceinline__ void stream_static_for(
     if constexpr (N_ > 0) { stream_static_for<N_ - 1>(f); f(std::integral_constant<int, N_ - 1>{}); }
 }
 
-template <int MT, int NT, int WK, int KS, int NB, int DBG = 0, int WN = 4>          // DBG (timing only, wrong results): 1 = W stream alone (no X DMA, no MFMA), 2 = no W loads
+template <int MT, int NT, int WK, int KS, int NB, int WN = 4>
 __global__ __launch_bounds__(64 * WN * WK) void gemm_stream_kernel(GemmP p, int KT, int kt_per_block) {
     constexpr int NWAVE = WN * WK, KSB = WK * KS;
     constexpr int XPIECES = MT * KSB;                        // 1 KB pieces of the step's X slab
-    constexpr int XP = DBG == 1 ? 0 : (XPIECES + NWAVE - 1) / NWAVE;       // LDS-DMAs per wave and step: the SAME count for every wave (the hand-counted waits need that): where the
-                                                                           // pieces do not divide evenly, the surplus DMAs re-load pieces 0.. (same bytes to the same place)
-    constexpr int NWL = DBG == 2 ? 0 : NT * KS;              // W loads per wave and step
+    constexpr int XP = (XPIECES + NWAVE - 1) / NWAVE;        // LDS-DMAs per wave and step: the SAME count for every wave (the hand-counted waits need that): where the
+                                                             // pieces do not divide evenly, the surplus DMAs re-load pieces 0.. (same bytes to the same place)
+    constexpr int NWL = NT * KS;                             // W loads per wave and step
     constexpr int LA = NB - 1;
     constexpr int ISSUE = NWL + XP;
     constexpr int VM_STEP = (LA - 1) * ISSUE;
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_stream_kernel(GemmP p, int 
     // X piece pi = (m-tile pi / KSB, k-tile pi % KSB of the step): lane -> row srow, 16-byte chunk spos ^ sswz (the ring GEMM's piece image)
     const int srow = lane >> 2, spos = lane & 3;
     const int sswz = (0x1230 >> (((srow >> 2) & 3) * 4)) & 3;
-    unsigned xo[XP + 1];
+    unsigned xo[XP];
 #pragma unroll
     for (int j = 0; j < XP; ++j) {
         const int pi = (wave + NWAVE * j) % XPIECES;
@@ -749,12 +749,10 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_stream_kernel(GemmP p, int 
 
     auto issue = [&](int step, auto buf_c) {          // everything step `step` needs, into register buffer / ring slot `buf`
         constexpr int buf = decltype(buf_c)::value;
-        if constexpr (DBG != 2) {
 #pragma unroll
-            for (int j = 0; j < NT; ++j)
+        for (int j = 0; j < NT; ++j)
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) load_w(wb[buf][j][ks], j, ks, step);
-        }
+            for (int ks = 0; ks < KS; ++ks) load_w(wb[buf][j][ks], j, ks, step);
 #pragma unroll
         for (int j = 0; j < XP; ++j) dma_x(buf, step, j);
     };
@@ -775,11 +773,6 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_stream_kernel(GemmP p, int 
             const int ktl = wk * KS + ks;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
-                if constexpr (DBG == 1) {          // keep the W registers live without the matrix pipe
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) if (i == 0) { const u32x4_t w4 = __builtin_bit_cast(u32x4_t, wb[cur][j][ks]); asm volatile("" :: "v"(w4[0]), "v"(w4[1]), "v"(w4[2]), "v"(w4[3])); }
-                    continue;
-                }
                 const bf16x8_t xf = *reinterpret_cast<const bf16x8_t*>(xs + (i * KSB + ktl) * 512 + aoff);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[cur][j][ks], xf, acc[i][j], 0, 0, 0);
@@ -881,7 +874,7 @@ static void launch_gemv16(const GemmP& p, const GemmPlan& pl, const GemvChain* c
 #undef GEMV16_GO
 }
 
-template <int MT, int NT, int WK, int KS, int NB, int DBG = 0, int WN = 4>
+template <int MT, int NT, int WK, int KS, int NB, int WN>
 static void launch_stream_t(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
     constexpr int KSB = WK * KS;
     constexpr size_t ring = (size_t)NB * MT * KSB * 1024, red = (size_t)(WK - 1) * WN * MT * NT * 1024;
@@ -889,20 +882,20 @@ static void launch_stream_t(const GemmP& p, const GemmPlan& pl, hipStream_t st) 
     static bool attr_set[64] = {};
     int adev = 0; hipGetDevice(&adev);
     if (smem > 65536 && adev >= 0 && adev < 64 && !attr_set[adev]) {
-        hipFuncSetAttribute((const void*)gemm_stream_kernel<MT, NT, WK, KS, NB, DBG, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        hipFuncSetAttribute((const void*)gemm_stream_kernel<MT, NT, WK, KS, NB, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         attr_set[adev] = true;
     }
-    hipLaunchKernelGGL((gemm_stream_kernel<MT, NT, WK, KS, NB, DBG, WN>), dim3(pl.gx, pl.splits), dim3(64 * WN * WK), smem, st, p, p.K >> 5, pl.kt_per_block);
+    hipLaunchKernelGGL((gemm_stream_kernel<MT, NT, WK, KS, NB, WN>), dim3(pl.gx, pl.splits), dim3(64 * WN * WK), smem, st, p, p.K >> 5, pl.kt_per_block);
     if (pl.reduce) launch_reduce(splitk_reduce_kernel<bf16_t>, p, pl.splits, st);
 }
 template <int MT, int NT, int WK, int KS, int NB>
 static void launch_stream_wn(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
     switch (pl.wn) {
-        case 5: return launch_stream_t<MT, NT, WK, KS, NB, 0, 5>(p, pl, st);
-        case 6: return launch_stream_t<MT, NT, WK, KS, NB, 0, 6>(p, pl, st);
-        case 7: return launch_stream_t<MT, NT, WK, KS, NB, 0, 7>(p, pl, st);
-        case 8: return launch_stream_t<MT, NT, WK, KS, NB, 0, 8>(p, pl, st);
-        default: return launch_stream_t<MT, NT, WK, KS, NB, 0, 4>(p, pl, st);
+        case 5: return launch_stream_t<MT, NT, WK, KS, NB, 5>(p, pl, st);
+        case 6: return launch_stream_t<MT, NT, WK, KS, NB, 6>(p, pl, st);
+        case 7: return launch_stream_t<MT, NT, WK, KS, NB, 7>(p, pl, st);
+        case 8: return launch_stream_t<MT, NT, WK, KS, NB, 8>(p, pl, st);
+        default: return launch_stream_t<MT, NT, WK, KS, NB, 4>(p, pl, st);
     }
 }
 static void launch_stream(const GemmP& p, const GemmPlan& pl, hipStream_t st) {          // (MT, NT) -> the steps WK x KS (plan_stream's KSB) and the ring depth NB of the instantiation
@@ -1117,16 +1110,16 @@ static void* ring_dump_slot() {
     return dump_slot[dev];
 }
 
-template <int WN, bool M32, int NS, bool EARLY, bool F16 = false>
+template <int WN, bool F16 = false>
 static hipError_t launch_ringx_t(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
     constexpr int BN = 64 * WN;
     const dim3 grid(pl.gx, 1, pl.splits);
     const int KT = p.K >> 5;
-    const size_t smem = NS * (256 * 32 + BN * 32) * sizeof(bf16_t);          // 96 KB / 72 KB (3 slots), 128 KB / 96 KB (4)
+    const size_t smem = 3 * (256 * 32 + BN * 32) * sizeof(bf16_t);          // three ring slots: 96 KB (WN = 4) / 72 KB (WN = 2)
     static bool attr_set[64] = {};          // per device (hipFuncSetAttribute applies to the current device's code object)
     int adev = 0; hipGetDevice(&adev);
     if (adev >= 0 && adev < 64 && !attr_set[adev]) {
-#define RX_ATTR(E) hipFuncSetAttribute((const void*)gemm_ringx_kernel<E, WN, M32, NS, EARLY, 0, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+#define RX_ATTR(E) hipFuncSetAttribute((const void*)gemm_ringx_kernel<E, WN, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         RX_ATTR(EPI_NONE) RX_ATTR(EPI_GELU_TANH) RX_ATTR(EPI_RESID)
         if constexpr (!F16) { RX_ATTR(EPI_GELU_ERF) RX_ATTR(EPI_SWIGLU) }
 #undef RX_ATTR
@@ -1136,7 +1129,7 @@ static hipError_t launch_ringx_t(const GemmP& p, const GemmPlan& pl, hipStream_t
     GemmP q = p;
     q.dump = ring_dump_slot();
     if (!q.dump) return hipErrorOutOfMemory;
-#define RX_GO(E) hipLaunchKernelGGL((gemm_ringx_kernel<E, WN, M32, NS, EARLY, 0, F16>), grid, block, smem, st, q, KT)
+#define RX_GO(E) hipLaunchKernelGGL((gemm_ringx_kernel<E, WN, F16>), grid, block, smem, st, q, KT)
     switch (p.epi) {          // (the IEEE-half form has the plain / GELU(tanh) / residual epilogues: the plan holds no other for it)
         case EPI_GELU_TANH: RX_GO(EPI_GELU_TANH); break;
         case EPI_GELU_ERF: if constexpr (!F16) RX_GO(EPI_GELU_ERF); break;
@@ -1148,72 +1141,15 @@ static hipError_t launch_ringx_t(const GemmP& p, const GemmPlan& pl, hipStream_t
     if (pl.reduce) launch_reduce(splitk_reduce_kernel<bf16_t>, p, pl.splits, st);
     return hipSuccess;
 }
-// the instantiations of gemm_ringx_kernel in the library (plan_ring, gemm_plan.h, says what they are for and rejects the flags of the others)
+// the instantiations of gemm_ringx_kernel in the library (plan_ring, gemm_plan.h, says what they are for)
 static hipError_t launch_ringx(const GemmP& p, const GemmPlan& pl, hipStream_t st) {
-    if (pl.f16) return launch_ringx_t<4, false, 3, true, true>(p, pl, st);
-    return pl.wn == 4 ? launch_ringx_t<4, false, 3, true>(p, pl, st) : launch_ringx_t<2, false, 3, true>(p, pl, st);
+    if (pl.f16) return launch_ringx_t<4, true>(p, pl, st);
+    return pl.wn == 4 ? launch_ringx_t<4>(p, pl, st) : launch_ringx_t<2>(p, pl, st);
 }
 
 static inline void set_plan(const GemmArgs& a, const GemmPlan& pl) {
     if (a.plan_out) { a.plan_out[0] = pl.kernel; a.plan_out[1] = pl.tiles; a.plan_out[2] = pl.splits; a.plan_out[3] = pl.blocks; }
 }
-
-#ifdef MMDUET_DEBUG_VARIANTS
-// Timing experiments of tools/bench_gemm.py (`make DEBUG_VARIANTS=1`; never in the library otherwise; most give WRONG results): variants 92-99 run gemm_ringx_kernel's DBG
-// modes, 300-339 sweep configurations of gemm_stream_kernel at M <= 64.  -> true: the variant was one of these and *err is its launch's result.
-template <int DBG, int NS = 3>
-static hipError_t launch_ringx_dbg(const GemmP& p, const GemmArgs& a, hipStream_t st) {
-    GemmPlan pl;
-    pl.kernel = GEMM_K_RING256; pl.tiles = cdiv(a.N, 256) * cdiv(a.M, 256); pl.blocks = pl.tiles <= 256 ? pl.tiles : 256;
-    set_plan(a, pl);
-    const size_t smem = NS * (256 * 32 + 256 * 32) * sizeof(bf16_t);
-    hipFuncSetAttribute((const void*)gemm_ringx_kernel<EPI_NONE, 4, false, NS, true, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL((gemm_ringx_kernel<EPI_NONE, 4, false, NS, true, DBG>), dim3(pl.blocks), dim3(512), smem, st, p, a.K >> 5);
-    return hipGetLastError();
-}
-static bool launch_debug_variant(GemmP p, const GemmArgs& a, hipStream_t st, hipError_t* err) {
-    const int variant = a.variant;
-    p.W = a.Wp;
-    if (variant >= 92 && variant <= 99) {
-        if (!big_packed_ok(MMD_BF16, a, 16) || (a.N % 32) != 0) { *err = hipErrorInvalidValue; return true; }
-        switch (variant) {
-            case 92: *err = launch_ringx_dbg<8, 4>(p, a, st); break;          // DBG 8 on the 4-slot ring
-            case 93: *err = launch_ringx_dbg<7>(p, a, st); break;
-            case 94: *err = launch_ringx_dbg<6>(p, a, st); break;
-            case 95: *err = launch_ringx_dbg<5>(p, a, st); break;
-            case 99: *err = launch_ringx_dbg<4>(p, a, st); break;
-            case 96: *err = launch_ringx_dbg<1>(p, a, st); break;
-            case 97: *err = launch_ringx_dbg<2>(p, a, st); break;
-            default: *err = launch_ringx_dbg<3>(p, a, st); break;
-        }
-        return true;
-    }
-    if (variant >= 300 && variant < 340 && a.M <= 64 && a.Wp) {
-        p.slabs = a.epi == EPI_SWIGLU ? 0 : 1;
-        GemmArgs b = a; int dummy = 0; if (a.epi != EPI_SWIGLU) { b.slabs_out = &dummy; b.epi = EPI_NONE; p.epi = EPI_NONE; }
-        const bool two = a.epi == EPI_SWIGLU;
-        GemmPlan pl;
-#define SGO(NT_, WK_, KS_, NB_, DBG_, WN_, SPLIT_) (stream_geometry(pl, b, 4, NT_, WK_ * KS_, WN_, SPLIT_), set_plan(a, pl), launch_stream_t<4, NT_, WK_, KS_, NB_, DBG_, WN_>(p, pl, st))
-#define SCFG(id, WK_, KS_, NB_, DBG_) case id: if (two) SGO(2, WK_, KS_, NB_, DBG_, 4, 0); else SGO(1, WK_, KS_, NB_, DBG_, 4, 0); break;
-        switch (variant - 300) {
-            SCFG(0, 2, 2, 4, 0) SCFG(1, 1, 4, 3, 0) SCFG(2, 4, 1, 4, 0) SCFG(3, 2, 4, 3, 0) SCFG(4, 1, 4, 4, 0) SCFG(5, 4, 2, 3, 0) SCFG(7, 2, 2, 6, 0)
-            SCFG(10, 2, 2, 4, 1) SCFG(11, 1, 4, 3, 1) SCFG(12, 2, 2, 4, 2) SCFG(13, 1, 4, 3, 2)
-            // balanced decompositions: 5 pairs per block (gate_up: 237 blocks), 7 n-tiles x 8 K chunks (down / o: 256 blocks)
-            case 20: if (two) SGO(2, 2, 2, 4, 0, 5, 0); else SGO(1, 2, 2, 4, 0, 7, 8); break;
-            case 21: if (two) SGO(2, 3, 2, 3, 0, 5, 0); else SGO(1, 2, 2, 4, 0, 7, 4); break;
-            case 22: if (two) SGO(2, 2, 2, 4, 1, 5, 0); else SGO(1, 2, 2, 4, 1, 7, 8); break;
-            case 23: if (two) SGO(2, 1, 4, 3, 0, 5, 0); else SGO(1, 1, 4, 3, 0, 7, 8); break;
-            case 24: if (two) SGO(2, 2, 2, 4, 0, 8, 0); else SGO(1, 2, 2, 4, 0, 7, 16); break;
-            default: *err = hipErrorInvalidValue; return true;
-        }
-#undef SCFG
-#undef SGO
-        *err = hipGetLastError();
-        return true;
-    }
-    return false;
-}
-#endif
 
 template <typename T>
 static hipError_t launch_t(const GemmArgs& a, const GemmPlan& pl, hipStream_t st) {
@@ -1224,9 +1160,6 @@ static hipError_t launch_t(const GemmArgs& a, const GemmPlan& pl, hipStream_t st
     p.vec = (sizeof(T) == 2 && (a.ldx % 8) == 0 && (a.ldw % 8) == 0 && ((uintptr_t)a.X % 16) == 0 && ((uintptr_t)a.W % 16) == 0) ? 1 : 0;
     if (a.ring_slabs_out) *a.ring_slabs_out = pl.ring_slabs;
     if (pl.kernel == GEMM_PLAN_EMPTY) return hipSuccess;
-#ifdef MMDUET_DEBUG_VARIANTS
-    if (hipError_t e = hipSuccess; sizeof(T) == 2 && launch_debug_variant(p, a, st, &e)) return e;
-#endif
     if (!pl.valid()) return hipErrorInvalidValue;
     if (a.slabs_out && (pl.kernel == GEMM_K_GEMV16 || pl.kernel == GEMM_K_SKINNY || pl.kernel == GEMM_K_STREAM)) *a.slabs_out = pl.slabs;
     set_plan(a, pl);

@@ -295,8 +295,8 @@ static inline int ring_split_choice(const GemmArgs& a) {
     return sp;
 }
 // gemm_ringx_kernel.  flags: 16 = 8 waves, 256 x 256 tiles, three-slot ring, refill DMAs in the first rows of a step (every tower / projector GEMM, gate_up and split-K down of a
-// chunk); 17 = 4 waves, 256 x 128 tiles, two blocks per CU (a chunk's qkv / o_proj where 256 x 256 tiles cannot fill the device).  The other instantiations the template was built to
-// test (late refill, 32x32x16 MFMA, four slots) lost their A/B (header of gemm_ringx_kernel) and are no longer compiled into the library: their flags give an invalid plan.
+// chunk); 17 = 4 waves, 256 x 128 tiles, two blocks per CU (a chunk's qkv / o_proj where 256 x 256 tiles cannot fill the device).  The flag values of the alternatives that lost their
+// A/B and were removed (late refill, 32x32x16 MFMA, four slots: header of gemm_ringx_kernel) give an invalid plan.
 static inline GemmPlan plan_ring(const GemmArgs& a, int flags, int splits) {
     GemmPlan pl;
     int WN = 4;                                                              // the fp16 tower runs the production 8-wave instantiation

@@ -1,11 +1,10 @@
 #!/bin/bash
-# Anatomy of the small-S (per-frame / decode) split-KV attention: wall per shape, per-kernel durations, SQ counters, segment stamps (debug library).
+# Anatomy of the small-S (per-frame / decode) split-KV attention: wall per shape, per-kernel durations, SQ counters.
 # usage (GPU box): bash tools/attn_small_probe.sh <tag>        -> gpurun_out/<tag>_*
 tag=${1:-r05_small}
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 python3 $R/tools/bench_attn.py small > $O/${tag}_shapes.txt 2>&1
-[ -f $R/mmduet_amd/csrc/libmmduet_hip_timing.so ] && python3 $R/tools/attn_small_timing.py > $O/${tag}_timing.log 2>&1
 for shape in "49 15000" "1 15000"; do
   s=${shape// /_}
   rm -rf $O/kt_$tag
@@ -24,7 +23,7 @@ for shape in "49 15000" "1 15000"; do
     rm -rf $O/pmc_$tag
   done
 done
-tail -n +1 $O/${tag}_shapes.txt $O/${tag}_timing.log $O/${tag}_kernels_*.txt | cut -c1-220
+tail -n +1 $O/${tag}_shapes.txt $O/${tag}_kernels_*.txt | cut -c1-220
 echo "--- ring form (attn_gqa128_kernel<2,4,8>) forced for rows >= 256" >> $O/${tag}_shapes.txt
 python3 $R/tools/bench_attn.py small 2>&1 | grep "S=  49\|S=  64" >> $O/${tag}_shapes.txt
 tail -12 $O/${tag}_shapes.txt

@@ -48,8 +48,7 @@ if __name__ == '__main__':
     which = sys.argv[1] if len(sys.argv) > 1 else 'prod'
     if which == 'prod':
         rows = []
-        variants = [(0, 'auto'), (4, 'big'), (6, 'ring256'), (16, 'rx-8w'), (17, 'rx-4w'), (24, 'rx-8w-ns4'), (32, 'rx-8w-early'), (33, 'rx-4w-early'), (40, 'rx-8w-ns4-early'), (42, 'rx-8w-m32-ns4-early'), (93, 'rx-fine'),
-                    (7, 'ring256-splitK'), (44, 'rx-8w-ns4-early-splitK'), (49, 'rx-4w-nostagger'), (65, 'rx-4w-early-nostagger'), (96, 'DBG-x-contig'), (97, 'DBG-no-x'), (98, 'DBG-no-dma'), (99, 'DBG-no-epilogue'), (95, 'DBG-stores-pending'), (94, 'DBG-convert-no-store')]
+        variants = [(0, 'auto'), (4, 'big'), (6, 'ring256'), (32, 'rx-8w-early'), (33, 'rx-4w-early'), (7, 'ring256-splitK')]
         if len(sys.argv) > 3: variants = [v for v in variants if v[1] in sys.argv[3].split(',')]
         for M, shapes in ((25515, VIT), (1274, LLM[:4]), (1323, LLM[:4])):
             for name, N, K, epi in shapes:
@@ -72,7 +71,7 @@ if __name__ == '__main__':
     if which == 'ab':
         # interleaved A/B (guide rule 24): python tools/bench_gemm.py ab <variant,variant,...> [rounds] [out.json]; every round runs every variant on the same operands
         import statistics
-        names = {200: 'ringw-3s3b', 201: 'ringw-4s2b', 202: 'ringw-4s3b', 204: 'ringw-3s3b-splitK', 0: 'auto', 4: 'big', 32: 'rx-8w-early', 33: 'rx-4w-early', 40: 'rx-8w-ns4-early', 92: 'DBG-ns4-half-barriers', 93: 'rx-fine', 99: 'DBG-no-epilogue', 98: 'DBG-no-dma', 7: 'ring-splitK', 48: 'rx-8w-early-splitK'}
+        names = {0: 'auto', 4: 'big', 32: 'rx-8w-early', 33: 'rx-4w-early', 7: 'ring-splitK'}
         vs = [int(v) for v in sys.argv[2].split(',')]
         rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 7
         shapes = [(25515, 'vit_qkv', 3456, 1152, 'none'), (25515, 'vit_o_none', 1152, 1152, 'none'), (25515, 'vit_fc1', 4352, 1152, 'gelu_tanh'), (25515, 'vit_fc2', 1152, 4352, 'resid'), (25515, 'proj2', 3584, 3584, 'none'),
@@ -133,25 +132,9 @@ if __name__ == '__main__':
         if len(sys.argv) > 2:
             json.dump(dict(note='tools/bench_gemm.py llm: weight-streaming kernels, random operands; GB/s = algorithmic bytes (weights at their stored width + activations) / time', rows=rows),
                       open(sys.argv[2], 'w'), indent=1)
-    if which == 'stream':      # gemm_stream_kernel configuration sweep (DEBUG_VARIANTS build): python tools/bench_gemm.py stream [M]
-        import statistics
-        M = int(sys.argv[2]) if len(sys.argv) > 2 else 49
-        cfgs = {2: 'skinny (shipped r03)', 300: 'WK2 KS2 NB4', 301: 'WK1 KS4 NB3', 302: 'WK4 KS1 NB4', 303: 'WK2 KS4 NB3', 304: 'WK1 KS4 NB4', 305: 'WK4 KS2 NB3', 307: 'WK2 KS2 NB6',
-                320: 'WN5 / WN7x8 WK2 KS2 NB4', 321: 'WN5 WK3 / WN7x4', 322: 'DBG W only WN5 / WN7x8', 323: 'WN5 / WN7x8 WK1 KS4 NB3', 324: 'WN8 / WN7x16',
-                310: 'DBG W only WK2', 311: 'DBG W only WK1', 312: 'DBG no W WK2', 313: 'DBG no W WK1'}
-        for name, N, K, epi in LLM[:4]:
-            t = {v: [] for v in cfgs}
-            for r in range(5):
-                for v in cfgs:
-                    vv = v if v != 2 else (2 if epi == 'swiglu' else 5)
-                    try: t[v].append(run(ops, M, N, K, epi, vv, iters=8))
-                    except Exception as e: t[v].append(float('nan'))
-            for v, nm in cfgs.items():
-                med = statistics.median(t[v]); gb = N * K * 2 / 1e9
-                print(f'STREAM M={M:4d} {name:8s} {nm:22s} median {med*1e3:8.1f} us   {gb/med*1e3:7.0f} GB/s of weights   {run.plan if v == 300 else ""}', flush=True)
     if which == 'square':       # the guide's reference shapes (4096^3, 8192^3): where does the ring stand against its 256^2 8-phase template (1.33 / 1.47 PF, random operands)?
         for n in (2048, 4096, 8192):
-            for variant, vn in ((32, 'rx-8w-early'), (40, 'rx-8w-ns4-early'), (4, 'big')):
+            for variant, vn in ((32, 'rx-8w-early'), (4, 'big')):
                 ms = run(ops, n, n, n, 'none', variant, iters=10)
                 print(f'{n}^3 {vn:16s} {ms*1e3:9.1f} us  {2*n**3/ms/1e9:7.1f} TF  {2*n**3/ms/1e9/2500:5.3f}', flush=True)
     if which in ('big', 'all'):
