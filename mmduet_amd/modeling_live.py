@@ -448,6 +448,7 @@ class VideoHeadLiveLlavaQwenForCausalLM:
         self._embed = _Embedding(self)
         self._tower = _VisionTower(self)
         self._finalized = False
+        self._loaded_shapes = {}          # name -> shape of what load_tensor handed over (merge_lora checks an adapter against it)
         self.lm_loss_weight = self.video_loss_weight = 1
         # RoPE table with the reference's own expression (transformers qwen2/modeling_qwen2.py:84-85)
         d = config.head_dim
@@ -503,8 +504,13 @@ class VideoHeadLiveLlavaQwenForCausalLM:
             check(lib().mmd_load_tensor(self._ctx, name.encode(), _ptr(t), _TORCH2MMD[t.dtype], shape, t.ndim, on_dev), self._ctx, f'load {name}')
             if on_dev:
                 torch.cuda.current_stream(self.device).synchronize()
+            self._loaded_shapes[name] = tuple(t.shape)
 
     def merge_lora(self, weight_name: str, A: torch.Tensor, B: torch.Tensor, scale: float):
+        """W += scale * B @ A on a loaded matrix.  The ABI carries r alone (the library copies r*in and out*r floats from the host pointers), so the pair is checked
+        here against the shape the tensor was loaded with, or the one the configuration gives it."""
+        from .weights import check_lora_shapes, expected_tensors
+        check_lora_shapes(weight_name, A, B, self._loaded_shapes.get(weight_name) or expected_tensors(self.config).get(weight_name))
         A = A.float().cpu().contiguous(); B = B.float().cpu().contiguous()
         with self._lock:
             self._bind_stream()

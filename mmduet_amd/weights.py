@@ -133,8 +133,8 @@ def load_lora_into(model, lora_dir):
     cfg = json.load(open(os.path.join(d, 'adapter_config.json')))
     scale = cfg['lora_alpha'] / cfg['r']
     path = os.path.join(d, 'adapter_model.safetensors')
-    A, B = {}, {}
-    need = set(expected_tensors(model.config))
+    A, B, saved = {}, {}, {}
+    need = expected_tensors(model.config)
     with safe_open(path, framework='pt', device='cpu') as sf:
         for key in sf.keys():
             name = key[len('base_model.model.'):] if key.startswith('base_model.model.') else key
@@ -148,12 +148,29 @@ def load_lora_into(model, lora_dir):
             else:
                 name = name.replace('.modules_to_save', '')
                 if name in need:
-                    model.load_tensor(name, sf.get_tensor(key))
-    for w in sorted(A):
+                    saved[name] = sf.get_tensor(key)
+    # the whole adapter is checked before the model sees any of it: the native merge is told r alone and reads r*in and out*r floats
+    for w in sorted(set(A) | set(B)):
         if w not in B:
             raise KeyError(f'LoRA adapter has lora_A but no lora_B for {w}')
+        if w not in A:
+            raise KeyError(f'LoRA adapter has lora_B but no lora_A for {w}')
+        check_lora_shapes(w, A[w], B[w], need.get(w))
+    for name, t in saved.items():
+        model.load_tensor(name, t)
+    for w in sorted(A):
         model.merge_lora(w, A[w], B[w], scale)
     return len(A)
+
+
+def check_lora_shapes(weight_name, A, B, target_shape=None):
+    """A [r, in], B [out, r] against the [out, in] matrix they are merged into (None: only against each other)."""
+    if A.ndim != 2 or B.ndim != 2:
+        raise ValueError(f'LoRA pair for {weight_name}: lora_A and lora_B must be matrices, got {tuple(A.shape)} and {tuple(B.shape)}')
+    if A.shape[0] != B.shape[1] or A.shape[0] < 1:
+        raise ValueError(f'LoRA pair for {weight_name}: lora_A {tuple(A.shape)} and lora_B {tuple(B.shape)} disagree on r')
+    if target_shape is not None and (len(target_shape) != 2 or tuple(target_shape) != (B.shape[0], A.shape[1])):
+        raise ValueError(f'LoRA pair for {weight_name}: lora_A {tuple(A.shape)}, lora_B {tuple(B.shape)} do not fit the {tuple(target_shape)} tensor')
 
 
 def save_checkpoint(named_tensors, out_dir, config=None):

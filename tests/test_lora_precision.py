@@ -34,27 +34,36 @@ def test_merged_bf16_weight_is_as_accurate_as_unmerged_bf16_execution(rel):
 
 @pytest.mark.gpu
 def test_merge_lora_bf16_against_unmerged_oracle():
-    """The real path (mmd_merge_lora on a bf16 context, then the model's GEMMs) against y = W x + s B (A x) in fp32 on the same bf16 tensors."""
-    import ctypes as C
+    """The real path (mmd_merge_lora on a bf16 context, then the model's GEMMs) against y = W x + s B (A x) in fp32 on the same bf16 tensors.  The GEMM's weight is the
+    matrix lora_merge_kernel wrote: W is loaded as the embedding table of a context whose vocabulary x hidden is N x K, merged there, finalized, and read back
+    bit for bit through mmd_embed_tokens."""
     from rawops import RawOps
-    from mmduet_amd._lib import lib, check
-    ops = RawOps(torch.bfloat16)
+    from helpers import product_config
+    from conftest import load_golden_weights
+    from mmduet_amd.modeling_live import VideoHeadLiveLlavaQwenForCausalLM
+    from mmduet_amd.weights import synthetic_weights
     g = torch.Generator().manual_seed(1)
     K, N, r, M, s = 1152, 512, 16, 64, 2.0
     W = (torch.randn(N, K, generator=g) * 0.02).bfloat16()
     A = (torch.randn(r, K, generator=g) / math.sqrt(K)).bfloat16()
     B = (torch.randn(N, r, generator=g) * 0.004).bfloat16()
     x = torch.randn(M, K, generator=g).bfloat16()
-    m = ops.m
-    shape = (C.c_int64 * 2)(N, K)
-    Wd = W.cuda()
-    check(lib().mmd_load_tensor(m._ctx, b'probe.weight', C.c_void_p(Wd.data_ptr()), 1, shape, 2, 1), m._ctx)
-    m.merge_lora('probe.weight', A.float(), B.float(), s)
-    # the merged tensor is not retrievable through the ABI; recompute what the kernel stores and run the production GEMM on it
-    merged = (W.float() + s * (B.float() @ A.float())).bfloat16()
-    Y = ops.gemm(x, merged, variant=0).float().cpu()
+    cfgd, _ = load_golden_weights('A')
+    pc = product_config(cfgd, vocab_size=N, hidden_size=K, num_attention_heads=9, num_key_value_heads=3, intermediate_size=128, num_hidden_layers=1)
+    m = VideoHeadLiveLlavaQwenForCausalLM(pc, torch_dtype=torch.bfloat16, max_vit_batch=2, max_step_tokens=64, kv_initial_tokens=256)
+    for name, t in synthetic_weights(pc, seed=1, device=m.device, dtype=torch.bfloat16):
+        m.load_tensor(name, t)
+    m.load_tensor('model.embed_tokens.weight', W.cuda())
+    m.merge_lora('model.embed_tokens.weight', A.float(), B.float(), s)
+    m.finalize()
+    merged = m.get_input_embeddings()(torch.arange(N))                     # what the kernel stored, on the device
+    exact_w = W.double() + s * (B.double() @ A.double())
+    assert merged.dtype == torch.bfloat16 and not torch.equal(merged.cpu(), W)
+    assert ((merged.cpu().double() - exact_w).abs() <= exact_w.abs() * 2.0 ** -8).all()          # it is the merge, to a bf16 rounding (tests/test_gpu_lora.py has the exact bound)
+    Y = RawOps.around(m).gemm(x, merged, variant=0).float().cpu()
     exact = x.float() @ (W.float() + s * (B.float() @ A.float())).T
     base = (x.float() @ W.float().T).bfloat16()
     t = (x.float() @ A.float().T).bfloat16()
     ref = (base.float() + ((t.float() @ B.float().T).bfloat16().float() * s).bfloat16().float()).bfloat16().float()
     assert (Y - exact).std().item() <= 1.15 * (ref - exact).std().item() + 1e-5
+    assert (Y - exact).std().item() < 0.8 * (base.float() - exact).std().item()          # and the adapter's signal is in what the GEMM computed
